@@ -16,10 +16,16 @@ value = proofs/s over all ranks. `prove_only_resident_witness` is the narrower r
 N ranks (BASELINE configs[3]): independent proofs per rank; every step's proof bytes are gathered over RCCL (to rank 0, the rank
 that consumes them) inside the timed region, overlapped with the next step's proving. No other data-path collective.
 
-Also reported (BASELINE configs[1], "NTT HBM GB/s vs peak"): the 2^20-point Goldilocks NTT + inverse over 128
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes the last timed step's
+proofs (dump_outputs). Every other leg runs only with --full: the engine clock beside the headline, proving from resident
+witnesses, the aggregation trees, the per-stage and witness-generation legs, the oracle and host-verifier checks of the
+headline's proof, the CPU baseline and the NTT below.
+
+Also reported with --full (BASELINE configs[1], "NTT HBM GB/s vs peak"): the 2^20-point Goldilocks NTT + inverse over 128
 columns; `roofline` is for that kernel pair, measured with HIP events on the launch stream by the library.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -225,6 +231,21 @@ def ntt_leg(pkg, gpu, log_n, batch, steps):
     return gbs, roof, ok, col0, out0
 
 
+DUMP_BUDGET = 60 << 20     # bytes of proofs.npy; --dump-outputs writes at most 64 MB in all
+
+
+def dump_outputs(out_dir, proofs):
+    """--dump-outputs: what the timed path handed its caller in its last step, proofs [m][proof_len] uint8, written as
+    DIR/proofs.npy (float32 byte values, exact) with DIR/proof_index.npy (float64), the rows of `proofs` kept: all of them while
+    they fit in DUMP_BUDGET, else a fixed seeded sample, so that two builds run with the same arguments dump the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    m, n = proofs.shape
+    k = min(m, DUMP_BUDGET // (4 * n))
+    idx = np.arange(m) if k == m else np.sort(np.random.default_rng(0).choice(m, k, replace=False))
+    np.save(os.path.join(out_dir, "proofs.npy"), proofs[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "proof_index.npy"), idx.astype(np.float64))
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N rank processes (fresh interpreters, created before this
     process makes any GPU or torch.cuda call), one per GPU, with the torchrun environment; rank 0 prints the JSON line.
@@ -283,7 +304,13 @@ def main():
     ap.add_argument("--no-tree", action="store_true", help="skip the 64-leaf aggregation-tree leg (BASELINE configs[4])")
     ap.add_argument("--all-gather", action="store_true", help="every rank receives every rank's proof bytes (all_gather) instead of the default gather to rank 0, "
                                                                "the rank that consumes them (SURVEY.md 8e)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run every other leg: engine clock, resident-witness proving, aggregation "
+                                                         "trees, per-stage and witness-generation legs, oracle checks, host verifier, CPU baseline, NTT roofline "
+                                                         "(--no-tree, --headline-only, --no-cpu-baseline and --no-ntt select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the proofs of the last timed step to DIR/proofs.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args.gpus))       # this process never touches a GPU: the ranks are fresh interpreters
@@ -355,6 +382,7 @@ def main():
     pool_gen = ThreadPoolExecutor(max_workers=1)
     gathered = None
     step_gather = None
+    last_block = None
 
     def barrier():
         if not use_torch:
@@ -409,7 +437,7 @@ def main():
         ring = min(k, AHEAD + 1)            # step j writes block j % ring, i.e. reuses step j - AHEAD - 1's
         # the workers write each step's proofs straight into one pinned block per ring slot; with several ranks that block is
         # what the step's collective sends (sharding.ProofBlockGather: no per-proof copies on the host)
-        nonlocal gathered, step_gather
+        nonlocal gathered, step_gather, last_block
         if step_gather is None or len(step_gather.send) < ring:
             if use_torch:
                 step_gather = pkg.sharding.ProofBlockGather(S, proof_len, dist if world > 1 else None, coll_dev, blocks=AHEAD + 1,
@@ -437,19 +465,22 @@ def main():
                 gather_ms.append((time.perf_counter() - _tg) * 1e3)
             last = sg.slot(j % ring, 0).tobytes()
             step_done.append(time.perf_counter())
+        last_block = (k - 1) % ring
         return last
 
     step_done = []
     gather_ms = []
     proof = run_steps(max(args.warmup, 1))
     barrier()
-    hclk = EngineClock(gpu)
+    hclk = EngineClock(gpu) if args.full else contextlib.nullcontext()
     with hclk:
         t0 = time.perf_counter()
         proof = run_steps(args.steps)
         barrier()
         dt = time.perf_counter() - t0
-    headline_clock = hclk.summary(skip_s=0.3)
+    headline_clock = hclk.summary(skip_s=0.3) if args.full else None
+    if args.dump_outputs and rank == 0:     # before any later leg reuses the ring's blocks
+        dump_outputs(args.dump_outputs, gathered.numpy().reshape(-1, proof_len) if world > 1 else step_gather.gather(last_block)[0])
     # spread: the timed region cut into three consecutive windows of steps (this rank's clock)
     windows = []
     if args.steps >= 3:
@@ -473,38 +504,39 @@ def main():
 
     extra = {}
     ok = True
-    # the same S proofs from FULL witnesses already resident in HBM (stage s1 outside the timed region): what rounds 1-3 reported
-    # as the headline; kept as a sub-key. The witnesses are generated here by the batched PartialWitness entry.
-    w_all = gpu.alloc(S * mat_bytes)
-    gen_c = pkg.Circuit(gpu, pack, max_batch=min(S, 32))
-    vals_all = np.stack([leaf.commit(x)[1] for x in inputs_all])
-    pis_mat = np.stack([leaf.commit(x)[2] for x in inputs_all])
-    for k0 in range(0, S, 32):
-        k1 = min(S, k0 + 32)
-        st_ = gen_c.generate_witness_partial_batch_dev(cells0, vals_all[k0:k1], pis_mat[k0:k1], w_all.ptr + k0 * mat_bytes)
-        if any(st_):
-            raise SystemExit("bench.py: witness generation failed: " + gpu.last_error())
-    gpu.sync()
-    gen_c.close()
-    wires0 = np.empty((nw_, n_), dtype=np.uint64)                # witness 0 as proved, for the oracle's byte-parity check below
-    gpu._check(gpu.lib.qpgpu_memcpy_d2h(gpu.ctx, wires0.ctypes.data, w_all.ptr, mat_bytes))
-    wires, pis = wires0, pis0
-    w_t = gpu.to_device(wires0)
-    rs = max(6, min(args.steps, 20))
-    run_steps(2, resident=w_all)
-    barrier()
-    tr = time.perf_counter()
-    proof_res = run_steps(rs, resident=w_all)
-    barrier()
-    dtr = time.perf_counter() - tr
-    if world > 1:
-        t = torch.tensor([dtr], dtype=torch.float64, device=coll_dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dtr = float(t.item())
-    ok = ok and proof_res == proof
-    extra["prove_only_resident_witness"] = {"proofs_per_s": round(rs * S * world / dtr, 1), "steps": rs,
-                                            "note": "stages s2..s12 from full witnesses resident in HBM (the timed region of rounds 1-3's headline); "
-                                                    "`value` above also contains commit (a1, host) and witness generation (s1, device)"}
+    if args.full:
+        # the same S proofs from FULL witnesses already resident in HBM (stage s1 outside the timed region): what rounds 1-3 reported
+        # as the headline; kept as a sub-key. The witnesses are generated here by the batched PartialWitness entry.
+        w_all = gpu.alloc(S * mat_bytes)
+        gen_c = pkg.Circuit(gpu, pack, max_batch=min(S, 32))
+        vals_all = np.stack([leaf.commit(x)[1] for x in inputs_all])
+        pis_mat = np.stack([leaf.commit(x)[2] for x in inputs_all])
+        for k0 in range(0, S, 32):
+            k1 = min(S, k0 + 32)
+            st_ = gen_c.generate_witness_partial_batch_dev(cells0, vals_all[k0:k1], pis_mat[k0:k1], w_all.ptr + k0 * mat_bytes)
+            if any(st_):
+                raise SystemExit("bench.py: witness generation failed: " + gpu.last_error())
+        gpu.sync()
+        gen_c.close()
+        wires0 = np.empty((nw_, n_), dtype=np.uint64)                # witness 0 as proved, for the oracle's byte-parity check below
+        gpu._check(gpu.lib.qpgpu_memcpy_d2h(gpu.ctx, wires0.ctypes.data, w_all.ptr, mat_bytes))
+        wires, pis = wires0, pis0
+        w_t = gpu.to_device(wires0)
+        rs = max(6, min(args.steps, 20))
+        run_steps(2, resident=w_all)
+        barrier()
+        tr = time.perf_counter()
+        proof_res = run_steps(rs, resident=w_all)
+        barrier()
+        dtr = time.perf_counter() - tr
+        if world > 1:
+            t = torch.tensor([dtr], dtype=torch.float64, device=coll_dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dtr = float(t.item())
+        ok = ok and proof_res == proof
+        extra["prove_only_resident_witness"] = {"proofs_per_s": round(rs * S * world / dtr, 1), "steps": rs,
+                                                "note": "stages s2..s12 from full witnesses resident in HBM (the timed region of rounds 1-3's headline); "
+                                                        "`value` above also contains commit (a1, host) and witness generation (s1, device)"}
 
     # ---- BASELINE configs[4]: the recursive aggregator tree, shape-equivalent ----
     # 64 leaf proofs -> 8 private batches of 8 (2^16 rows, zero-knowledge) -> 1 public batch of 8 (2^16 rows), reference
@@ -513,7 +545,7 @@ def main():
     # the proving work per level. Witness generation of the recursive verifiers (host work in the reference) is not included.
     tree = None
     tree_check = None
-    if not args.no_tree:
+    if args.full and not args.no_tree:
         agg = pkg.aggregation
         # recursive-verifier gate mix (Poseidon, extension arithmetic, Reducing*, RandomAccess, Exponentiation, PoseidonMds,
         # CosetInterpolation); private batch: standard_recursion_zk_config with 60 routed wires
@@ -589,7 +621,7 @@ def main():
     # proofs carrying the PUBLIC-BATCH logic; every wrapper also verifies the Merkle half of its inner proofs in-circuit and replays
     # their transcripts (qpgpu_wrapper_circuit_build; what that leaves out is listed in csrc/wrapper_circuit.cpp).
     attest = None
-    if not args.no_tree:
+    if args.full and not args.no_tree:
         try:
             at = pkg.recursion.AttestingTree(pkg, gpu, per_batch=8, batches=8, rank=rank, world=world, aggregator_address=bytes([3] * 32), zero_knowledge=True)
             # the same 64 inputs on every rank: 48 real spends of ONE block (their leaves in one 4-ary tree of depth 3), every spend
@@ -652,7 +684,7 @@ def main():
             at.close()
         except pkg.QpGpuError as e:
             attest = {"error": str(e)}
-    if rank == 0:
+    if rank == 0 and args.full:
         extra["attesting_tree"] = attest
         extra["aggregation_tree"] = tree
         ok = ok and tree_check is not False

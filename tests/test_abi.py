@@ -46,11 +46,11 @@ def test_product_does_not_reference_oracle():
                     assert "liboracle" not in text and "oracle_binding" not in text and "load_oracle" not in text, os.path.join(dp, f)
 
 
-def test_c_example_compiles_against_the_header():
+def test_c_example_compiles_against_the_header(tmp_path):
     """examples/prove_example.c uses only include/qpgpu.h; it must compile and link with plain gcc."""
-    import subprocess, tempfile
+    import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = os.path.join(tempfile.gettempdir(), "qpgpu_prove_example")
+    out = str(tmp_path / "qpgpu_prove_example")
     subprocess.check_call(["gcc", "-O2", "-Wall", "-I", os.path.join(root, "include"), os.path.join(root, "examples", "prove_example.c"),
                            "-L", os.path.join(root, "qp-zk-circuits_amd"), "-lqpgpu",
                            "-Wl,-rpath," + os.path.join(root, "qp-zk-circuits_amd"), "-o", out])

@@ -86,14 +86,13 @@ def test_two_layers_from_circuit_inputs(pkg, gpu, orc):
     pub.close(); priv.close()
 
 
-def test_batch_c_example_runs(pkg):
+def test_batch_c_example_runs(pkg, tmp_path):
     """examples/batch_prove_example.c: both aggregation layers from plain C — CircuitInputs -> leaf proofs -> zero-knowledge private
     batch -> public batch, circuits built by the library, blinding wires and public inputs on the device, every proof verified."""
     import os
     import subprocess
-    import tempfile
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = os.path.join(tempfile.gettempdir(), "qpgpu_batch_prove_example_gpu")
+    out = str(tmp_path / "qpgpu_batch_prove_example_gpu")
     subprocess.check_call(["gcc", "-O2", "-I", os.path.join(root, "include"), os.path.join(root, "examples", "batch_prove_example.c"),
                            "-L", os.path.join(root, "qp-zk-circuits_amd"), "-lqpgpu", "-lpthread",
                            "-Wl,-rpath," + os.path.join(root, "qp-zk-circuits_amd"), "-o", out])

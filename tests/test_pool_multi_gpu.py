@@ -4,7 +4,6 @@ GPU — which exercises everything but the second physical device: job routing (
 PartialWitness jobs), byte parity of every proof with the oracle, failure isolation, draining at destroy."""
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -81,10 +80,10 @@ def test_pool_without_workspace_refuses_host_jobs(pkg, gpu):
     pool.close(); d.free()
 
 
-def test_leaf_c_example_runs(pkg):
+def test_leaf_c_example_runs(pkg, tmp_path):
     """examples/leaf_prove_example.c: the leaf path from plain C over devices {0, 0} (no Python, no torch in the process)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = os.path.join(tempfile.gettempdir(), "qpgpu_leaf_prove_example_gpu")
+    out = str(tmp_path / "qpgpu_leaf_prove_example_gpu")
     subprocess.check_call(["gcc", "-O2", "-I", os.path.join(root, "include"), os.path.join(root, "examples", "leaf_prove_example.c"),
                            "-L", os.path.join(root, "qp-zk-circuits_amd"), "-lqpgpu", "-lpthread",
                            "-Wl,-rpath," + os.path.join(root, "qp-zk-circuits_amd"), "-o", out])

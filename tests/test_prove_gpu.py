@@ -222,11 +222,11 @@ def test_largest_private_batch_shape(pkg, gpu, orc):
     oc.close()
 
 
-def test_c_example_runs(pkg):
+def test_c_example_runs(pkg, tmp_path):
     """The same flow from plain C through the C ABI (no Python in the loop)."""
-    import os, subprocess, tempfile
+    import os, subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = os.path.join(tempfile.gettempdir(), "qpgpu_prove_example_gpu")
+    out = str(tmp_path / "qpgpu_prove_example_gpu")
     subprocess.check_call(["gcc", "-O2", "-I", os.path.join(root, "include"), os.path.join(root, "examples", "prove_example.c"),
                            "-L", os.path.join(root, "qp-zk-circuits_amd"), "-lqpgpu",
                            "-Wl,-rpath," + os.path.join(root, "qp-zk-circuits_amd"), "-o", out])

@@ -17,12 +17,15 @@ first = "--first-layout" in args
 excerpt = args[args.index("--excerpt") + 1] if "--excerpt" in args else None
 files = [a for a in args if a.endswith(".hip")]
 src = files[0] if files else os.path.join(ROOT, "qp-zk-circuits_amd", "csrc", "merkle_kernels_mx.hip")
-asm = os.path.join(tempfile.gettempdir(), os.path.basename(src) + (".first" if first else "") + ".hazard.s")
+work = tempfile.TemporaryDirectory(prefix="mfma_hazard_")   # per run: a fixed name in the shared temp dir belongs to whoever built first
+asm = os.path.join(work.name, os.path.basename(src) + (".first" if first else "") + ".hazard.s")
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--offload-device-only", "-S", src, "-o", asm, "-I", os.path.dirname(os.path.abspath(src))]
 if first:
     cmd.insert(1, "-DPMF_NO_KEEPALIVE")
 subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-text = open(asm).read()
+with open(asm) as f:
+    text = f.read()
+work.cleanup()
 
 REG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 def regs(op):
