@@ -57,6 +57,17 @@ int qpgpu_verifier_query_indices(const qpgpu_verifier *v, const uint8_t *proof, 
 int qpgpu_verifier_verify_many(const qpgpu_verifier *v, const uint8_t *const *proofs, const size_t *lens, size_t count, unsigned threads,
                                int *results, char *err);
 
+/* verify_many with the query rounds of every proof on ctx's GPU: Merkle paths of the four initial oracles and of every FRI
+ * round, FRI continuation, coset interpolation at beta, final polynomial. The transcript, proof of work and quotient identity
+ * run on up to `threads` host threads (0 = all cores). results[i] and the return value / err are exactly what
+ * qpgpu_verifier_verify_many would give. reasons: NULL, or count * QPGPU_VERIFY_ERR_CAP bytes; row i receives the text
+ * qpgpu_verifier_verify gives for proof i ("" when accepted). The verifier's hasher must equal the context's
+ * (qpgpu_ctx_set_hasher), else QPGPU_EINVAL. count == 0 returns 0 at once. A HIP error returns QPGPU_EDEVICE with
+ * qpgpu_last_error(ctx) set; the proofs not decided by then get results[i] = QPGPU_EDEVICE (no host fallback). Synchronous on
+ * the ctx stream; same threading rule as every ctx call. */
+int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, struct qpgpu_ctx *ctx, const uint8_t *const *proofs, const size_t *lens,
+                                      size_t count, unsigned threads, int *results, char *reasons, char *err);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,9 @@ extern "C" {
                                  hasher_params: *const u64, n_params: usize, out: *mut *mut QpgpuVerifier, err: *mut c_char) -> i32;
     pub fn qpgpu_verifier_free(v: *mut QpgpuVerifier);
     pub fn qpgpu_verifier_verify(v: *const QpgpuVerifier, proof: *const u8, len: usize, err: *mut c_char) -> i32;
+    // the query rounds of a batch of proofs on ctx's GPU; results / err as qpgpu_verifier_verify_many, reasons: count * 200 bytes or null
+    pub fn qpgpu_verifier_verify_many_device(v: *const QpgpuVerifier, ctx: *mut QpgpuCtx, proofs: *const *const u8, lens: *const usize, count: usize,
+                                             threads: u32, results: *mut i32, reasons: *mut c_char, err: *mut c_char) -> i32;
     // include/qpgpu.h — the proving pool over one GPU or several: one queue, a worker set per device,
     // proofs written into the caller's host buffers
     pub fn qpgpu_pool_create_multi(devices: *const i32, n_devices: u32, pack: *const u64, n_words: usize, workers_per_device: u32,

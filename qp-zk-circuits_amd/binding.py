@@ -47,6 +47,7 @@ def load_library():
         "qpgpu_verifier_constants_sigmas_cap": (c.c_int, [vp, vp, c.c_size_t]),
         "qpgpu_verifier_verify": (c.c_int, [vp, c.c_char_p, c.c_size_t, c.c_char_p]),
         "qpgpu_verifier_verify_many": (c.c_int, [vp, vp, vp, c.c_size_t, c.c_uint, vp, c.c_char_p]),
+        "qpgpu_verifier_verify_many_device": (c.c_int, [vp, vp, vp, vp, c.c_size_t, c.c_uint, vp, vp, c.c_char_p]),
         "qpgpu_ctx_create": (c.c_int, [c.c_int, c.POINTER(vp)]),
         "qpgpu_ctx_destroy": (None, [vp]),
         "qpgpu_last_error": (c.c_char_p, [vp]),
@@ -517,17 +518,29 @@ class Verifier:
         self.reason = err.value.decode()
         return rc == 0
 
-    def verify_many(self, proofs, threads=0):
-        """[accepted?] per proof, verified on up to `threads` host threads (0 = all cores); .reason names the first rejection."""
+    def verify_many(self, proofs, threads=0, gpu=None):
+        """[accepted?] per proof, verified on up to `threads` host threads (0 = all cores); .reason names the first rejection.
+        gpu: a QpGpu whose device runs the query rounds (qpgpu_verifier_verify_many_device; its hasher must be the verifier's);
+        then .reasons holds the verifier's text for every proof ("" when accepted) and .results the codes."""
         n = len(proofs)
         if n == 0:
+            self.reasons, self.results = [], []
             return []
         bufs = [bytes(p) for p in proofs]
         ptrs = (ctypes.c_char_p * n)(*bufs)
         lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
         res = (ctypes.c_int * n)()
         err = ctypes.create_string_buffer(200)
-        self.lib.qpgpu_verifier_verify_many(self.h, ptrs, lens, n, threads, res, err)
+        if gpu is None:
+            self.lib.qpgpu_verifier_verify_many(self.h, ptrs, lens, n, threads, res, err)
+        else:
+            rows = ctypes.create_string_buffer(200 * n)
+            rc = self.lib.qpgpu_verifier_verify_many_device(self.h, gpu.ctx, ptrs, lens, n, threads, res, rows, err)
+            if rc not in (0, -6):
+                raise QpGpuError(rc, err.value.decode())
+            raw = rows.raw
+            self.reasons = [raw[200 * i:200 * (i + 1)].split(b"\0", 1)[0].decode() for i in range(n)]
+            self.results = list(res)
         self.reason = err.value.decode()
         return [r == 0 for r in res]
 

@@ -73,6 +73,10 @@ struct qpgpu_ctx {
     // `rows` pieces of `width` bytes, `src_pitch` bytes apart on the device, packed back to back on the host
     int read_back_2d(void *host_dst, const void *dev_src, size_t src_pitch, size_t width, size_t rows);
     int upload(const std::vector<uint64_t> &host, uint64_t **dptr);
+    // batch verification workspace (verify_device.cpp): pinned staging of one chunk of proofs + records, and its device copy
+    // with the verdict codes behind it; grow-only, freed at destroy
+    void *vd_pin = nullptr, *vd_dev = nullptr;
+    size_t vd_pin_bytes = 0, vd_dev_bytes = 0;
 };
 
 // HIP's current device is per host thread: every entry point selects the ctx's GPU first

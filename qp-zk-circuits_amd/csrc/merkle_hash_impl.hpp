@@ -17,6 +17,7 @@ struct Poseidon2QP {  // the plug when the context's block is qp-poseidon-core's
     static __device__ __forceinline__ void permute(u64 (&s)[12], const poseidon2::Params *p2) { poseidon2::permute_qp(s, *p2); }
 };
 
+#ifndef MERKLE_HASH_PLUGS_ONLY   // a unit with kernels of its own (verify_kernels.hip) takes the permutation plugs alone
 // tree of the batch a global leaf / node index belongs to (counts are powers of two)
 __device__ __forceinline__ u32 ilog2_64(u64 x) { return 63u - (u32)__clzll((long long)x); }
 
@@ -150,5 +151,6 @@ hipError_t hash_launch_pow(const PowArgs &a, dim3 g, const HasherDev &h, hipStre
     else hipLaunchKernelGGL((pow_kernel<PoseidonV1>), g, dim3(256), 0, st, a, h.p2);
     return hipGetLastError();
 }
+#endif  // MERKLE_HASH_PLUGS_ONLY
 
 }  // namespace

@@ -88,6 +88,8 @@ void qpgpu_ctx_destroy(qpgpu_ctx *ctx) {
     if (ctx->d_p2) (void)hipFree(ctx->d_p2);
     if (ctx->d_p2_app) (void)hipFree(ctx->d_p2_app);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
+    if (ctx->vd_pin) (void)hipHostFree(ctx->vd_pin);
+    if (ctx->vd_dev) (void)hipFree(ctx->vd_dev);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }

@@ -16,6 +16,7 @@
 #include "circuit.hpp"
 #include "gl64.hpp"
 #include "poseidon.hpp"
+#include "verifier.hpp"
 #include "verify_math.hpp"
 
 using gl::e2;
@@ -107,13 +108,6 @@ void ntt(std::vector<u64> &a, unsigned log_n, u64 root) {
 using vmath::gate_constraints;
 
 }  // namespace
-
-struct qpgpu_verifier {
-    CircuitPack pack;
-    hasher::Config hash;
-    std::vector<u64> cs_cap;
-    size_t proof_size = 0;
-};
 
 namespace {
 
@@ -251,7 +245,10 @@ int qpgpu_verifier_query_indices(const qpgpu_verifier *v, const uint8_t *proof, 
     if (!v || !out || cap < v->pack.num_query_rounds) return fail(err, QPGPU_EINVAL, "query_indices: null argument or room for fewer than num_query_rounds indices");
     return verify_impl(v, proof, len, err, out);
 }
-static int verify_impl(const qpgpu_verifier *v, const uint8_t *proof, size_t len, char *err, uint64_t *indices_out) {
+}  // extern "C"
+
+// the head of verification: parse, transcript, proof of work, quotient identity at zeta, the query indices
+int verify_head(const qpgpu_verifier *v, const uint8_t *proof, size_t len, char *err, VerifyHead &h) {
     if (!v || !proof) return fail(err, QPGPU_EINVAL, "null argument");
     const CircuitPack &c = v->pack;
     const Hash H{&v->hash};
@@ -263,16 +260,17 @@ static int verify_impl(const qpgpu_verifier *v, const uint8_t *proof, size_t len
     const size_t n_rounds = c.arity_bits.size();
 
     Reader b{proof, len};
-    std::vector<u64> wires_cap(cap_words), zs_cap(cap_words), q_cap(cap_words);
+    std::vector<u64> &wires_cap = h.wires_cap, &zs_cap = h.zs_cap, &q_cap = h.q_cap;
+    wires_cap.assign(cap_words, 0); zs_cap.assign(cap_words, 0); q_cap.assign(cap_words, 0);
     b.vec(wires_cap.data(), cap_words); b.vec(zs_cap.data(), cap_words); b.vec(q_cap.data(), cap_words);
     std::vector<e2> o_cs, o_w, o_zs, o_zn, o_pp, o_q;
     b.exts(o_cs, ncs); b.exts(o_w, NW); b.exts(o_zs, nch); b.exts(o_zn, nch); b.exts(o_pp, nch * npp); b.exts(o_q, nq);
-    std::vector<u64> fri_caps(cap_words * n_rounds);
+    std::vector<u64> &fri_caps = h.fri_caps;
+    fri_caps.assign(cap_words * n_rounds, 0);
     b.vec(fri_caps.data(), cap_words * n_rounds);
-    const size_t queries_pos = b.pos;
+    h.queries_pos = b.pos;
     const size_t salt = c.zero_knowledge ? 4 : 0;
     const size_t widths[4] = {ncs, NW + salt, nch * (1 + npp) + salt, nq + salt};
-    const size_t polys[4] = {ncs, NW, nch * (1 + npp), nq};
     {
         size_t q = 0, lvl = L;
         for (size_t w : widths) q += w * 8 + 1 + (L - cap_h) * 32;
@@ -281,7 +279,7 @@ static int verify_impl(const qpgpu_verifier *v, const uint8_t *proof, size_t len
     }
     size_t fin_bits = d;
     for (u64 ab : c.arity_bits) fin_bits -= ab;
-    std::vector<e2> final_poly;
+    std::vector<e2> &final_poly = h.final_poly;
     b.exts(final_poly, (size_t)1 << fin_bits);
     u64 pow_witness = b.word();
     std::vector<u64> pis(c.num_public_inputs + 1);
@@ -302,10 +300,11 @@ static int verify_impl(const qpgpu_verifier *v, const uint8_t *proof, size_t len
     ch.observe(zs_cap.data(), cap_words);
     for (size_t k = 0; k < nch; k++) alphas[k] = ch.get();
     ch.observe(q_cap.data(), cap_words);
-    const e2 zeta = ch.get_ext();
+    const e2 zeta = h.zeta = ch.get_ext();
     ch.observe(o_cs); ch.observe(o_w); ch.observe(o_zs); ch.observe(o_pp); ch.observe(o_q); ch.observe(o_zn);
-    const e2 fri_alpha = ch.get_ext();
-    std::vector<e2> fri_betas(n_rounds);
+    const e2 fri_alpha = h.fri_alpha = ch.get_ext();
+    std::vector<e2> &fri_betas = h.fri_betas;
+    fri_betas.assign(n_rounds, E(0));
     for (size_t r = 0; r < n_rounds; r++) { ch.observe(fri_caps.data() + r * cap_words, cap_words); fri_betas[r] = ch.get_ext(); }
     ch.observe(final_poly);
     ch.observe(&pow_witness, 1);
@@ -333,21 +332,46 @@ static int verify_impl(const qpgpu_verifier *v, const uint8_t *proof, size_t len
     }
 
     // ---- FRI ----
-    e2 red0 = E(0), red1 = E(0);     // reduced openings: sum_j opening_j alpha^j, batch 0 in oracle order, batch 1 = Zs at g zeta
+    e2 &red0 = h.red0, &red1 = h.red1;     // reduced openings: sum_j opening_j alpha^j, batch 0 in oracle order, batch 1 = Zs at g zeta
     {
+        red0 = red1 = E(0);
         const std::vector<e2> *parts[5] = {&o_cs, &o_w, &o_zs, &o_pp, &o_q};
         for (int p = 5; p-- > 0;) for (size_t j = parts[p]->size(); j-- > 0;) red0 = red0 * fri_alpha + (*parts[p])[j];
         for (size_t j = nch; j-- > 0;) red1 = red1 * fri_alpha + o_zn[j];
     }
-    const e2 g_zeta = scale(zeta, gl::root_of_unity(d));
-    const e2 alpha_nch = gl::e2_pow(fri_alpha, nch);
-    const u64 *caps0[4] = {v->cs_cap.data(), wires_cap.data(), zs_cap.data(), q_cap.data()};
-    Reader q{proof, len, queries_pos};
+    h.g_zeta = scale(zeta, gl::root_of_unity(d));
+    h.alpha_nch = gl::e2_pow(fri_alpha, nch);
+    h.x_indices.resize(c.num_query_rounds);      // the query rounds do not touch the transcript: draw them all first
+    for (size_t qi = 0; qi < c.num_query_rounds; qi++) h.x_indices[qi] = (size_t)(ch.get() % lde_n);
+    return QPGPU_OK;
+}
+
+extern "C" {
+
+static int verify_impl(const qpgpu_verifier *v, const uint8_t *proof, size_t len, char *err, uint64_t *indices_out) {
+    VerifyHead h;
+    const int head = verify_head(v, proof, len, err, h);
+    if (head != QPGPU_OK) return head;
+    if (indices_out) { for (size_t qi = 0; qi < h.x_indices.size(); qi++) indices_out[qi] = h.x_indices[qi]; return QPGPU_OK; }
+    const CircuitPack &c = v->pack;
+    const Hash H{&v->hash};
+    const unsigned d = (unsigned)c.degree_bits, rb = (unsigned)c.rate_bits, cap_h = (unsigned)c.cap_height, L = d + rb;
+    const size_t NW = c.num_wires, nch = c.num_challenges;
+    const size_t npp = c.num_partial_products, ncs = c.num_cs_cols();
+    const size_t cap_words = ((size_t)1 << cap_h) * 4, nq = nch * c.quotient_degree_factor;
+    const size_t n_rounds = c.arity_bits.size();
+    const size_t salt = c.zero_knowledge ? 4 : 0;
+    const size_t widths[4] = {ncs, NW + salt, nch * (1 + npp) + salt, nq + salt};
+    const size_t polys[4] = {ncs, NW, nch * (1 + npp), nq};
+    const std::vector<size_t> &x_indices = h.x_indices;
+    const std::vector<u64> &fri_caps = h.fri_caps;
+    const std::vector<e2> &fri_betas = h.fri_betas, &final_poly = h.final_poly;
+    const e2 zeta = h.zeta, g_zeta = h.g_zeta, fri_alpha = h.fri_alpha, alpha_nch = h.alpha_nch, red0 = h.red0, red1 = h.red1;
+
+    const u64 *caps0[4] = {v->cs_cap.data(), h.wires_cap.data(), h.zs_cap.data(), h.q_cap.data()};
+    Reader q{proof, len, h.queries_pos};
     std::vector<u64> row(ncs + NW + nch * (1 + npp) + nq + 16), path(64 * 4), ev(64);
     const u64 w_lde = gl::root_of_unity(L);
-    std::vector<size_t> x_indices(c.num_query_rounds);      // the loop below does not touch the transcript: draw them all first
-    for (size_t qi = 0; qi < c.num_query_rounds; qi++) x_indices[qi] = (size_t)(ch.get() % lde_n);
-    if (indices_out) { for (size_t qi = 0; qi < c.num_query_rounds; qi++) indices_out[qi] = x_indices[qi]; return QPGPU_OK; }
     for (size_t qi = 0; qi < c.num_query_rounds; qi++) {
         size_t x_index = x_indices[qi];
         const u64 *rows[4];

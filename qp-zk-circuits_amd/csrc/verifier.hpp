@@ -1,0 +1,30 @@
+// verifier.hpp — the verifier handle and the head of verification (verifier.cpp), shared by the host query loop and the device
+// query rounds (verify_device.cpp).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+#include "circuit.hpp"
+#include "gl64.hpp"
+#include "poseidon.hpp"
+
+struct qpgpu_verifier {
+    CircuitPack pack;
+    hasher::Config hash;
+    std::vector<gl::u64> cs_cap;
+    size_t proof_size = 0;
+};
+
+// Everything the query rounds need, as the head of verify_impl leaves it: the transcript replayed through the proof of work,
+// the quotient identity checked at zeta, the query indices drawn.
+struct VerifyHead {
+    std::vector<gl::u64> wires_cap, zs_cap, q_cap, fri_caps;   // 4 << cap_height words each (fri_caps: one per round)
+    std::vector<gl::e2> final_poly, fri_betas;
+    gl::e2 zeta, g_zeta, fri_alpha, alpha_nch, red0, red1;    // red0 / red1: reduced openings at zeta / g zeta
+    std::vector<size_t> x_indices;                            // num_query_rounds
+    size_t queries_pos = 0;                                   // byte offset of the first query round
+};
+
+// 0, or the code and reason the verifier gives for a proof that fails before its query rounds (size, layout, non-canonical
+// element, proof of work, quotient identity)
+int verify_head(const qpgpu_verifier *v, const uint8_t *proof, size_t len, char *err, VerifyHead &h);

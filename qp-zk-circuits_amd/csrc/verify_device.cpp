@@ -1,0 +1,259 @@
+// verify_device.cpp — qpgpu_verifier_verify_many_device (include/qpgpu_verify.h): verify_many with the query rounds of every
+// proof on the context's GPU. Three phases per chunk of proofs:
+//   1. on host threads, the head of verification (verifier.cpp: verify_head — parse, transcript, proof of work, quotient
+//      identity, query indices); a proof that passes is copied into the pinned staging buffer with its record (VerifyLayout)
+//   2. one host-to-device copy of the chunk, the query-round kernels (verify_kernels.hip), the per-query verdicts read back
+//      through the context's pinned read-back
+//   3. per proof, the first failing query's verdict written out in the host verifier's words
+// The verdict and reason of every proof are the host verifier's (qpgpu_verifier_verify); the host query loop is the specification.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+#include "../../include/qpgpu.h"
+#include "../../include/qpgpu_verify.h"
+#include "ctx.hpp"
+#include "verifier.hpp"
+#include "verify_kernels.hpp"
+
+using gl::u64;
+
+namespace {
+
+int vfail(char *err, int code, const char *fmt, ...) {
+    if (err) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(err, QPGPU_VERIFY_ERR_CAP, fmt, ap);
+        va_end(ap);
+    }
+    return code;
+}
+
+bool same_hasher(const hasher::Config &a, const hasher::Config &b) {
+    if (a.kind != b.kind) return false;
+    if (a.kind != hasher::POSEIDON2) return true;
+    return memcmp(a.p2.rc_ext, b.p2.rc_ext, sizeof a.p2.rc_ext) == 0 && memcmp(a.p2.rc_int, b.p2.rc_int, sizeof a.p2.rc_int) == 0 &&
+           memcmp(a.p2.diag_m1, b.p2.diag_m1, sizeof a.p2.diag_m1) == 0 && memcmp(a.p2.m4, b.p2.m4, sizeof a.p2.m4) == 0;
+}
+
+// where every opening of a query round sits: the proof layout of verifier.cpp (proof_size_of, verify_impl)
+bool make_layout(const CircuitPack &c, size_t proof_size, VerifyLayout &lay) {
+    const size_t n_rounds = c.arity_bits.size();
+    if (n_rounds > (size_t)VERIFY_MAX_ROUNDS || proof_size >= ((size_t)1 << 31)) return false;
+    const unsigned cap_h = (unsigned)c.cap_height, L = (unsigned)(c.degree_bits + c.rate_bits);
+    const size_t ncs = c.num_cs_cols(), NW = c.num_wires, nch = c.num_challenges, npp = c.num_partial_products;
+    const size_t nq = nch * c.quotient_degree_factor, salt = c.zero_knowledge ? 4 : 0, cap_bytes = ((size_t)1 << cap_h) * 32;
+    const size_t widths[4] = {ncs, NW + salt, nch * (1 + npp) + salt, nq + salt};
+    const size_t polys[4] = {ncs, NW, nch * (1 + npp), nq};
+    const size_t openings = (ncs + NW + 2 * nch + nch * npp + nq) * 16;
+    const size_t fri_caps_pos = 3 * cap_bytes + openings;
+    memset(&lay, 0, sizeof lay);
+    size_t off = 0;
+    for (int o = 0; o < 4; o++) {
+        lay.op[o] = {(uint32_t)off, (uint32_t)widths[o], L - cap_h, 0, o == 0 ? VERIFY_CAP_VERIFIER : (uint32_t)((o - 1) * cap_bytes)};
+        lay.polys[o] = (uint32_t)polys[o];
+        off += widths[o] * 8 + 1 + (L - cap_h) * 32;
+    }
+    unsigned lvl = L, shift = 0, fin_bits = (unsigned)c.degree_bits;
+    for (size_t r = 0; r < n_rounds; r++) {
+        const unsigned ab = (unsigned)c.arity_bits[r];
+        lvl -= ab; shift += ab; fin_bits -= ab;
+        lay.arity_bits[r] = ab;
+        lay.op[4 + r] = {(uint32_t)off, 2u << ab, lvl - cap_h, shift, (uint32_t)(fri_caps_pos + r * cap_bytes)};
+        off += ((size_t)1 << ab) * 16 + 1 + (lvl - cap_h) * 32;
+    }
+    lay.nq = (uint32_t)c.num_query_rounds;
+    lay.n_open = (uint32_t)(4 + n_rounds);
+    lay.queries_pos = (uint32_t)(fri_caps_pos + n_rounds * cap_bytes);
+    lay.q_bytes = (uint32_t)off;
+    lay.final_off = (uint32_t)(lay.queries_pos + lay.nq * off);
+    lay.final_n = 1u << fin_bits;
+    lay.stride_words = (uint32_t)((proof_size + 7) / 8 + 1);
+    lay.rec_words = vrec_words((uint32_t)n_rounds, lay.nq);
+    lay.log_lde = L;
+    lay.nch = (uint32_t)nch;
+    return true;
+}
+
+// the host verifier's words for a query round's first failing check (verifier.cpp: verify_impl)
+void query_reason(char *out, size_t qi, uint32_t code) {
+    const unsigned kind = code >> 8, at = code & 0xff;
+    switch (kind) {
+    case VQ_ORACLE_PLEN: vfail(out, 0, "query %zu: Merkle path length of oracle %d out of range", qi, (int)at); break;
+    case VQ_ORACLE_PATH: vfail(out, 0, "query %zu: Merkle path of initial oracle %d does not lead to its cap", qi, (int)at); break;
+    case VQ_ROUND_PLEN: vfail(out, 0, "query %zu: Merkle path length of FRI round %zu out of range", qi, (size_t)at); break;
+    case VQ_ROUND_CONT: vfail(out, 0, "query %zu: FRI round %zu does not continue the previous evaluation", qi, (size_t)at); break;
+    case VQ_ROUND_PATH: vfail(out, 0, "query %zu: Merkle path of FRI round %zu does not lead to its cap", qi, (size_t)at); break;
+    default: vfail(out, 0, "query %zu: the final polynomial does not match the last FRI round", qi); break;
+    }
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+void host_stat(qpgpu_ctx *ctx, const char *name, double ms) {
+    if (!ctx->profiling) return;
+    ctx->kstats[name].ms += ms;
+    ctx->kstats[name].launches++;
+}
+
+constexpr size_t CHUNK_PROOFS = 1024;
+constexpr size_t CHUNK_BYTES = (size_t)256 << 20;
+
+}  // namespace
+
+extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_ctx *ctx, const uint8_t *const *proofs, const size_t *lens,
+                                                 size_t count, unsigned threads, int *results, char *reasons, char *err) {
+    if (!v || !ctx) return vfail(err, QPGPU_EINVAL, "null argument");
+    if (count == 0) return QPGPU_OK;
+    if (!proofs || !lens || !results) return vfail(err, QPGPU_EINVAL, "null argument");
+    if (!same_hasher(v->hash, ctx->hasher)) {
+        ctx->fail(QPGPU_EINVAL, "verify_many_device: the verifier's hasher is not the context's (qpgpu_ctx_set_hasher)");
+        return vfail(err, QPGPU_EINVAL, "%s", ctx->err.c_str());
+    }
+    VerifyLayout lay;
+    if (!make_layout(v->pack, v->proof_size, lay)) {
+        ctx->fail(QPGPU_EINVAL, "verify_many_device: circuit outside the supported range");
+        return vfail(err, QPGPU_EINVAL, "%s", ctx->err.c_str());
+    }
+    if (threads == 0) threads = std::max(1u, std::thread::hardware_concurrency());
+    const size_t cap_words = v->cs_cap.size(), SW = lay.stride_words, RW = lay.rec_words, nq = lay.nq;
+    const size_t chunk = std::max<size_t>(1, std::min(CHUNK_PROOFS, CHUNK_BYTES / (SW * 8)));
+    const size_t pin_bytes = (chunk * (SW + RW) + cap_words) * 8;
+    const size_t mcode_off = (pin_bytes + 255) & ~(size_t)255, qcode_off = (mcode_off + chunk * nq * lay.n_open + 255) & ~(size_t)255;
+    const size_t dev_bytes = qcode_off + chunk * nq * 4;
+    std::vector<uint32_t> qcodes(chunk * nq);
+    std::vector<char> own_reasons;          // the caller's rows, or rows of our own for err
+    if (!reasons) own_reasons.assign(count * QPGPU_VERIFY_ERR_CAP, 0);
+    char *const rows = reasons ? reasons : own_reasons.data();
+    auto reason_row = [&](size_t i) { return rows + i * QPGPU_VERIFY_ERR_CAP; };
+
+    // a HIP failure: the proofs not yet decided get QPGPU_EDEVICE; err carries the context's message. Proofs below `headed`
+    // whose result is not EDEVICE were decided on the host.
+    size_t chunk_from = 0, headed = 0;
+    auto device_fail = [&](int rc) {
+        for (size_t i = chunk_from; i < count; i++)
+            if (i >= headed || results[i] == QPGPU_EDEVICE) { results[i] = QPGPU_EDEVICE; reason_row(i)[0] = 0; }
+        return vfail(err, rc, "%s", ctx->err.c_str());
+    };
+    {
+        const hipError_t e = hipSetDevice(ctx->device);
+        if (e != hipSuccess) return device_fail(ctx->hip_fail(e, "hipSetDevice"));
+    }
+    if (int rc = merkle_ensure_constants(ctx)) return device_fail(rc);
+    if (pin_bytes > ctx->vd_pin_bytes) {
+        hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess && ctx->vd_pin) { e = hipHostFree(ctx->vd_pin); ctx->vd_pin = nullptr; ctx->vd_pin_bytes = 0; }
+        if (e == hipSuccess) e = hipHostMalloc(&ctx->vd_pin, pin_bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { ctx->vd_pin = nullptr; return device_fail(ctx->hip_fail(e, "hipHostMalloc (verification staging)")); }
+        ctx->vd_pin_bytes = pin_bytes;
+    }
+    if (dev_bytes > ctx->vd_dev_bytes) {
+        hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess && ctx->vd_dev) { e = hipFree(ctx->vd_dev); ctx->vd_dev = nullptr; ctx->vd_dev_bytes = 0; }
+        if (e == hipSuccess) e = hipMalloc(&ctx->vd_dev, dev_bytes);
+        if (e != hipSuccess) { ctx->vd_dev = nullptr; return device_fail(ctx->hip_fail(e, "hipMalloc (verification workspace)")); }
+        ctx->vd_dev_bytes = dev_bytes;
+    }
+    uint8_t *const dev = (uint8_t *)ctx->vd_dev;
+    u64 *const pin = (u64 *)ctx->vd_pin;
+
+    for (size_t c0 = 0; c0 < count; c0 += chunk) {
+        const size_t n = std::min(chunk, count - c0);
+        chunk_from = headed = c0;
+        // chunk layout, host and device alike: n proofs (SW words each), n records (RW words each), the constants/sigmas cap
+        u64 *const h_proofs = pin, *const h_recs = pin + n * SW, *const h_cap = h_recs + n * RW;
+        std::memcpy(h_cap, v->cs_cap.data(), cap_words * 8);
+
+        // ---- phase 1: the head of every proof on host threads; the survivors staged ----
+        auto t0 = std::chrono::steady_clock::now();
+        std::atomic<size_t> next{0};
+        std::atomic<bool> layout_mismatch{false};
+        auto work = [&] {
+            char local[QPGPU_VERIFY_ERR_CAP];
+            VerifyHead h;
+            for (size_t k = next.fetch_add(1); k < n; k = next.fetch_add(1)) {
+                const size_t i = c0 + k;
+                u64 *rec = h_recs + k * RW;
+                rec[VREC_LIVE] = 0;
+                char *row = reason_row(i);
+                row[0] = 0;
+                if (!proofs[i]) { results[i] = QPGPU_EINVAL; continue; }
+                local[0] = 0;
+                const int rc = verify_head(v, proofs[i], lens[i], local, h);
+                if (rc != QPGPU_OK) { results[i] = rc; std::memcpy(row, local, QPGPU_VERIFY_ERR_CAP); continue; }
+                if (h.queries_pos != lay.queries_pos) { layout_mismatch = true; results[i] = QPGPU_EDEVICE; continue; }
+                u64 *dst = h_proofs + k * SW;
+                dst[SW - 2] = 0; dst[SW - 1] = 0;          // the partial last word and the padding word
+                std::memcpy(dst, proofs[i], lens[i]);
+                const gl::e2 ex[6] = {h.zeta, h.g_zeta, h.fri_alpha, h.alpha_nch, h.red0, h.red1};
+                for (int e = 0; e < 6; e++) { rec[1 + 2 * e] = ex[e].a; rec[2 + 2 * e] = ex[e].b; }
+                for (size_t r = 0; r < h.fri_betas.size(); r++) { rec[VREC_BETAS + 2 * r] = h.fri_betas[r].a; rec[VREC_BETAS + 2 * r + 1] = h.fri_betas[r].b; }
+                for (size_t q = 0; q < nq; q++) rec[VREC_BETAS + 2 * h.fri_betas.size() + q] = h.x_indices[q];
+                rec[VREC_LIVE] = 1;
+                results[i] = QPGPU_EDEVICE;                 // until the device has decided
+            }
+        };
+        const unsigned nt = (unsigned)std::min<size_t>(threads, n);
+        std::vector<std::thread> pool;
+        try {
+            for (unsigned t = 1; t < nt; t++) pool.emplace_back(work);
+        } catch (...) {}                 // no more threads to be had: the ones that started (and this one) drain the queue
+        work();
+        for (auto &t : pool) t.join();
+        headed = c0 + n;
+        host_stat(ctx, "verify_many_device.head", ms_since(t0));
+        if (layout_mismatch) {
+            ctx->fail(QPGPU_EINVAL, "verify_many_device: the proof layout of the verifier and the device path disagree");
+            return device_fail(QPGPU_EINVAL);
+        }
+        bool any = false;
+        for (size_t k = 0; k < n && !any; k++) any = h_recs[k * RW + VREC_LIVE] != 0;
+        if (!any) continue;
+
+        // ---- phase 2: one copy of the chunk, the query-round kernels, the verdicts back ----
+        t0 = std::chrono::steady_clock::now();
+        const size_t bytes = (n * (SW + RW) + cap_words) * 8;
+        hipError_t e = hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return device_fail(ctx->hip_fail(e, "hipMemcpyAsync (proofs of the chunk)"));
+        if (ctx->profiling) {
+            if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return device_fail(ctx->hip_fail(e, "hipStreamSynchronize"));
+            host_stat(ctx, "verify_many_device.upload", ms_since(t0));
+            t0 = std::chrono::steady_clock::now();
+        }
+        const u64 *d_proofs = (const u64 *)dev, *d_recs = d_proofs + n * SW, *d_cap = d_recs + n * RW;
+        uint8_t *d_mcodes = dev + mcode_off;
+        uint32_t *d_qcodes = (uint32_t *)(dev + qcode_off);
+        e = verify_query_rounds(lay, d_proofs, d_recs, d_cap, (uint32_t)n, d_mcodes, d_qcodes, ctx->hasher_dev(), ctx->stream);
+        if (e != hipSuccess) return device_fail(ctx->hip_fail(e, "verify_query_rounds"));
+        if (int rc = ctx->read_back(qcodes.data(), d_qcodes, n * nq * 4)) return device_fail(rc);
+        host_stat(ctx, "verify_many_device.kernels", ms_since(t0));
+
+        // ---- phase 3: the first failing query of each proof, in the host verifier's words ----
+        t0 = std::chrono::steady_clock::now();
+        for (size_t k = 0; k < n; k++) {
+            if (!h_recs[k * RW + VREC_LIVE]) continue;
+            const size_t i = c0 + k;
+            results[i] = QPGPU_OK;
+            for (size_t q = 0; q < nq; q++) {
+                const uint32_t code = qcodes[k * nq + q];
+                if (!code) continue;
+                results[i] = QPGPU_EVERIFY;
+                query_reason(reason_row(i), q, code);
+                break;
+            }
+        }
+        host_stat(ctx, "verify_many_device.reasons", ms_since(t0));
+    }
+    for (size_t i = 0; i < count; i++)
+        if (results[i]) return vfail(err, QPGPU_EVERIFY, "proof %zu: %.170s", i, reason_row(i));
+    return QPGPU_OK;
+}
