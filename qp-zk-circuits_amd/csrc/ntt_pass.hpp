@@ -40,6 +40,22 @@ struct NttPassArgs {
     const uint64_t *in_scale_b;
 };
 
+// Column-resident coset LDE (ntt_lde_column.hip): 2^log_n_in coefficients per column, 2^rate_bits cosets, leaf (bit-reversed)
+// slot order. One workgroup per (column, coset); grid.z = proof of a lockstep batch.
+struct NttLdeColumnArgs {
+    const uint64_t *in;
+    uint64_t *out;             // 16-byte aligned, as are the two output strides
+    uint64_t in_col_stride, out_col_stride;
+    uint64_t in_proof_stride, out_proof_stride;
+    const uint64_t *scale;     // [2^rate_bits][2^log_n_in]: (shift w_L^k)^i, L = log_n_in + rate_bits
+    const uint64_t *tw_outer;  // [2^(log_n_in - 8)][256]: w_(2^log_n_in)^(m brev(j)), the twiddle behind the first round
+    const uint64_t *tw_inner;  // [16][16]: w_256^(n brev(j)), behind the second
+    uint32_t ncols;
+    uint32_t rate_bits;
+    uint32_t xcd_map;          // 1 (ncols a multiple of 8): the cosets of a column share a workgroup index mod 8
+};
+hipError_t ntt_lde_column_launch(const NttLdeColumnArgs &a, unsigned log_n_in, uint32_t n_proofs, hipStream_t st);
+
 bool ntt_pass_uses_split(int ka, int kb);   // split 32-bit LDS exchange (half the LDS per workgroup) for this pass shape
 unsigned ntt_pass_row_pitch(int ka, int kb, int log_t);
 size_t ntt_pass_lds_bytes(int ka, int kb, int log_t);

@@ -111,6 +111,72 @@ int pick_log_t(int ka, int kb, u64 lanes_total) {
     return log_t;
 }
 
+// a table that is not a plain powers table: built once per context and key
+template <class Build>
+int cached_table(qpgpu_ctx *ctx, const std::string &key, Build build, const uint64_t **out) {
+    auto it = ctx->ntt_tables.find(key);
+    if (it == ctx->ntt_tables.end()) {
+        auto t = std::make_shared<NttTables>();
+        int rc = ctx->upload(build(), &t->d);
+        if (rc) return rc;
+        ctx->ntt_tables[key] = t;
+        it = ctx->ntt_tables.find(key);
+    }
+    *out = it->second->d;
+    return QPGPU_OK;
+}
+
+unsigned brev_bits(unsigned x, unsigned bits) {
+    unsigned r = 0;
+    for (unsigned i = 0; i < bits; i++) r |= ((x >> i) & 1u) << (bits - 1 - i);
+    return r;
+}
+
+// QPGPU_NTT_LDE_COLUMN: 1 (default) proof-sized coset LDEs run column-resident in one launch (ntt_lde_column.hip); 0 restores the
+// two generic passes; 2 keeps the new kernel but maps workgroups to (column, coset) in plain order (measurements only).
+int lde_column_mode() { static const int m = env_int("QPGPU_NTT_LDE_COLUMN", 1); return m; }
+
+// Tables and launch of the column-resident LDE: 2^d coefficients per column -> 2^(d + r) values on shift <w_(d+r)>, leaf order.
+int lde_column_run(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned d, unsigned r, size_t batch, u64 shift,
+                   u64 in_cs, u64 out_cs, uint32_t nproofs, u64 in_ps, u64 out_ps) {
+    const u64 n = 1ull << d;
+    NttLdeColumnArgs a{};
+    a.in = d_in; a.out = d_out;
+    a.in_col_stride = in_cs; a.out_col_stride = out_cs;
+    a.in_proof_stride = in_ps; a.out_proof_stride = out_ps;
+    a.ncols = (uint32_t)batch; a.rate_bits = r;
+    a.xcd_map = (lde_column_mode() == 1 && batch % 8 == 0) ? 1 : 0;
+    const std::string dr = std::to_string(d) + "_" + std::to_string(r);
+    QP_TRY_NTT(cached_table(ctx, "lcs" + std::to_string(shift) + "_" + dr, [&] {
+        std::vector<uint64_t> t((size_t)n << r);
+        const u64 wL = gl::root_of_unity(d + r);
+        u64 base = gl::canon(shift);                                       // shift * w_L^k
+        for (u64 k = 0; k < (1ull << r); k++) {
+            u64 acc = 1;
+            for (u64 i = 0; i < n; i++) { t[(size_t)(k << d) + i] = gl::canon(acc); acc = gl::mul(acc, base); }
+            base = gl::mul(base, wL);
+        }
+        return t;
+    }, &a.scale));
+    QP_TRY_NTT(cached_table(ctx, "lco" + std::to_string(d), [&] {
+        std::vector<uint64_t> w = powers(gl::root_of_unity(d), n), t(n);
+        for (u64 j = 0; j < (n >> 8); j++)
+            for (u64 m = 0; m < 256; m++) t[j * 256 + m] = w[m * brev_bits((unsigned)j, d - 8)];
+        return t;
+    }, &a.tw_outer));
+    QP_TRY_NTT(cached_table(ctx, "lci", [&] {
+        std::vector<uint64_t> w = powers(gl::root_of_unity(8), 256), t(256);
+        for (u64 j = 0; j < 16; j++)
+            for (u64 m = 0; m < 16; m++) t[j * 16 + m] = w[m * brev_bits((unsigned)j, 4)];
+        return t;
+    }, &a.tw_inner));
+    ctx->prof_begin("ntt_lde_column");
+    hipError_t le = ctx->plan_only ? hipSuccess : ntt_lde_column_launch(a, d, nproofs, ctx->stream);
+    ctx->prof_end();
+    QP_HIP(ctx, le);
+    return QPGPU_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -230,6 +296,25 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
         static hipError_t init_err = hipSuccess;
         std::call_once(once, [] { init_err = ntt_pass_init(); });
         QP_HIP(ctx, init_err);
+    }
+
+    // proof-sized coset LDE in leaf order: one launch, no intermediate (ntt_lde_column.hip). Everything else, and buffers the
+    // kernel's 16-byte stores or its read-while-others-write order do not suit, stays on the generic passes.
+    if (lde_column_mode() && !inverse && out_bitrev && coset && log_n_in >= 11 && log_n_in <= 13 && L > log_n_in && L - log_n_in <= 3) {
+        const u64 in_cs = g.in_col_stride ? g.in_col_stride : n_in, out_cs = g.out_col_stride ? g.out_col_stride : N;
+        const u64 in_span = (g.nproofs - 1) * g.in_ps + (batch - 1) * in_cs + n_in, out_span = (g.nproofs - 1) * g.out_ps + (batch - 1) * out_cs + N;
+        const bool aligned = ((uintptr_t)d_out % 16 == 0) && out_cs % 2 == 0 && g.out_ps % 2 == 0;
+        bool disjoint = d_in + in_span <= d_out || d_out + out_span <= d_in;
+        if (!disjoint && g.nproofs > 1 && g.in_ps == g.out_ps) {
+            // a lockstep batch keeps input and output in one workspace per proof: the regions interleave without touching
+            const int64_t ps = (int64_t)g.in_ps, delta = d_out - d_in, nb = (int64_t)g.nproofs;
+            const int64_t in_one = (int64_t)((batch - 1) * in_cs + n_in), out_one = (int64_t)((batch - 1) * out_cs + N);
+            disjoint = true;
+            for (int64_t e = -(nb - 1); e <= nb - 1 && disjoint; e++)
+                if (e * ps < delta + out_one && delta < e * ps + in_one) disjoint = false;
+        }
+        if (aligned && disjoint)
+            return lde_column_run(ctx, d_in, d_out, log_n_in, L - log_n_in, batch, coset_shift, in_cs, out_cs, g.nproofs, g.in_ps, g.out_ps);
     }
 
     const std::string dir = inverse ? "i" : "f";
