@@ -12,13 +12,9 @@
 #include <map>
 #include <string>
 #include <vector>
+#include "batch_host.hpp"
 
-namespace {
-
-constexpr uint64_t P = 0xFFFFFFFF00000001ull;
-constexpr int ERR_INVALID = -1, ERR_UNSAT = -4;
-
-int fail(char *err, int code, const char *fmt, ...) {
+int batch::fail(char *err, int code, const char *fmt, ...) {
     if (err) {
         va_list ap;
         va_start(ap, fmt);
@@ -27,6 +23,12 @@ int fail(char *err, int code, const char *fmt, ...) {
     }
     return code;
 }
+using batch::fail;
+
+namespace {
+
+constexpr uint64_t P = 0xFFFFFFFF00000001ull;
+constexpr int ERR_INVALID = -1, ERR_UNSAT = -4;
 
 using Digest = std::array<uint64_t, 4>;
 Digest digest_at(const uint64_t *p) { return {p[0], p[1], p[2], p[3]}; }

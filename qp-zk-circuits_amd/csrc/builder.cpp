@@ -640,20 +640,11 @@ std::string Builder::build(CircuitPack &pack) {
     // commitment, which is computed at load time on the device. Here: the proof-system hash of the shape words and of a running
     // hash over the constants/sigmas VALUES, which binds the transcript to this circuit. NOT the fork's formula.
     {
-        auto hash_no_pad = [](const u64 *in, size_t cnt, u64 out[4]) {
-            u64 st[12] = {0};
-            for (size_t i = 0; i < cnt; i += 8) {
-                const size_t len = std::min<size_t>(8, cnt - i);
-                for (size_t k = 0; k < len; k++) st[k] = gl::canon(in[i + k]);
-                hasher::host_permute(st);
-            }
-            for (int i = 0; i < 4; i++) out[i] = st[i];
-        };
         u64 vh[4];
-        hash_no_pad(pack.constants_sigmas.data(), pack.constants_sigmas.size(), vh);
+        hasher::hash_no_pad(hasher::process_default(), pack.constants_sigmas.data(), pack.constants_sigmas.size(), vh);
         const u64 shape[12] = {degree_bits, NW, R, pack.num_public_inputs, pack.num_selectors, (u64)pack.gates.size(), pack.zero_knowledge,
                                0x51504342ull /* "BCPQ": built by cb::Builder */, vh[0], vh[1], vh[2], vh[3]};
-        hash_no_pad(shape, 12, pack.circuit_digest);
+        hasher::hash_no_pad(hasher::process_default(), shape, 12, pack.circuit_digest);
     }
     return pack.validate();
 }

@@ -14,6 +14,7 @@ void witness_plan_free(WitnessPlan *p);
 struct qpgpu_circuit {
     qpgpu_ctx *ctx = nullptr;
     CircuitPack pack;
+    proof_layout::Proof layout;      // byte layout of this circuit's proofs
     std::vector<void *> allocs;
     // witness-derived regions: overwritten by qpgpu_circuit_scrub, by qpgpu_circuit_free, and after every proof of the
     // host-buffer entry qpgpu_prove. The _dev / batch / pool entries leave them resident between proofs (the next proof

@@ -89,9 +89,13 @@ int oracle_commit_values(qpgpu_ctx *ctx, const u64 *d_values, PolyOracle &o, con
 }
 
 namespace {
+proof_layout::Fri proof_part(const FriParams &p, const std::vector<size_t> &leaf_widths) {
+    return proof_layout::fri_part(p.degree_bits, p.rate_bits, p.cap_h, std::vector<uint64_t>(p.arity_bits.begin(), p.arity_bits.end()), p.num_queries, leaf_widths);
+}
 struct Layout {
     size_t comp, fin, vals, coeffs0, coeffs1, gather, alpha, ws;
     std::vector<size_t> digests, leafrows;
+    proof_layout::Fri proof;
     size_t gather_words;
     // batch-level tables, offsets from the end of the per-proof blocks
     size_t t_points, t_shifts, t_betas, pow_states, pow_bases, pow_results, qidx, total;
@@ -103,15 +107,15 @@ Layout layout(const FriParams &p, const std::vector<size_t> &leaf_widths, size_t
     size_t off = 0;
     auto take = [&](size_t words) { size_t o = off; off += (words + 1) & ~(size_t)1; return o; };   // 16-byte aligned
     l.comp = take(2 * n); l.fin = take(2 * n); l.vals = take(2 * lde_n); l.coeffs0 = take(2 * n); l.coeffs1 = take(2 * n);
-    size_t gw = 0;
-    for (size_t w : leaf_widths) gw += w + (size_t)(L - p.cap_h) * 4;
     unsigned lvl = L;
     for (unsigned a : p.arity_bits) {
         lvl -= a;
         l.digests.push_back(take(digest_words(lvl, p.cap_h)));
         l.leafrows.push_back(take((size_t)2 << (lvl + a)));
-        gw += (2ull << a) + (size_t)(lvl - p.cap_h) * 4;
     }
+    l.proof = proof_part(p, leaf_widths);
+    size_t gw = 0;      // every opened row and path of a proof, four words per sibling
+    for (const proof_layout::Opening &o : l.proof.op) gw += o.row_words + o.path_len * 4;
     l.gather_words = gw * p.num_queries;
     l.gather = take(l.gather_words); l.alpha = take(2 * max_batch_polys);
     l.ws = off;
@@ -134,18 +138,12 @@ void FriWork::bind(u64 *base, const FriParams &p, const std::vector<size_t> &lea
     for (size_t o : l.digests) digests.push_back(base + o);
     for (size_t o : l.leafrows) leafrows.push_back(base + o);
     gather = base + l.gather; alpha_ext = (e2 *)(base + l.alpha);
-    gather_words = l.gather_words; max_batch_polys = mbp;
+    gather_words = l.gather_words; max_batch_polys = mbp; proof = l.proof;
     t_points = (e2 *)(base + l.t_points); t_shifts = (e2 *)(base + l.t_shifts); t_betas = (e2 *)(base + l.t_betas);
     pow_states = base + l.pow_states; pow_bases = base + l.pow_bases; pow_results = base + l.pow_results; qidx = base + l.qidx;
 }
 
-size_t fri_proof_bytes(const FriParams &p, const std::vector<size_t> &leaf_widths) {
-    const size_t cap = (1ull << p.cap_h) * 32, L = p.degree_bits + p.rate_bits;
-    size_t sz = 0, q = 0, lvl = L, fin = p.degree_bits;
-    for (size_t w : leaf_widths) q += w * 8 + 1 + (L - p.cap_h) * 32;
-    for (unsigned a : p.arity_bits) { sz += cap; lvl -= a; fin -= a; q += (16ull << a) + 1 + (lvl - p.cap_h) * 32; }
-    return sz + p.num_queries * q + (16ull << fin) + 8;
-}
+size_t fri_proof_bytes(const FriParams &p, const std::vector<size_t> &leaf_widths) { return proof_part(p, leaf_widths).total; }
 
 int fri_prove(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracles, size_t n_oracles,
               const std::vector<FriBatch> &batches, uint32_t nb, Challenger *chs, FriWork &w, Stager &stage, ByteWriter *outs) {
@@ -155,6 +153,7 @@ int fri_prove(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracl
     const u64 n = 1ull << d, lde_n = n << p.rate_bits;
     const size_t cap_words = (1ull << cap_h) * 4;
     if (nb == 0 || nb > w.nb_cap) return ctx->fail(QPGPU_EINVAL, "fri_prove: batch larger than the workspace");
+    if (w.proof.op.size() != n_oracles + p.arity_bits.size()) return ctx->fail(QPGPU_EINVAL, "fri_prove: workspace bound for other oracles or FRI rounds");
     for (size_t i = 0; i < n_oracles; i++) {
         if (oracles[i]->log_n != d || oracles[i]->rate_bits != p.rate_bits || oracles[i]->cap_h != cap_h)
             return ctx->fail(QPGPU_EINVAL, "fri_prove: oracle " + std::to_string(i) + " does not match the FRI parameters");
@@ -322,9 +321,9 @@ int fri_prove(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracl
     struct Sec { size_t off, words; bool is_path; };
     std::vector<Sec> secs;
     size_t goff = 0;
-    const uint32_t plen0 = L - cap_h;
     for (size_t i = 0; i < n_oracles; i++) {
         const PolyOracle *o = oracles[i];
+        const uint32_t plen0 = (uint32_t)w.proof.op[i].path_len;
         QP_HIP(ctx, pk_gather_rows(o->lde, lde_n, o->ncols, w.qidx, nqr, w.gather + goff, nb, o->ps_lde, w.ws, st));
         secs.push_back({goff, o->ncols, false}); goff += (size_t)o->ncols * nqr;
         if (o->salt) {
@@ -334,16 +333,13 @@ int fri_prove(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracl
         QP_HIP(ctx, pk_gather_paths(o->digests, lde_n, plen0, w.qidx, 0, nqr, w.gather + goff, nb, o->ps_digests, w.ws, st));
         secs.push_back({goff, (size_t)plen0 * 4, true}); goff += (size_t)plen0 * 4 * nqr;
     }
-    {
-        uint32_t sh = 0;
-        for (size_t r = 0; r < p.arity_bits.size(); r++) {
-            const uint32_t ab = p.arity_bits[r], width = 2u << ab, pl = tree_log_leaves[r] - cap_h;
-            sh += ab;
-            QP_HIP(ctx, pk_gather_leaf_rows(w.leafrows[r], width, w.qidx, sh, nqr, w.gather + goff, nb, w.ws, w.ws, st));
-            secs.push_back({goff, width, false}); goff += (size_t)width * nqr;
-            QP_HIP(ctx, pk_gather_paths(w.digests[r], 1ull << tree_log_leaves[r], pl, w.qidx, sh, nqr, w.gather + goff, nb, w.ws, w.ws, st));
-            secs.push_back({goff, (size_t)pl * 4, true}); goff += (size_t)pl * 4 * nqr;
-        }
+    for (size_t r = 0; r < p.arity_bits.size(); r++) {
+        const proof_layout::Opening &op = w.proof.op[n_oracles + r];
+        const uint32_t width = (uint32_t)op.row_words, pl = (uint32_t)op.path_len, sh = (uint32_t)op.shift;
+        QP_HIP(ctx, pk_gather_leaf_rows(w.leafrows[r], width, w.qidx, sh, nqr, w.gather + goff, nb, w.ws, w.ws, st));
+        secs.push_back({goff, width, false}); goff += (size_t)width * nqr;
+        QP_HIP(ctx, pk_gather_paths(w.digests[r], 1ull << tree_log_leaves[r], pl, w.qidx, sh, nqr, w.gather + goff, nb, w.ws, w.ws, st));
+        secs.push_back({goff, (size_t)pl * 4, true}); goff += (size_t)pl * 4 * nqr;
     }
     if (goff != w.gather_words) return ctx->fail(QPGPU_EDEVICE, "prove: internal gather size mismatch");
     std::vector<u64> gathered(goff * nb);

@@ -7,6 +7,7 @@
 // The hashing kernels take the permutation as a template plug (the fork may back the
 // same config with Poseidon2; that plug needs qp-poseidon-core's constants).
 #pragma once
+#include <stddef.h>
 #include "gl64.hpp"
 
 namespace poseidon {
@@ -457,4 +458,13 @@ const Config &process_default();
 void set_process_default(int kind, const poseidon2::Params *p);
 inline int kind() { return process_default().kind; }
 inline void host_permute(gl::u64 (&s)[12]) { process_default().permute(s); }
+// hash_n_to_hash_no_pad on the host: overwrite absorption, rate 8, no padding; the input need not be canonical
+inline void hash_no_pad(const Config &h, const gl::u64 *in, size_t n, gl::u64 out[4]) {
+    gl::u64 st[12] = {0};
+    for (size_t i = 0; i < n; i += 8) {
+        for (size_t k = 0; k < 8 && i + k < n; k++) st[k] = gl::canon(in[i + k]);
+        h.permute(st);
+    }
+    for (int i = 0; i < 4; i++) out[i] = st[i];
+}
 }  // namespace hasher

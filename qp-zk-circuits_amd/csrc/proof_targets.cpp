@@ -11,26 +11,19 @@
 // (integration/qpgpu_backend.rs), exactly as for the leaf circuit's targets (include/qpgpu_leaf.h), and
 // qpgpu_leaf_map_targets / qpgpu_generate_witness_partial_dev take it from there.
 #include "../../include/qpgpu_batch.h"
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
+#include "batch_host.hpp"
 #include "circuit.hpp"
+#include "proof_layout.hpp"
+
+using batch::fail;
 
 namespace {
 
 constexpr uint64_t P = 0xFFFFFFFF00000001ull;
-
-int fail(char *err, int code, const char *fmt, ...) {
-    if (err) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(err, QPGPU_BATCH_ERR_CAP, fmt, ap);
-        va_end(ap);
-    }
-    return code;
-}
 
 // vector lengths of a ProofWithPublicInputs (or of its target), in the order ensure_proof_shape_matches_targets visits them
 struct Shape {
@@ -84,39 +77,27 @@ struct Shape {
 // what add_virtual_proof_with_pis(common_data) allocates for a proof of the circuit `c`
 Shape target_shape(const CircuitPack &c) {
     Shape s;
-    const uint32_t cap = 1u << c.cap_height, nch = (uint32_t)c.num_challenges, salt = c.zero_knowledge ? 4 : 0;
-    const uint32_t L = (uint32_t)(c.degree_bits + c.rate_bits);
+    const proof_layout::Proof lay = proof_layout::of(c);
+    const uint32_t cap = (uint32_t)(lay.cap_bytes / 32);
     s.public_inputs = (uint32_t)c.num_public_inputs;
     s.wires_cap = s.zs_pp_cap = s.quotient_cap = cap;
-    s.openings[0] = (uint32_t)(c.num_selectors + c.num_constants); s.openings[1] = (uint32_t)c.num_routed_wires; s.openings[2] = (uint32_t)c.num_wires;
-    s.openings[3] = nch; s.openings[4] = nch; s.openings[5] = nch * (uint32_t)c.num_partial_products; s.openings[6] = (uint32_t)c.num_quotient_cols();
+    for (int i = 0; i < 7; i++) s.openings[i] = (uint32_t)lay.openings[i].count;
     s.openings[7] = s.openings[8] = 0;      // none of the reference's circuits registers a lookup table
-    s.commit_caps.assign(c.arity_bits.size(), cap);
+    s.commit_caps.assign(lay.fri.n_rounds(), cap);
     Shape::Round r;
-    const uint32_t widths[4] = {(uint32_t)c.num_cs_cols(), (uint32_t)c.num_wires + salt, (uint32_t)c.num_zs_pp_cols() + salt, (uint32_t)c.num_quotient_cols() + salt};
-    for (uint32_t w : widths) { r.evals.push_back(w); r.siblings.push_back(L - (uint32_t)c.cap_height); }
-    uint32_t lvl = L, fin = (uint32_t)c.degree_bits;
-    for (uint64_t ab : c.arity_bits) {
-        lvl -= (uint32_t)ab; fin -= (uint32_t)ab;
-        r.step_evals.push_back(1u << ab);                   // uncompressed query steps carry every evaluation of the coset
-        r.step_siblings.push_back(lvl - (uint32_t)c.cap_height);
+    for (size_t i = 0; i < lay.fri.op.size(); i++) {
+        const proof_layout::Opening &o = lay.fri.op[i];
+        if (i < 4) { r.evals.push_back((uint32_t)o.row_words); r.siblings.push_back((uint32_t)o.path_len); }
+        // uncompressed query steps carry every evaluation of the coset, as extension elements
+        else { r.step_evals.push_back((uint32_t)(o.row_words / 2)); r.step_siblings.push_back((uint32_t)o.path_len); }
     }
-    s.rounds.assign(c.num_query_rounds, r);
-    s.final_poly = 1u << fin;
+    s.rounds.assign(lay.fri.num_query_rounds, r);
+    s.final_poly = (uint32_t)lay.fri.final_len;
     return s;
 }
 
-struct Reader {
-    const uint8_t *p; size_t len, pos = 0; bool bad = false, noncanonical = false;
-    uint64_t word() {
-        if (pos + 8 > len) { bad = true; pos = len; return 0; }
-        uint64_t v; std::memcpy(&v, p + pos, 8); pos += 8;
-        if (v >= P) noncanonical = true;
-        return v;
-    }
-    uint8_t byte() { if (pos + 1 > len) { bad = true; return 0; } return p[pos++]; }
-    void words(std::vector<uint64_t> &out, size_t n) { for (size_t i = 0; i < n && !bad; i++) out.push_back(word()); }
-};
+using proof_layout::Reader;
+void read_words(Reader &b, std::vector<uint64_t> &out, size_t n) { for (size_t i = 0; i < n && !b.bad; i++) out.push_back(b.word()); }
 
 // a proof's field elements, vector by vector, as ProofWithPublicInputs::from_bytes(bytes, common_data) reads them
 // (util::serialization order): the only lengths the bytes carry are the Merkle paths'
@@ -131,33 +112,33 @@ std::string parse_proof(const CircuitPack &c, const uint8_t *bytes, size_t len, 
     const Shape t = target_shape(c);
     Reader b{bytes, len};
     out.shape = t;
-    for (int i = 0; i < 3; i++) b.words(out.caps[i], (size_t)t.wires_cap * 4);
+    for (int i = 0; i < 3; i++) read_words(b, out.caps[i], (size_t)t.wires_cap * 4);
     const int byte_order[7] = {0, 1, 2, 3, 4, 5, 6};
-    for (int i : byte_order) b.words(out.openings[i], (size_t)t.openings[i] * 2);
-    b.words(out.commit_caps, (size_t)t.commit_caps.size() * t.wires_cap * 4);
+    for (int i : byte_order) read_words(b, out.openings[i], (size_t)t.openings[i] * 2);
+    read_words(b, out.commit_caps, (size_t)t.commit_caps.size() * t.wires_cap * 4);
     out.rounds.assign(t.rounds.size(), Parsed::Round());
     for (size_t q = 0; q < t.rounds.size() && !b.bad; q++) {
         Parsed::Round &r = out.rounds[q];
         Shape::Round &sr = out.shape.rounds[q];
         for (size_t j = 0; j < t.rounds[q].evals.size(); j++) {
-            r.evals.emplace_back(); b.words(r.evals.back(), t.rounds[q].evals[j]);
+            r.evals.emplace_back(); read_words(b, r.evals.back(), t.rounds[q].evals[j]);
             const uint8_t n_sib = b.byte();                   // write_merkle_proof's one-byte length
             sr.siblings[j] = n_sib;
-            r.siblings.emplace_back(); b.words(r.siblings.back(), (size_t)n_sib * 4);
+            r.siblings.emplace_back(); read_words(b, r.siblings.back(), (size_t)n_sib * 4);
         }
         for (size_t j = 0; j < t.rounds[q].step_evals.size(); j++) {
-            r.step_evals.emplace_back(); b.words(r.step_evals.back(), (size_t)t.rounds[q].step_evals[j] * 2);
+            r.step_evals.emplace_back(); read_words(b, r.step_evals.back(), (size_t)t.rounds[q].step_evals[j] * 2);
             const uint8_t n_sib = b.byte();
             sr.step_siblings[j] = n_sib;
-            r.step_siblings.emplace_back(); b.words(r.step_siblings.back(), (size_t)n_sib * 4);
+            r.step_siblings.emplace_back(); read_words(b, r.step_siblings.back(), (size_t)n_sib * 4);
         }
     }
-    b.words(out.final_poly, (size_t)t.final_poly * 2);
+    read_words(b, out.final_poly, (size_t)t.final_poly * 2);
     out.pow_witness = b.word();
     // the public inputs take what is left: their count is the one length a caller can get wrong without breaking the layout
     if (!b.bad && (len - b.pos) % 8 == 0) {
         const size_t n = (len - b.pos) / 8;
-        b.words(out.public_inputs, n);
+        read_words(b, out.public_inputs, n);
         out.shape.public_inputs = (uint32_t)n;
     } else b.bad = true;
     if (b.bad || b.pos != len) return "proof bytes end inside a vector or leave trailing bytes (" + std::to_string(len) + " bytes)";

@@ -27,16 +27,6 @@ using gl::u64;
 
 namespace {
 
-void host_hash_no_pad(const hasher::Config &h, const u64 *in, size_t n, u64 out[4]) {
-    u64 st[12] = {0};
-    for (size_t i = 0; i < n; i += 8) {
-        size_t len = std::min<size_t>(8, n - i);
-        for (size_t k = 0; k < len; k++) st[k] = gl::canon(in[i + k]);
-        h.permute(st);
-    }
-    std::memcpy(out, st, 32);
-}
-
 std::vector<u64> powers_table(u64 base, u64 count) {
     std::vector<u64> t(count);
     u64 a = 1;
@@ -116,17 +106,7 @@ int plan_transforms(qpgpu_circuit *c) {
 extern "C" {
 
 size_t qpgpu_proof_size(const qpgpu_circuit *c) {
-    if (!c) return 0;
-    const CircuitPack &p = c->pack;
-    const size_t ncs = p.num_cs_cols(), nch = p.num_challenges, cap = (1ull << p.cap_height) * 32;
-    const size_t L = p.degree_bits + p.rate_bits;
-    size_t sz = 3 * cap + (ncs + p.num_wires + nch * 2 + nch * p.num_partial_products + p.num_quotient_cols()) * 16;
-    const size_t salt = p.zero_knowledge ? 4 : 0;
-    const size_t widths[4] = {ncs, (size_t)p.num_wires + salt, (size_t)p.num_zs_pp_cols() + salt, (size_t)p.num_quotient_cols() + salt};
-    size_t q = 0, lvl = L, fin = p.degree_bits;
-    for (size_t w : widths) q += w * 8 + 1 + (L - p.cap_height) * 32;
-    for (u64 a : p.arity_bits) { sz += cap; lvl -= a; fin -= a; q += (16ull << a) + 1 + (lvl - p.cap_height) * 32; }
-    return sz + p.num_query_rounds * q + (16ull << fin) + 8 + p.num_public_inputs * 8;
+    return c ? c->layout.total : 0;
 }
 
 void qpgpu_circuit_free(qpgpu_circuit *c) {
@@ -161,6 +141,7 @@ int qpgpu_circuit_load_batch(qpgpu_ctx *ctx, const uint64_t *pack_words, size_t 
     std::string err = c->pack.parse(pack_words, n_words);
     if (!err.empty()) { delete c; return ctx->fail(QPGPU_EINVAL, "circuit_load: " + err); }
     const CircuitPack &p = c->pack;
+    c->layout = proof_layout::of(p);
     if (p.num_chunks() > 16 || p.num_challenges > 4) { delete c; return ctx->fail(QPGPU_EINVAL, "circuit_load: too many chunks/challenges"); }
     if (p.degree_bits + p.rate_bits > 23) { delete c; return ctx->fail(QPGPU_EINVAL, "circuit_load: LDE larger than 2^23 not supported"); }
     if (p.degree_bits + p.rate_bits > 20 && p.rate_bits > 3) { delete c; return ctx->fail(QPGPU_EINVAL, "circuit_load: an LDE beyond 2^20 points needs rate_bits <= 3"); }
@@ -244,8 +225,7 @@ int qpgpu_circuit_load_batch(qpgpu_ctx *ctx, const uint64_t *pack_words, size_t 
         c->fri.degree_bits = d; c->fri.rate_bits = (unsigned)p.rate_bits; c->fri.cap_h = (unsigned)p.cap_height;
         c->fri.pow_bits = (unsigned)p.proof_of_work_bits; c->fri.num_queries = (uint32_t)p.num_query_rounds;
         for (u64 a : p.arity_bits) c->fri.arity_bits.push_back((unsigned)a);
-        const size_t salt = p.zero_knowledge ? 4 : 0;
-        const std::vector<size_t> widths = {(size_t)p.num_cs_cols(), (size_t)p.num_wires + salt, (size_t)p.num_zs_pp_cols() + salt, (size_t)p.num_quotient_cols() + salt};
+        const std::vector<size_t> widths(c->layout.widths, c->layout.widths + 4);
         u64 *base = nullptr;
         CK(c->alloc(&base, FriWork::words(c->fri, widths, n_open, B), true));
         c->fri_work.bind(base, c->fri, widths, n_open, B);
@@ -323,7 +303,7 @@ static int prove_batch_impl(qpgpu_circuit *c, uint32_t nb, const u64 *d_wires, c
     c->wires.set_batch(nb); c->zs.set_batch(nb); c->quot.set_batch(nb);
     c->quot.ps_coeffs = (u64)nch * q_n;    // = num_quotient_cols * n: the same dense array seen as nq chunk polynomials
     std::vector<std::array<u64, 4>> pih(nb);
-    for (uint32_t b = 0; b < nb; b++) host_hash_no_pad(ctx->hasher, public_inputs[b], p.num_public_inputs, pih[b].data());
+    for (uint32_t b = 0; b < nb; b++) hasher::hash_no_pad(ctx->hasher, public_inputs[b], p.num_public_inputs, pih[b].data());
     if (p.zero_knowledge) {
         // 256 fresh bits per proof from the OS entropy source (the reference: thread_rng); a seed injected for the next
         // batch makes its bytes reproducible (tests)

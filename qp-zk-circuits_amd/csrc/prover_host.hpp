@@ -1,5 +1,5 @@
 // prover_host.hpp — host-side pieces shared by the all-in-one prover (prover.cpp) and the stage-level
-// C ABI (oracle_api.cpp): the duplex challenger, committed polynomial batches ("oracles", plonky2's
+// C ABI (oracle_api.cpp): committed polynomial batches ("oracles", plonky2's
 // PolynomialBatch), the FRI opening prover and the proof byte writer.
 //
 // Everything here works on a lockstep batch of `nb` proofs of one circuit: each stage is launched once for all of
@@ -9,30 +9,11 @@
 #include <hip/hip_runtime_api.h>
 #include <cstring>
 #include <vector>
+#include "challenger.hpp"
 #include "ctx.hpp"
 #include "gl64.hpp"
 #include "poseidon.hpp"
-
-// ---- host duplex challenger (plonky2::iop::challenger::Challenger) ----
-struct Challenger {
-    const hasher::Config *h;
-    gl::u64 state[12] = {0};
-    gl::u64 in[8]; int n_in = 0;
-    gl::u64 out[8]; int n_out = 0;
-    explicit Challenger(const hasher::Config &cfg) : h(&cfg) {}
-    void duplex() {
-        for (int i = 0; i < n_in; i++) state[i] = in[i];
-        n_in = 0;
-        h->permute(state);
-        std::memcpy(out, state, sizeof out);
-        n_out = 8;
-    }
-    void observe(const gl::u64 *x, size_t n) {
-        for (size_t i = 0; i < n; i++) { n_out = 0; in[n_in++] = gl::canon(x[i]); if (n_in == 8) duplex(); }
-    }
-    gl::u64 get() { if (n_in > 0 || n_out == 0) duplex(); return out[--n_out]; }
-    gl::e2 get_ext() { gl::u64 a = get(), b = get(); return gl::e2_make(a, b); }
-};
+#include "proof_layout.hpp"
 
 struct ByteWriter {
     uint8_t *p; size_t cap, len = 0; bool overflow = false;
@@ -101,6 +82,7 @@ struct FriWork {
     gl::u64 *gather = nullptr;
     gl::e2 *alpha_ext = nullptr;
     size_t gather_words = 0, max_batch_polys = 0;
+    proof_layout::Fri proof;         // where the gathered rows and paths go in the proof bytes
     // batch-level tables: [nb] each (qidx: [nb][num_queries], pow_states: [nb][12])
     gl::e2 *t_points = nullptr, *t_shifts = nullptr, *t_betas = nullptr;
     gl::u64 *pow_states = nullptr, *pow_bases = nullptr, *pow_results = nullptr, *qidx = nullptr;

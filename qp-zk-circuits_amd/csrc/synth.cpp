@@ -25,15 +25,7 @@ struct SplitMix {
     u64 felt() { for (;;) { u64 v = next(); if (v < gl::P) return v; } }
     u64 below(u64 n) { return next() % n; }
 };
-void host_hash_no_pad(const u64 *in, size_t n, u64 out[4]) {
-    u64 st[12] = {0};
-    for (size_t i = 0; i < n; i += 8) {
-        size_t len = std::min<size_t>(8, n - i);
-        for (size_t k = 0; k < len; k++) st[k] = gl::canon(in[i + k]);
-        hasher::host_permute(st);
-    }
-    for (int i = 0; i < 4; i++) out[i] = st[i];
-}
+void host_hash_no_pad(const u64 *in, size_t n, u64 out[4]) { hasher::hash_no_pad(hasher::process_default(), in, n, out); }
 struct GateSpec { uint64_t type, p0, p1, degree, ncons; std::string id; uint64_t p2 = 0; };
 }  // namespace
 

@@ -13,6 +13,7 @@
 #include <thread>
 #include <string>
 #include <vector>
+#include "challenger.hpp"
 #include "circuit.hpp"
 #include "gl64.hpp"
 #include "poseidon.hpp"
@@ -22,9 +23,7 @@
 using gl::e2;
 using gl::u64;
 
-namespace {
-
-int fail(char *err, int code, const char *fmt, ...) {
+int verify::fail(char *err, int code, const char *fmt, ...) {
     if (err) {
         va_list ap;
         va_start(ap, fmt);
@@ -33,6 +32,9 @@ int fail(char *err, int code, const char *fmt, ...) {
     }
     return code;
 }
+using verify::fail;
+
+namespace {
 
 // ---- extension-field shorthands (F[x]/(x^2 - 7)) ----
 inline e2 E(u64 a) { return gl::e2_from(a); }
@@ -42,42 +44,15 @@ inline bool same(e2 x, e2 y) { x = gl::e2_canon(x); y = gl::e2_canon(y); return 
 // ---- hashing under the proof system's permutation ----
 struct Hash {
     const hasher::Config *h;
-    void no_pad(const u64 *in, size_t n, u64 out[4]) const {       // hash_n_to_hash_no_pad: overwrite absorption, rate 8
-        u64 st[12] = {0};
-        for (size_t i = 0; i < n; i += 8) {
-            const size_t len = std::min<size_t>(8, n - i);
-            for (size_t k = 0; k < len; k++) st[k] = in[i + k];
-            h->permute(st);
-        }
-        std::memcpy(out, st, 32);
-    }
     void leaf(const u64 *row, size_t width, u64 out[4]) const {     // hash_or_noop
         if (width <= 4) { for (size_t i = 0; i < 4; i++) out[i] = i < width ? row[i] : 0; return; }
-        no_pad(row, width, out);
+        hasher::hash_no_pad(*h, row, width, out);
     }
     void two_to_one(const u64 *l, const u64 *r, u64 out[4]) const {
         u64 st[12] = {l[0], l[1], l[2], l[3], r[0], r[1], r[2], r[3], 0, 0, 0, 0};
         h->permute(st);
         std::memcpy(out, st, 32);
     }
-};
-
-struct Transcript {     // plonky2::iop::challenger::Challenger
-    const hasher::Config *h;
-    u64 state[12] = {0};
-    u64 in[8]; int n_in = 0;
-    u64 out[8]; int n_out = 0;
-    void duplex() {
-        for (int i = 0; i < n_in; i++) state[i] = in[i];
-        n_in = 0;
-        h->permute(state);
-        std::memcpy(out, state, sizeof out);
-        n_out = 8;
-    }
-    void observe(const u64 *x, size_t n) { for (size_t i = 0; i < n; i++) { n_out = 0; in[n_in++] = x[i]; if (n_in == 8) duplex(); } }
-    void observe(const std::vector<e2> &v) { for (const e2 &x : v) { u64 t[2] = {x.a, x.b}; observe(t, 2); } }
-    u64 get() { if (n_in > 0 || n_out == 0) duplex(); return out[--n_out]; }
-    e2 get_ext() { const u64 a = get(), b = get(); return gl::e2_make(a, b); }
 };
 
 inline uint32_t bitrev(uint32_t x, unsigned bits) {
@@ -111,20 +86,6 @@ using vmath::gate_constraints;
 
 namespace {
 
-size_t proof_size_of(const CircuitPack &p) {
-    const size_t ncs = p.num_cs_cols(), nch = p.num_challenges, cap = ((size_t)1 << p.cap_height) * 32;
-    const size_t openings = (ncs + p.num_wires + 2 * nch + nch * p.num_partial_products + nch * p.quotient_degree_factor) * 16;
-    const size_t L = p.degree_bits + p.rate_bits, salt = p.zero_knowledge ? 4 : 0;
-    const size_t widths[4] = {ncs, p.num_wires + salt, p.num_zs_pp_cols() + salt, p.num_quotient_cols() + salt};
-    size_t q = 0, sz = 3 * cap + openings, lvl = L, fin = p.degree_bits;
-    for (size_t w : widths) q += w * 8 + 1 + (L - p.cap_height) * 32;
-    for (u64 ab : p.arity_bits) {
-        sz += cap; lvl -= ab; fin -= ab;
-        q += ((size_t)1 << ab) * 16 + 1 + (lvl - p.cap_height) * 32;
-    }
-    return sz + p.num_query_rounds * q + ((size_t)1 << fin) * 16 + 8 + p.num_public_inputs * 8;
-}
-
 // constants/sigmas cap from the pack: per column values -> coefficients -> coset LDE in leaf order; leaves hashed, tree to the cap
 void host_cs_cap(const CircuitPack &p, const Hash &H, std::vector<u64> &cap) {
     const unsigned d = (unsigned)p.degree_bits, L = d + (unsigned)p.rate_bits;
@@ -153,22 +114,11 @@ void host_cs_cap(const CircuitPack &p, const Hash &H, std::vector<u64> &cap) {
     cap.assign(level.begin(), level.begin() + 4 * cnt);
 }
 
-struct Reader {
-    const uint8_t *p; size_t len, pos = 0; bool bad = false, noncanonical = false;
-    u64 word() {
-        if (pos + 8 > len) { bad = true; return 0; }
-        u64 v; std::memcpy(&v, p + pos, 8); pos += 8;
-        if (v >= gl::P) noncanonical = true;      // Field::from_canonical_u64 on read: a proof carries canonical elements only
-        return v;
-    }
-    uint8_t byte() { if (pos + 1 > len) { bad = true; return 0; } return p[pos++]; }
-    void vec(u64 *out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = word(); }
-    e2 ext() { const u64 a = word(), b = word(); return gl::e2_make(a, b); }
-    void exts(std::vector<e2> &v, size_t n) { v.resize(n); for (size_t i = 0; i < n; i++) v[i] = ext(); }
-};
+using proof_layout::Reader;
+void read_exts(Reader &b, std::vector<e2> &v, size_t n) { v.resize(n); b.vec((u64 *)v.data(), 2 * n); }
 
-bool path_ok(const Hash &H, const u64 *leaf, size_t width, size_t index, const u64 *path, size_t plen, const u64 *cap, unsigned cap_h, size_t log_leaves) {
-    if (plen != log_leaves - cap_h) return false;
+bool path_ok(const Hash &H, const u64 *leaf, size_t width, size_t index, const u64 *path, size_t plen, const u64 *cap, size_t layout_plen) {
+    if (plen != layout_plen) return false;
     u64 cur[4], nxt[4];
     H.leaf(leaf, width, cur);
     for (size_t i = 0; i < plen; i++) {
@@ -221,13 +171,13 @@ int qpgpu_verifier_create(const uint64_t *pack_words, size_t n_words, const uint
         const Hash H{&v->hash};
         host_cs_cap(p, H, v->cs_cap);
     }
-    v->proof_size = proof_size_of(p);
+    v->layout = proof_layout::of(p);
     *out = v;
     return QPGPU_OK;
 }
 
 void qpgpu_verifier_free(qpgpu_verifier *v) { delete v; }
-size_t qpgpu_verifier_proof_size(const qpgpu_verifier *v) { return v ? v->proof_size : 0; }
+size_t qpgpu_verifier_proof_size(const qpgpu_verifier *v) { return v ? v->layout.total : 0; }
 int qpgpu_verifier_constants_sigmas_cap(const qpgpu_verifier *v, uint64_t *out, size_t out_words) {
     if (!v || !out || out_words < v->cs_cap.size()) return QPGPU_EINVAL;
     std::memcpy(out, v->cs_cap.data(), v->cs_cap.size() * 8);
@@ -251,36 +201,26 @@ int qpgpu_verifier_query_indices(const qpgpu_verifier *v, const uint8_t *proof, 
 int verify_head(const qpgpu_verifier *v, const uint8_t *proof, size_t len, char *err, VerifyHead &h) {
     if (!v || !proof) return fail(err, QPGPU_EINVAL, "null argument");
     const CircuitPack &c = v->pack;
-    const Hash H{&v->hash};
-    if (len != v->proof_size) return fail(err, QPGPU_EVERIFY, "proof has %zu bytes, this circuit's proofs have %zu", len, v->proof_size);
-    const unsigned d = (unsigned)c.degree_bits, rb = (unsigned)c.rate_bits, cap_h = (unsigned)c.cap_height, L = d + rb;
-    const size_t n = (size_t)1 << d, lde_n = n << rb, NW = c.num_wires, nch = c.num_challenges;
-    const size_t npp = c.num_partial_products, ncs = c.num_cs_cols();
-    const size_t cap_words = ((size_t)1 << cap_h) * 4, nq = nch * c.quotient_degree_factor;
-    const size_t n_rounds = c.arity_bits.size();
+    const proof_layout::Proof &lay = v->layout;
+    if (len != lay.total) return fail(err, QPGPU_EVERIFY, "proof has %zu bytes, this circuit's proofs have %zu", len, lay.total);
+    const unsigned d = (unsigned)c.degree_bits, rb = (unsigned)c.rate_bits;
+    const size_t n = (size_t)1 << d, lde_n = n << rb, nch = c.num_challenges;
+    const size_t cap_words = lay.cap_bytes / 8, n_rounds = c.arity_bits.size();
 
     Reader b{proof, len};
     std::vector<u64> &wires_cap = h.wires_cap, &zs_cap = h.zs_cap, &q_cap = h.q_cap;
     wires_cap.assign(cap_words, 0); zs_cap.assign(cap_words, 0); q_cap.assign(cap_words, 0);
     b.vec(wires_cap.data(), cap_words); b.vec(zs_cap.data(), cap_words); b.vec(q_cap.data(), cap_words);
     std::vector<e2> o_cs, o_w, o_zs, o_zn, o_pp, o_q;
-    b.exts(o_cs, ncs); b.exts(o_w, NW); b.exts(o_zs, nch); b.exts(o_zn, nch); b.exts(o_pp, nch * npp); b.exts(o_q, nq);
+    const proof_layout::Vec *ov = lay.openings;      // constants and sigmas are one vector here, as in the oracle that holds them
+    read_exts(b, o_cs, ov[0].count + ov[1].count); read_exts(b, o_w, ov[2].count); read_exts(b, o_zs, ov[3].count); read_exts(b, o_zn, ov[4].count);
+    read_exts(b, o_pp, ov[5].count); read_exts(b, o_q, ov[6].count);
     std::vector<u64> &fri_caps = h.fri_caps;
     fri_caps.assign(cap_words * n_rounds, 0);
     b.vec(fri_caps.data(), cap_words * n_rounds);
-    h.queries_pos = b.pos;
-    const size_t salt = c.zero_knowledge ? 4 : 0;
-    const size_t widths[4] = {ncs, NW + salt, nch * (1 + npp) + salt, nq + salt};
-    {
-        size_t q = 0, lvl = L;
-        for (size_t w : widths) q += w * 8 + 1 + (L - cap_h) * 32;
-        for (u64 ab : c.arity_bits) { lvl -= ab; q += ((size_t)1 << ab) * 16 + 1 + (lvl - cap_h) * 32; }
-        b.pos += q * c.num_query_rounds;
-    }
-    size_t fin_bits = d;
-    for (u64 ab : c.arity_bits) fin_bits -= ab;
+    b.pos = lay.final_pos;                           // over the query rounds
     std::vector<e2> &final_poly = h.final_poly;
-    b.exts(final_poly, (size_t)1 << fin_bits);
+    read_exts(b, final_poly, lay.fri.final_len);
     u64 pow_witness = b.word();
     std::vector<u64> pis(c.num_public_inputs + 1);
     b.vec(pis.data(), c.num_public_inputs);
@@ -289,9 +229,10 @@ int verify_head(const qpgpu_verifier *v, const uint8_t *proof, size_t len, char 
 
     // ---- challenges: the prover's transcript, replayed ----
     u64 pih[4];
-    H.no_pad(pis.data(), c.num_public_inputs, pih);
-    Transcript ch{&v->hash};
-    ch.observe(c.circuit_digest, 4);
+    hasher::hash_no_pad(v->hash, pis.data(), c.num_public_inputs, pih);
+    Challenger ch(v->hash);
+    auto observe = [&ch](const std::vector<e2> &x) { ch.observe((const u64 *)x.data(), 2 * x.size()); };
+    ch.observe_raw(c.circuit_digest, 4);
     ch.observe(pih, 4);
     ch.observe(wires_cap.data(), cap_words);
     u64 betas[4], gammas[4], alphas[4];
@@ -301,12 +242,12 @@ int verify_head(const qpgpu_verifier *v, const uint8_t *proof, size_t len, char 
     for (size_t k = 0; k < nch; k++) alphas[k] = ch.get();
     ch.observe(q_cap.data(), cap_words);
     const e2 zeta = h.zeta = ch.get_ext();
-    ch.observe(o_cs); ch.observe(o_w); ch.observe(o_zs); ch.observe(o_pp); ch.observe(o_q); ch.observe(o_zn);
+    observe(o_cs); observe(o_w); observe(o_zs); observe(o_pp); observe(o_q); observe(o_zn);
     const e2 fri_alpha = h.fri_alpha = ch.get_ext();
     std::vector<e2> &fri_betas = h.fri_betas;
     fri_betas.assign(n_rounds, E(0));
     for (size_t r = 0; r < n_rounds; r++) { ch.observe(fri_caps.data() + r * cap_words, cap_words); fri_betas[r] = ch.get_ext(); }
-    ch.observe(final_poly);
+    observe(final_poly);
     ch.observe(&pow_witness, 1);
     const u64 pow_response = ch.get();
     if (c.proof_of_work_bits && (pow_response >> (64 - c.proof_of_work_bits)) != 0)
@@ -355,22 +296,19 @@ static int verify_impl(const qpgpu_verifier *v, const uint8_t *proof, size_t len
     if (indices_out) { for (size_t qi = 0; qi < h.x_indices.size(); qi++) indices_out[qi] = h.x_indices[qi]; return QPGPU_OK; }
     const CircuitPack &c = v->pack;
     const Hash H{&v->hash};
-    const unsigned d = (unsigned)c.degree_bits, rb = (unsigned)c.rate_bits, cap_h = (unsigned)c.cap_height, L = d + rb;
-    const size_t NW = c.num_wires, nch = c.num_challenges;
-    const size_t npp = c.num_partial_products, ncs = c.num_cs_cols();
-    const size_t cap_words = ((size_t)1 << cap_h) * 4, nq = nch * c.quotient_degree_factor;
-    const size_t n_rounds = c.arity_bits.size();
-    const size_t salt = c.zero_knowledge ? 4 : 0;
-    const size_t widths[4] = {ncs, NW + salt, nch * (1 + npp) + salt, nq + salt};
-    const size_t polys[4] = {ncs, NW, nch * (1 + npp), nq};
+    const proof_layout::Proof &lay = v->layout;
+    const size_t *widths = lay.widths, *polys = lay.polys;
+    const proof_layout::Opening *op = lay.fri.op.data();     // the four initial oracles, then the FRI rounds
+    const unsigned L = (unsigned)(c.degree_bits + c.rate_bits);
+    const size_t nch = c.num_challenges, cap_words = lay.cap_bytes / 8, n_rounds = c.arity_bits.size();
     const std::vector<size_t> &x_indices = h.x_indices;
     const std::vector<u64> &fri_caps = h.fri_caps;
     const std::vector<e2> &fri_betas = h.fri_betas, &final_poly = h.final_poly;
     const e2 zeta = h.zeta, g_zeta = h.g_zeta, fri_alpha = h.fri_alpha, alpha_nch = h.alpha_nch, red0 = h.red0, red1 = h.red1;
 
     const u64 *caps0[4] = {v->cs_cap.data(), h.wires_cap.data(), h.zs_cap.data(), h.q_cap.data()};
-    Reader q{proof, len, h.queries_pos};
-    std::vector<u64> row(ncs + NW + nch * (1 + npp) + nq + 16), path(64 * 4), ev(64);
+    Reader q{proof, len, lay.queries_pos};
+    std::vector<u64> row(widths[0] + widths[1] + widths[2] + widths[3]), path(64 * 4), ev(64);
     const u64 w_lde = gl::root_of_unity(L);
     for (size_t qi = 0; qi < c.num_query_rounds; qi++) {
         size_t x_index = x_indices[qi];
@@ -383,7 +321,7 @@ static int verify_impl(const qpgpu_verifier *v, const uint8_t *proof, size_t len
             const size_t plen = q.byte();
             if (plen > 60) return fail(err, QPGPU_EVERIFY, "query %zu: Merkle path length of oracle %d out of range", qi, o);
             q.vec(path.data(), plen * 4);
-            if (q.bad || !path_ok(H, r, widths[o], x_index, path.data(), plen, caps0[o], cap_h, L))
+            if (q.bad || !path_ok(H, r, widths[o], x_index, path.data(), plen, caps0[o], op[o].path_len))
                 return fail(err, QPGPU_EVERIFY, "query %zu: Merkle path of initial oracle %d does not lead to its cap", qi, o);
         }
         u64 subgroup_x = gl::mul(gl::MULT_GEN, gl::pow(w_lde, bitrev((uint32_t)x_index, L)));
@@ -394,7 +332,6 @@ static int verify_impl(const qpgpu_verifier *v, const uint8_t *proof, size_t len
         e2 sum = (e0 - red0) * gl::e2_inv(sx - zeta);
         sum = sum * alpha_nch + (e1 - red1) * gl::e2_inv(sx - g_zeta);
         e2 old_eval = sum;
-        size_t lvl = L;
         for (size_t r = 0; r < n_rounds; r++) {
             const unsigned ab = (unsigned)c.arity_bits[r];
             const size_t arity = (size_t)1 << ab;
@@ -405,8 +342,7 @@ static int verify_impl(const qpgpu_verifier *v, const uint8_t *proof, size_t len
             const size_t coset_index = x_index >> ab, within = x_index & (arity - 1);
             if (!same(gl::e2_make(ev[2 * within], ev[2 * within + 1]), old_eval))
                 return fail(err, QPGPU_EVERIFY, "query %zu: FRI round %zu does not continue the previous evaluation", qi, r);
-            lvl -= ab;
-            if (q.bad || !path_ok(H, ev.data(), 2 * arity, coset_index, path.data(), plen, fri_caps.data() + r * cap_words, cap_h, lvl))
+            if (q.bad || !path_ok(H, ev.data(), 2 * arity, coset_index, path.data(), plen, fri_caps.data() + r * cap_words, op[4 + r].path_len))
                 return fail(err, QPGPU_EVERIFY, "query %zu: Merkle path of FRI round %zu does not lead to its cap", qi, r);
             // compute_evaluation: interpolate the coset's 2^ab evaluations and evaluate at beta
             const u64 g = gl::root_of_unity(ab);

@@ -7,12 +7,13 @@
 #include "circuit.hpp"
 #include "gl64.hpp"
 #include "poseidon.hpp"
+#include "proof_layout.hpp"
 
 struct qpgpu_verifier {
     CircuitPack pack;
     hasher::Config hash;
     std::vector<gl::u64> cs_cap;
-    size_t proof_size = 0;
+    proof_layout::Proof layout;      // byte layout of this circuit's proofs
 };
 
 // Everything the query rounds need, as the head of verify_impl leaves it: the transcript replayed through the proof of work,
@@ -22,8 +23,10 @@ struct VerifyHead {
     std::vector<gl::e2> final_poly, fri_betas;
     gl::e2 zeta, g_zeta, fri_alpha, alpha_nch, red0, red1;    // red0 / red1: reduced openings at zeta / g zeta
     std::vector<size_t> x_indices;                            // num_query_rounds
-    size_t queries_pos = 0;                                   // byte offset of the first query round
 };
+
+// the reason (printf form) into the caller's QPGPU_VERIFY_ERR_CAP bytes, where there are any; returns `code`
+namespace verify { int fail(char *err, int code, const char *fmt, ...); }
 
 // 0, or the code and reason the verifier gives for a proof that fails before its query rounds (size, layout, non-canonical
 // element, proof of work, quotient identity)

@@ -10,7 +10,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -26,16 +25,6 @@ using gl::u64;
 
 namespace {
 
-int vfail(char *err, int code, const char *fmt, ...) {
-    if (err) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(err, QPGPU_VERIFY_ERR_CAP, fmt, ap);
-        va_end(ap);
-    }
-    return code;
-}
-
 bool same_hasher(const hasher::Config &a, const hasher::Config &b) {
     if (a.kind != b.kind) return false;
     if (a.kind != hasher::POSEIDON2) return true;
@@ -43,42 +32,29 @@ bool same_hasher(const hasher::Config &a, const hasher::Config &b) {
            memcmp(a.p2.diag_m1, b.p2.diag_m1, sizeof a.p2.diag_m1) == 0 && memcmp(a.p2.m4, b.p2.m4, sizeof a.p2.m4) == 0;
 }
 
-// where every opening of a query round sits: the proof layout of verifier.cpp (proof_size_of, verify_impl)
-bool make_layout(const CircuitPack &c, size_t proof_size, VerifyLayout &lay) {
+// the proof layout (proof_layout.hpp) as the kernels read it, and the strides of the device buffer
+bool make_layout(const CircuitPack &c, const proof_layout::Proof &p, VerifyLayout &lay) {
     const size_t n_rounds = c.arity_bits.size();
-    if (n_rounds > (size_t)VERIFY_MAX_ROUNDS || proof_size >= ((size_t)1 << 31)) return false;
-    const unsigned cap_h = (unsigned)c.cap_height, L = (unsigned)(c.degree_bits + c.rate_bits);
-    const size_t ncs = c.num_cs_cols(), NW = c.num_wires, nch = c.num_challenges, npp = c.num_partial_products;
-    const size_t nq = nch * c.quotient_degree_factor, salt = c.zero_knowledge ? 4 : 0, cap_bytes = ((size_t)1 << cap_h) * 32;
-    const size_t widths[4] = {ncs, NW + salt, nch * (1 + npp) + salt, nq + salt};
-    const size_t polys[4] = {ncs, NW, nch * (1 + npp), nq};
-    const size_t openings = (ncs + NW + 2 * nch + nch * npp + nq) * 16;
-    const size_t fri_caps_pos = 3 * cap_bytes + openings;
+    if (n_rounds > (size_t)VERIFY_MAX_ROUNDS || p.total >= ((size_t)1 << 31)) return false;
     memset(&lay, 0, sizeof lay);
-    size_t off = 0;
-    for (int o = 0; o < 4; o++) {
-        lay.op[o] = {(uint32_t)off, (uint32_t)widths[o], L - cap_h, 0, o == 0 ? VERIFY_CAP_VERIFIER : (uint32_t)((o - 1) * cap_bytes)};
-        lay.polys[o] = (uint32_t)polys[o];
-        off += widths[o] * 8 + 1 + (L - cap_h) * 32;
+    for (size_t i = 0; i < 4 + n_rounds; i++) {
+        const proof_layout::Opening &o = p.fri.op[i];
+        // the cap an opening leads to: the verifier's own, a cap at the head of the proof, the FRI round's
+        const size_t cap_off = i == 0 ? VERIFY_CAP_VERIFIER : i < 4 ? (i - 1) * p.cap_bytes : p.fri_caps_pos + (i - 4) * p.cap_bytes;
+        lay.op[i] = {(uint32_t)o.off, (uint32_t)o.row_words, (uint32_t)o.path_len, (uint32_t)o.shift, (uint32_t)cap_off};
     }
-    unsigned lvl = L, shift = 0, fin_bits = (unsigned)c.degree_bits;
-    for (size_t r = 0; r < n_rounds; r++) {
-        const unsigned ab = (unsigned)c.arity_bits[r];
-        lvl -= ab; shift += ab; fin_bits -= ab;
-        lay.arity_bits[r] = ab;
-        lay.op[4 + r] = {(uint32_t)off, 2u << ab, lvl - cap_h, shift, (uint32_t)(fri_caps_pos + r * cap_bytes)};
-        off += ((size_t)1 << ab) * 16 + 1 + (lvl - cap_h) * 32;
-    }
+    for (int o = 0; o < 4; o++) lay.polys[o] = (uint32_t)p.polys[o];
+    for (size_t r = 0; r < n_rounds; r++) lay.arity_bits[r] = (uint32_t)c.arity_bits[r];
     lay.nq = (uint32_t)c.num_query_rounds;
     lay.n_open = (uint32_t)(4 + n_rounds);
-    lay.queries_pos = (uint32_t)(fri_caps_pos + n_rounds * cap_bytes);
-    lay.q_bytes = (uint32_t)off;
-    lay.final_off = (uint32_t)(lay.queries_pos + lay.nq * off);
-    lay.final_n = 1u << fin_bits;
-    lay.stride_words = (uint32_t)((proof_size + 7) / 8 + 1);
+    lay.queries_pos = (uint32_t)p.queries_pos;
+    lay.q_bytes = (uint32_t)p.fri.round_bytes;
+    lay.final_off = (uint32_t)p.final_pos;
+    lay.final_n = (uint32_t)p.fri.final_len;
+    lay.stride_words = (uint32_t)((p.total + 7) / 8 + 1);
     lay.rec_words = vrec_words((uint32_t)n_rounds, lay.nq);
-    lay.log_lde = L;
-    lay.nch = (uint32_t)nch;
+    lay.log_lde = (uint32_t)(c.degree_bits + c.rate_bits);
+    lay.nch = (uint32_t)c.num_challenges;
     return true;
 }
 
@@ -86,12 +62,12 @@ bool make_layout(const CircuitPack &c, size_t proof_size, VerifyLayout &lay) {
 void query_reason(char *out, size_t qi, uint32_t code) {
     const unsigned kind = code >> 8, at = code & 0xff;
     switch (kind) {
-    case VQ_ORACLE_PLEN: vfail(out, 0, "query %zu: Merkle path length of oracle %d out of range", qi, (int)at); break;
-    case VQ_ORACLE_PATH: vfail(out, 0, "query %zu: Merkle path of initial oracle %d does not lead to its cap", qi, (int)at); break;
-    case VQ_ROUND_PLEN: vfail(out, 0, "query %zu: Merkle path length of FRI round %zu out of range", qi, (size_t)at); break;
-    case VQ_ROUND_CONT: vfail(out, 0, "query %zu: FRI round %zu does not continue the previous evaluation", qi, (size_t)at); break;
-    case VQ_ROUND_PATH: vfail(out, 0, "query %zu: Merkle path of FRI round %zu does not lead to its cap", qi, (size_t)at); break;
-    default: vfail(out, 0, "query %zu: the final polynomial does not match the last FRI round", qi); break;
+    case VQ_ORACLE_PLEN: verify::fail(out, 0, "query %zu: Merkle path length of oracle %d out of range", qi, (int)at); break;
+    case VQ_ORACLE_PATH: verify::fail(out, 0, "query %zu: Merkle path of initial oracle %d does not lead to its cap", qi, (int)at); break;
+    case VQ_ROUND_PLEN: verify::fail(out, 0, "query %zu: Merkle path length of FRI round %zu out of range", qi, (size_t)at); break;
+    case VQ_ROUND_CONT: verify::fail(out, 0, "query %zu: FRI round %zu does not continue the previous evaluation", qi, (size_t)at); break;
+    case VQ_ROUND_PATH: verify::fail(out, 0, "query %zu: Merkle path of FRI round %zu does not lead to its cap", qi, (size_t)at); break;
+    default: verify::fail(out, 0, "query %zu: the final polynomial does not match the last FRI round", qi); break;
     }
 }
 
@@ -112,17 +88,17 @@ constexpr size_t CHUNK_BYTES = (size_t)256 << 20;
 
 extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_ctx *ctx, const uint8_t *const *proofs, const size_t *lens,
                                                  size_t count, unsigned threads, int *results, char *reasons, char *err) {
-    if (!v || !ctx) return vfail(err, QPGPU_EINVAL, "null argument");
+    if (!v || !ctx) return verify::fail(err, QPGPU_EINVAL, "null argument");
     if (count == 0) return QPGPU_OK;
-    if (!proofs || !lens || !results) return vfail(err, QPGPU_EINVAL, "null argument");
+    if (!proofs || !lens || !results) return verify::fail(err, QPGPU_EINVAL, "null argument");
     if (!same_hasher(v->hash, ctx->hasher)) {
         ctx->fail(QPGPU_EINVAL, "verify_many_device: the verifier's hasher is not the context's (qpgpu_ctx_set_hasher)");
-        return vfail(err, QPGPU_EINVAL, "%s", ctx->err.c_str());
+        return verify::fail(err, QPGPU_EINVAL, "%s", ctx->err.c_str());
     }
     VerifyLayout lay;
-    if (!make_layout(v->pack, v->proof_size, lay)) {
+    if (!make_layout(v->pack, v->layout, lay)) {
         ctx->fail(QPGPU_EINVAL, "verify_many_device: circuit outside the supported range");
-        return vfail(err, QPGPU_EINVAL, "%s", ctx->err.c_str());
+        return verify::fail(err, QPGPU_EINVAL, "%s", ctx->err.c_str());
     }
     if (threads == 0) threads = std::max(1u, std::thread::hardware_concurrency());
     const size_t cap_words = v->cs_cap.size(), SW = lay.stride_words, RW = lay.rec_words, nq = lay.nq;
@@ -142,7 +118,7 @@ extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_
     auto device_fail = [&](int rc) {
         for (size_t i = chunk_from; i < count; i++)
             if (i >= headed || results[i] == QPGPU_EDEVICE) { results[i] = QPGPU_EDEVICE; reason_row(i)[0] = 0; }
-        return vfail(err, rc, "%s", ctx->err.c_str());
+        return verify::fail(err, rc, "%s", ctx->err.c_str());
     };
     {
         const hipError_t e = hipSetDevice(ctx->device);
@@ -176,7 +152,6 @@ extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_
         // ---- phase 1: the head of every proof on host threads; the survivors staged ----
         auto t0 = std::chrono::steady_clock::now();
         std::atomic<size_t> next{0};
-        std::atomic<bool> layout_mismatch{false};
         auto work = [&] {
             char local[QPGPU_VERIFY_ERR_CAP];
             VerifyHead h;
@@ -190,7 +165,6 @@ extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_
                 local[0] = 0;
                 const int rc = verify_head(v, proofs[i], lens[i], local, h);
                 if (rc != QPGPU_OK) { results[i] = rc; std::memcpy(row, local, QPGPU_VERIFY_ERR_CAP); continue; }
-                if (h.queries_pos != lay.queries_pos) { layout_mismatch = true; results[i] = QPGPU_EDEVICE; continue; }
                 u64 *dst = h_proofs + k * SW;
                 dst[SW - 2] = 0; dst[SW - 1] = 0;          // the partial last word and the padding word
                 std::memcpy(dst, proofs[i], lens[i]);
@@ -211,10 +185,6 @@ extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_
         for (auto &t : pool) t.join();
         headed = c0 + n;
         host_stat(ctx, "verify_many_device.head", ms_since(t0));
-        if (layout_mismatch) {
-            ctx->fail(QPGPU_EINVAL, "verify_many_device: the proof layout of the verifier and the device path disagree");
-            return device_fail(QPGPU_EINVAL);
-        }
         bool any = false;
         for (size_t k = 0; k < n && !any; k++) any = h_recs[k * RW + VREC_LIVE] != 0;
         if (!any) continue;
@@ -254,6 +224,6 @@ extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_
         host_stat(ctx, "verify_many_device.reasons", ms_since(t0));
     }
     for (size_t i = 0; i < count; i++)
-        if (results[i]) return vfail(err, QPGPU_EVERIFY, "proof %zu: %.170s", i, reason_row(i));
+        if (results[i]) return verify::fail(err, QPGPU_EVERIFY, "proof %zu: %.170s", i, reason_row(i));
     return QPGPU_OK;
 }

@@ -1,5 +1,5 @@
 // verify_kernels.hpp — launch interface of the query-round kernels of batch verification (verify_kernels.hip, driven by
-// verify_device.cpp). A proof of a circuit has one layout (verifier.cpp: proof_size_of), so every opening of every query round
+// verify_device.cpp). A proof of a circuit has one layout (proof_layout.hpp), so every opening of every query round
 // sits at a byte offset that depends only on (query, oracle or FRI round): the host describes it once per call in VerifyLayout.
 #pragma once
 #include <hip/hip_runtime_api.h>

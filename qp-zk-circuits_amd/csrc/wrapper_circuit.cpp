@@ -32,6 +32,7 @@
 #include "builder.hpp"
 #include "gadgets.hpp"
 #include "poseidon.hpp"
+#include "proof_layout.hpp"
 #include "verify_math.hpp"
 
 using cb::BoolTarget;
@@ -88,31 +89,27 @@ ProofTargets add_virtual_proof(Builder &b, const CircuitPack &c) {
     ProofTargets t;
     auto one = [&]() { const Target x = b.add_virtual_target(); t.all.push_back(x); return x; };
     auto hash = [&]() { HashOutTarget h; for (auto &e : h.elements) e = one(); return h; };
-    const uint32_t cap = 1u << c.cap_height, nch = (uint32_t)c.num_challenges, salt = c.zero_knowledge ? 4 : 0;
-    const uint32_t L = (uint32_t)(c.degree_bits + c.rate_bits);
+    const proof_layout::Proof lay = proof_layout::of(c);
+    const size_t cap = lay.cap_bytes / 32, n_rounds = lay.fri.n_rounds();
     for (uint64_t i = 0; i < c.num_public_inputs; i++) t.public_inputs.push_back(one());
-    for (int k = 0; k < 3; k++) for (uint32_t i = 0; i < cap; i++) t.caps[k].push_back(hash());
-    // openings at zeta (constants, plonk_sigmas, wires, plonk_zs, partial_products, quotient_polys), then plonk_zs_next: 2 per element
-    const uint64_t openings = (c.num_selectors + c.num_constants) + c.num_routed_wires + c.num_wires + nch + nch * c.num_partial_products + c.num_quotient_cols() + nch;
-    for (uint64_t i = 0; i < 2 * openings; i++) t.openings.push_back(one());
+    for (int k = 0; k < 3; k++) for (size_t i = 0; i < cap; i++) t.caps[k].push_back(hash());
+    // openings at zeta (constants, plonk_sigmas, wires, plonk_zs, partial_products, quotient_polys), then plonk_zs_next: 2 per element.
+    // The order within them does not matter here: all seven vectors become one run of targets.
+    size_t openings = 0;
+    for (const proof_layout::Vec &v : lay.openings) openings += v.count;
+    for (size_t i = 0; i < 2 * openings; i++) t.openings.push_back(one());
     t.pow_witness = one();
-    uint32_t fin = (uint32_t)c.degree_bits;
-    for (uint64_t ab : c.arity_bits) fin -= (uint32_t)ab;
-    for (uint32_t i = 0; i < (2u << fin); i++) t.final_poly.push_back(one());
-    for (size_t r = 0; r < c.arity_bits.size(); r++) { t.commit_caps.emplace_back(); for (uint32_t i = 0; i < cap; i++) t.commit_caps.back().push_back(hash()); }
-    const uint32_t widths[4] = {(uint32_t)c.num_cs_cols(), (uint32_t)c.num_wires + salt, (uint32_t)c.num_zs_pp_cols() + salt, (uint32_t)c.num_quotient_cols() + salt};
-    t.rounds.resize(c.num_query_rounds);
+    for (size_t i = 0; i < 2 * lay.fri.final_len; i++) t.final_poly.push_back(one());
+    for (size_t r = 0; r < n_rounds; r++) { t.commit_caps.emplace_back(); for (size_t i = 0; i < cap; i++) t.commit_caps.back().push_back(hash()); }
+    t.rounds.resize(lay.fri.num_query_rounds);
     for (QueryRoundTargets &q : t.rounds) {
-        for (int o = 0; o < 4; o++) {
-            for (uint32_t i = 0; i < widths[o]; i++) q.evals[o].push_back(one());
-            for (uint32_t i = 0; i < L - (uint32_t)c.cap_height; i++) q.siblings[o].push_back(hash());
-        }
-        uint32_t lvl = L;
-        for (uint64_t ab : c.arity_bits) {
-            lvl -= (uint32_t)ab;
-            q.step_evals.emplace_back(); q.step_siblings.emplace_back();
-            for (uint32_t i = 0; i < (2u << ab); i++) q.step_evals.back().push_back(one());
-            for (uint32_t i = 0; i < lvl - (uint32_t)c.cap_height; i++) q.step_siblings.back().push_back(hash());
+        q.step_evals.resize(n_rounds); q.step_siblings.resize(n_rounds);
+        for (size_t o = 0; o < 4 + n_rounds; o++) {
+            const proof_layout::Opening &op = lay.fri.op[o];
+            std::vector<Target> &evals = o < 4 ? q.evals[o] : q.step_evals[o - 4];
+            std::vector<HashOutTarget> &siblings = o < 4 ? q.siblings[o] : q.step_siblings[o - 4];
+            for (size_t i = 0; i < op.row_words; i++) evals.push_back(one());
+            for (size_t i = 0; i < op.path_len; i++) siblings.push_back(hash());
         }
     }
     return t;
@@ -120,7 +117,7 @@ ProofTargets add_virtual_proof(Builder &b, const CircuitPack &c) {
 
 // RecursiveChallenger (iop/challenger.rs): the duplex sponge of the transcript, in-circuit. observe buffers; a challenge first
 // absorbs the buffered inputs eight at a time (overwrite mode, one permutation per chunk), squeezes the rate part and pops from
-// the END of the output buffer — the order the prover's and the host verifier's transcripts use (csrc/prover_host.hpp).
+// the END of the output buffer — the order the prover's and the host verifier's transcripts use (csrc/challenger.hpp).
 struct RecursiveChallenger {
     Builder &b;
     Builder::State state;
