@@ -68,6 +68,19 @@ int qpgpu_verifier_verify_many(const qpgpu_verifier *v, const uint8_t *const *pr
 int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, struct qpgpu_ctx *ctx, const uint8_t *const *proofs, const size_t *lens,
                                       size_t count, unsigned threads, int *results, char *reasons, char *err);
 
+/* The same with flags. flags = 0 is qpgpu_verifier_verify_many_device exactly. QPGPU_VERIFY_HEAD_ON_DEVICE moves the rest of
+ * the verification to the GPU as well: canonical check, public-input hash, Fiat-Shamir transcript, proof of work, the
+ * vanishing polynomial at zeta against Z_H(zeta) * quotient(zeta), reduced openings and query indices run as kernels, so a
+ * proof goes from bytes to verdict without the host reading its contents. The host checks pointer and length, copies each proof
+ * into the pinned chunk (`threads` bounds the copying threads only) and puts the verdict codes into the host verifier's words.
+ * Verdicts, reasons, return value and err are unchanged: qpgpu_verifier_verify is the specification for both heads. All other
+ * rules are those of qpgpu_verifier_verify_many_device; an unknown flag is QPGPU_EINVAL. Meant for callers with few host
+ * threads to spare; a proof's transcript is a chain of about 120 dependent permutations, so a small batch may well be slower
+ * than with the host head. Its timings have not been measured yet (profiles/verify_device_head.txt). Default off. */
+#define QPGPU_VERIFY_HEAD_ON_DEVICE 1u
+int qpgpu_verifier_verify_many_device_ex(const qpgpu_verifier *v, struct qpgpu_ctx *ctx, const uint8_t *const *proofs, const size_t *lens,
+                                         size_t count, unsigned threads, unsigned flags, int *results, char *reasons, char *err);
+
 #ifdef __cplusplus
 }
 #endif

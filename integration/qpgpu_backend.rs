@@ -76,6 +76,9 @@ extern "C" {
     // the query rounds of a batch of proofs on ctx's GPU; results / err as qpgpu_verifier_verify_many, reasons: count * 200 bytes or null
     pub fn qpgpu_verifier_verify_many_device(v: *const QpgpuVerifier, ctx: *mut QpgpuCtx, proofs: *const *const u8, lens: *const usize, count: usize,
                                              threads: u32, results: *mut i32, reasons: *mut c_char, err: *mut c_char) -> i32;
+    // the same with flags: 1 (QPGPU_VERIFY_HEAD_ON_DEVICE) runs the transcript, proof of work and quotient identity on the GPU too
+    pub fn qpgpu_verifier_verify_many_device_ex(v: *const QpgpuVerifier, ctx: *mut QpgpuCtx, proofs: *const *const u8, lens: *const usize, count: usize,
+                                                threads: u32, flags: u32, results: *mut i32, reasons: *mut c_char, err: *mut c_char) -> i32;
     // include/qpgpu.h — the proving pool over one GPU or several: one queue, a worker set per device,
     // proofs written into the caller's host buffers
     pub fn qpgpu_pool_create_multi(devices: *const i32, n_devices: u32, pack: *const u64, n_words: usize, workers_per_device: u32,

@@ -48,6 +48,7 @@ def load_library():
         "qpgpu_verifier_verify": (c.c_int, [vp, c.c_char_p, c.c_size_t, c.c_char_p]),
         "qpgpu_verifier_verify_many": (c.c_int, [vp, vp, vp, c.c_size_t, c.c_uint, vp, c.c_char_p]),
         "qpgpu_verifier_verify_many_device": (c.c_int, [vp, vp, vp, vp, c.c_size_t, c.c_uint, vp, vp, c.c_char_p]),
+        "qpgpu_verifier_verify_many_device_ex": (c.c_int, [vp, vp, vp, vp, c.c_size_t, c.c_uint, c.c_uint, vp, vp, c.c_char_p]),
         "qpgpu_ctx_create": (c.c_int, [c.c_int, c.POINTER(vp)]),
         "qpgpu_ctx_destroy": (None, [vp]),
         "qpgpu_last_error": (c.c_char_p, [vp]),
@@ -518,10 +519,16 @@ class Verifier:
         self.reason = err.value.decode()
         return rc == 0
 
-    def verify_many(self, proofs, threads=0, gpu=None):
+    HEAD_ON_DEVICE = 1      # QPGPU_VERIFY_HEAD_ON_DEVICE
+
+    def verify_many(self, proofs, threads=0, gpu=None, device_head=False):
         """[accepted?] per proof, verified on up to `threads` host threads (0 = all cores); .reason names the first rejection.
         gpu: a QpGpu whose device runs the query rounds (qpgpu_verifier_verify_many_device; its hasher must be the verifier's);
-        then .reasons holds the verifier's text for every proof ("" when accepted) and .results the codes."""
+        then .reasons holds the verifier's text for every proof ("" when accepted) and .results the codes. device_head (with
+        gpu): the transcript, proof of work and quotient identity run on the device too (qpgpu_verifier_verify_many_device_ex,
+        QPGPU_VERIFY_HEAD_ON_DEVICE); same verdicts and texts."""
+        if device_head and gpu is None:
+            raise ValueError("device_head=True needs gpu=")
         n = len(proofs)
         if n == 0:
             self.reasons, self.results = [], []
@@ -535,7 +542,8 @@ class Verifier:
             self.lib.qpgpu_verifier_verify_many(self.h, ptrs, lens, n, threads, res, err)
         else:
             rows = ctypes.create_string_buffer(200 * n)
-            rc = self.lib.qpgpu_verifier_verify_many_device(self.h, gpu.ctx, ptrs, lens, n, threads, res, rows, err)
+            rc = self.lib.qpgpu_verifier_verify_many_device_ex(self.h, gpu.ctx, ptrs, lens, n, threads,
+                                                               self.HEAD_ON_DEVICE if device_head else 0, res, rows, err)
             if rc not in (0, -6):
                 raise QpGpuError(rc, err.value.decode())
             raw = rows.raw

@@ -25,6 +25,7 @@ hipError_t merkle_tp_rows(const u64 *rows, u64 n_leaves, u32 width, u64 *digests
 hipError_t merkle_tp_nodes(const u64 *in, u64 *out, u64 n_out, u32 batch, u64 ps, const HasherDev &h, hipStream_t st);
 hipError_t merkle_tp_pow(const PowArgs &a, dim3 g, const HasherDev &h, hipStream_t st);
 hipError_t verify_upload_constants(const u64 *rc360);   // verify_kernels.hip
+hipError_t verify_head_upload_constants(const u64 *rc360);   // verify_head_kernels.hip
 // matrix-pipe build (merkle_kernels_mx.hip)
 hipError_t merkle_mx_upload_constants(const u64 *rc360);
 hipError_t merkle_mx_leaves(const MerkleLeafArgs &a, u64 total, const HasherDev &h, hipStream_t st);
@@ -70,7 +71,8 @@ bool merkle_mx_in_use() { return mx_enabled(); }
 hipError_t merkle_upload_constants(const u64 *rc360) {
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_poseidon_rc), rc360, sizeof(u64) * poseidon::ROUNDS * poseidon::WIDTH);
     if (e == hipSuccess) e = merkle_tp_upload_constants(rc360);
-    if (e == hipSuccess) e = verify_upload_constants(rc360);     // the batch verifier's unit (verify_kernels.hip)
+    if (e == hipSuccess) e = verify_upload_constants(rc360);     // the batch verifier's units (verify_kernels.hip, verify_head_kernels.hip)
+    if (e == hipSuccess) e = verify_head_upload_constants(rc360);
     if (e != hipSuccess || !mx_enabled()) return e;       // QPGPU_MX=0: no matrix build, no table, no device self-test
     return merkle_mx_upload_constants(rc360);
 }

@@ -172,6 +172,14 @@ int qpgpu_verifier_create(const uint64_t *pack_words, size_t n_words, const uint
         host_cs_cap(p, H, v->cs_cap);
     }
     v->layout = proof_layout::of(p);
+    {   // the consistency check vanishing_at_zeta makes of the gate table does not read the openings: asked once, on zeros, for
+        // the device head (verify_device.cpp), which reports it where verify_head does
+        const size_t nch = p.num_challenges;
+        const std::vector<e2> zero(std::max<size_t>(std::max<size_t>(p.num_cs_cols(), p.num_wires), nch * (1 + p.num_partial_products)) + 8, E(0));
+        const e2 z = E(0), four[4] = {z, z, z, z};
+        std::vector<e2> van;
+        v->pack_why = vmath::vanishing_at_zeta<e2>(p, z, z, zero.data(), zero.data(), zero.data(), zero.data(), zero.data(), four, four, four, four, van);
+    }
     *out = v;
     return QPGPU_OK;
 }

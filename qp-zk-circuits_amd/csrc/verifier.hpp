@@ -3,6 +3,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string>
 #include <vector>
 #include "circuit.hpp"
 #include "gl64.hpp"
@@ -14,6 +15,7 @@ struct qpgpu_verifier {
     hasher::Config hash;
     std::vector<gl::u64> cs_cap;
     proof_layout::Proof layout;      // byte layout of this circuit's proofs
+    std::string pack_why;            // "" or what vanishing_at_zeta finds inconsistent in the pack's gate table (it depends on the pack alone)
 };
 
 // Everything the query rounds need, as the head of verify_impl leaves it: the transcript replayed through the proof of work,

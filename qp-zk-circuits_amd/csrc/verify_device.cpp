@@ -6,6 +6,11 @@
 //      through the context's pinned read-back
 //   3. per proof, the first failing query's verdict written out in the host verifier's words
 // The verdict and reason of every proof are the host verifier's (qpgpu_verifier_verify); the host query loop is the specification.
+//
+// qpgpu_verifier_verify_many_device_ex with QPGPU_VERIFY_HEAD_ON_DEVICE moves phase 1 to the device as well
+// (verify_head_kernels.hip): the host checks pointer and length, copies the proof into the pinned chunk and, once per call,
+// states the layout and asks verify_math.hpp whether the pack's gate table is consistent; the transcript, the proof of work and
+// the quotient identity are kernels, and a proof goes from bytes to verdict without the host reading its contents.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -20,6 +25,7 @@
 #include "ctx.hpp"
 #include "verifier.hpp"
 #include "verify_kernels.hpp"
+#include "verify_math.hpp"
 
 using gl::u64;
 
@@ -71,6 +77,42 @@ void query_reason(char *out, size_t qi, uint32_t code) {
     }
 }
 
+// what the head kernels read, beyond VerifyLayout; false: a gate beyond the bounds of the device code's local arrays
+bool make_head_layout(const qpgpu_verifier *v, const VerifyLayout &lay, HeadLayout &hl, std::string &pack_why) {
+    const CircuitPack &c = v->pack;
+    const proof_layout::Proof &p = v->layout;
+    if (c.num_challenges > 4 || c.gates.size() > 60000) return false;
+    for (const GateInfo &g : c.gates)
+        if (g.type == GATE_RANDOM_ACCESS && g.param0 > vmath::MAX_RANDOM_ACCESS_BITS) return false;
+    hl = HeadLayout();
+    hl.cap_words = (uint32_t)(p.cap_bytes / 8);
+    hl.n_rounds = (uint32_t)c.arity_bits.size();
+    for (int i = 0; i < 7; i++) { hl.open_pos[i] = (uint32_t)p.openings[i].pos; hl.open_cnt[i] = (uint32_t)p.openings[i].count; }
+    hl.fri_caps_pos = (uint32_t)p.fri_caps_pos; hl.final_pos = (uint32_t)p.final_pos; hl.pow_pos = (uint32_t)p.pow_pos;
+    hl.pis_pos = (uint32_t)p.pis_pos; hl.n_pis = (uint32_t)c.num_public_inputs; hl.total = (uint32_t)p.total;
+    hl.degree_bits = (uint32_t)c.degree_bits; hl.pow_bits = (uint32_t)c.proof_of_work_bits;
+    hl.num_selectors = (uint32_t)c.num_selectors; hl.num_constants = (uint32_t)c.num_constants; hl.num_routed = (uint32_t)c.num_routed_wires;
+    hl.num_pp = (uint32_t)c.num_partial_products; hl.qdf = (uint32_t)c.quotient_degree_factor;
+    hl.n_gates = (uint32_t)c.gates.size(); hl.n_slots = hl.n_gates + 2;
+    hl.gate_term0 = (uint32_t)(c.num_challenges * (2 + c.num_partial_products));
+    hl.hrec_words = HREC_WORDS;
+    std::memcpy(hl.digest, c.circuit_digest, sizeof hl.digest);
+    hl.p2 = c.p2_layout;
+    pack_why = v->pack_why;      // vanishing_at_zeta's check of the gate table, asked once when the verifier was created
+    hl.pack_bad = pack_why.empty() ? 0 : 1;
+    return true;
+}
+
+// the host verifier's words for a head verdict (verifier.cpp: verify_head)
+void head_reason(char *out, uint32_t code, const CircuitPack &c, const std::string &pack_why) {
+    switch (code >> 8) {
+    case VH_NONCANONICAL: verify::fail(out, 0, "proof holds a non-canonical field element"); break;
+    case VH_POW: verify::fail(out, 0, "proof-of-work response has fewer than %llu leading zero bits", (unsigned long long)c.proof_of_work_bits); break;
+    case VH_PACK: verify::fail(out, 0, "%s", pack_why.c_str()); break;
+    default: verify::fail(out, 0, "quotient identity fails at zeta (challenge %zu): the openings do not satisfy the circuit", (size_t)(code & 0xff)); break;
+    }
+}
+
 double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -88,7 +130,14 @@ constexpr size_t CHUNK_BYTES = (size_t)256 << 20;
 
 extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_ctx *ctx, const uint8_t *const *proofs, const size_t *lens,
                                                  size_t count, unsigned threads, int *results, char *reasons, char *err) {
+    return qpgpu_verifier_verify_many_device_ex(v, ctx, proofs, lens, count, threads, 0, results, reasons, err);
+}
+
+extern "C" int qpgpu_verifier_verify_many_device_ex(const qpgpu_verifier *v, qpgpu_ctx *ctx, const uint8_t *const *proofs, const size_t *lens,
+                                                    size_t count, unsigned threads, unsigned flags, int *results, char *reasons, char *err) {
     if (!v || !ctx) return verify::fail(err, QPGPU_EINVAL, "null argument");
+    if (flags & ~(unsigned)QPGPU_VERIFY_HEAD_ON_DEVICE) return verify::fail(err, QPGPU_EINVAL, "verify_many_device: unknown flag");
+    const bool device_head = (flags & QPGPU_VERIFY_HEAD_ON_DEVICE) != 0;
     if (count == 0) return QPGPU_OK;
     if (!proofs || !lens || !results) return verify::fail(err, QPGPU_EINVAL, "null argument");
     if (!same_hasher(v->hash, ctx->hasher)) {
@@ -100,13 +149,25 @@ extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_
         ctx->fail(QPGPU_EINVAL, "verify_many_device: circuit outside the supported range");
         return verify::fail(err, QPGPU_EINVAL, "%s", ctx->err.c_str());
     }
+    HeadLayout hl;
+    std::string pack_why;
+    if (device_head && !make_head_layout(v, lay, hl, pack_why)) {
+        ctx->fail(QPGPU_EINVAL, "verify_many_device: circuit outside the supported range");
+        return verify::fail(err, QPGPU_EINVAL, "%s", ctx->err.c_str());
+    }
     if (threads == 0) threads = std::max(1u, std::thread::hardware_concurrency());
     const size_t cap_words = v->cs_cap.size(), SW = lay.stride_words, RW = lay.rec_words, nq = lay.nq;
+    // device head: the gate table (GateInfo, 8 words each) and k_is travel behind the cap
+    const size_t table_words = device_head ? 8 * v->pack.gates.size() + v->pack.k_is.size() : 0;
     const size_t chunk = std::max<size_t>(1, std::min(CHUNK_PROOFS, CHUNK_BYTES / (SW * 8)));
-    const size_t pin_bytes = (chunk * (SW + RW) + cap_words) * 8;
+    const size_t pin_bytes = (chunk * (SW + RW) + cap_words + table_words) * 8;
     const size_t mcode_off = (pin_bytes + 255) & ~(size_t)255, qcode_off = (mcode_off + chunk * nq * lay.n_open + 255) & ~(size_t)255;
-    const size_t dev_bytes = qcode_off + chunk * nq * 4;
-    std::vector<uint32_t> qcodes(chunk * nq);
+    // the head verdicts sit right behind the query verdicts of the chunk's proofs (one read-back); head records and slots follow
+    const size_t hrec_off = (qcode_off + chunk * (nq + 1) * 4 + 255) & ~(size_t)255;
+    const size_t part_off = hrec_off + (device_head ? chunk * HREC_WORDS * 8 : 0);
+    const size_t dev_bytes = part_off + (device_head ? chunk * hl.n_slots * VERIFY_PARTIAL_WORDS * 8 : 0);
+    std::vector<uint32_t> qcodes(chunk * (nq + 1));
+    std::vector<uint8_t> staged(device_head ? chunk : 0);
     std::vector<char> own_reasons;          // the caller's rows, or rows of our own for err
     if (!reasons) own_reasons.assign(count * QPGPU_VERIFY_ERR_CAP, 0);
     char *const rows = reasons ? reasons : own_reasons.data();
@@ -148,11 +209,38 @@ extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_
         // chunk layout, host and device alike: n proofs (SW words each), n records (RW words each), the constants/sigmas cap
         u64 *const h_proofs = pin, *const h_recs = pin + n * SW, *const h_cap = h_recs + n * RW;
         std::memcpy(h_cap, v->cs_cap.data(), cap_words * 8);
+        if (device_head) {
+            u64 *h_table = h_cap + cap_words;
+            std::memcpy(h_table, v->pack.gates.data(), 8 * v->pack.gates.size() * 8);
+            std::memcpy(h_table + 8 * v->pack.gates.size(), v->pack.k_is.data(), v->pack.k_is.size() * 8);
+        }
 
         // ---- phase 1: the head of every proof on host threads; the survivors staged ----
         auto t0 = std::chrono::steady_clock::now();
         std::atomic<size_t> next{0};
-        auto work = [&] {
+        // device head: pointer and length are all the host looks at; the proof is copied, its head is the device's
+        auto stage = [&] {
+            for (size_t k = next.fetch_add(1); k < n; k = next.fetch_add(1)) {
+                const size_t i = c0 + k;
+                u64 *rec = h_recs + k * RW;
+                rec[VREC_LIVE] = 0;
+                staged[k] = 0;
+                char *row = reason_row(i);
+                row[0] = 0;
+                if (!proofs[i]) { results[i] = QPGPU_EINVAL; continue; }
+                if (lens[i] != v->layout.total) {
+                    results[i] = verify::fail(row, QPGPU_EVERIFY, "proof has %zu bytes, this circuit's proofs have %zu", lens[i], v->layout.total);
+                    continue;
+                }
+                u64 *dst = h_proofs + k * SW;
+                dst[SW - 2] = 0; dst[SW - 1] = 0;
+                std::memcpy(dst, proofs[i], lens[i]);
+                rec[VREC_LIVE] = 1;
+                staged[k] = 1;
+                results[i] = QPGPU_EDEVICE;
+            }
+        };
+        auto head_work = [&] {
             char local[QPGPU_VERIFY_ERR_CAP];
             VerifyHead h;
             for (size_t k = next.fetch_add(1); k < n; k = next.fetch_add(1)) {
@@ -176,6 +264,7 @@ extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_
                 results[i] = QPGPU_EDEVICE;                 // until the device has decided
             }
         };
+        auto work = [&] { if (device_head) stage(); else head_work(); };
         const unsigned nt = (unsigned)std::min<size_t>(threads, n);
         std::vector<std::thread> pool;
         try {
@@ -184,14 +273,14 @@ extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_
         work();
         for (auto &t : pool) t.join();
         headed = c0 + n;
-        host_stat(ctx, "verify_many_device.head", ms_since(t0));
+        host_stat(ctx, device_head ? "verify_many_device.copy" : "verify_many_device.head", ms_since(t0));
         bool any = false;
         for (size_t k = 0; k < n && !any; k++) any = h_recs[k * RW + VREC_LIVE] != 0;
         if (!any) continue;
 
         // ---- phase 2: one copy of the chunk, the query-round kernels, the verdicts back ----
         t0 = std::chrono::steady_clock::now();
-        const size_t bytes = (n * (SW + RW) + cap_words) * 8;
+        const size_t bytes = (n * (SW + RW) + cap_words + table_words) * 8;
         hipError_t e = hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return device_fail(ctx->hip_fail(e, "hipMemcpyAsync (proofs of the chunk)"));
         if (ctx->profiling) {
@@ -199,19 +288,39 @@ extern "C" int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, qpgpu_
             host_stat(ctx, "verify_many_device.upload", ms_since(t0));
             t0 = std::chrono::steady_clock::now();
         }
-        const u64 *d_proofs = (const u64 *)dev, *d_recs = d_proofs + n * SW, *d_cap = d_recs + n * RW;
+        const u64 *d_proofs = (const u64 *)dev, *d_cap = d_proofs + n * (SW + RW);
+        u64 *d_recs = (u64 *)dev + n * SW;
         uint8_t *d_mcodes = dev + mcode_off;
-        uint32_t *d_qcodes = (uint32_t *)(dev + qcode_off);
+        uint32_t *d_qcodes = (uint32_t *)(dev + qcode_off), *d_hcodes = d_qcodes + n * nq;
+        if (device_head) {     // the records are the device's: transcript, identity slots, verdict; a rejected proof leaves not live
+            u64 *d_hrecs = (u64 *)(dev + hrec_off), *d_parts = (u64 *)(dev + part_off);
+            ctx->prof_begin("verify_many_device.transcript");
+            e = verify_head_transcript(lay, hl, d_proofs, d_recs, d_hrecs, (uint32_t)n, ctx->hasher_dev(), ctx->stream);
+            ctx->prof_end();
+            if (e != hipSuccess) return device_fail(ctx->hip_fail(e, "verify_head_transcript"));
+            ctx->prof_begin("verify_many_device.identity");
+            e = verify_head_identity(lay, hl, d_proofs, d_recs, d_hrecs, d_cap + cap_words, d_parts, (uint32_t)n, ctx->stream);
+            if (e == hipSuccess) e = verify_head_verdict(lay, hl, d_recs, d_hrecs, d_parts, d_hcodes, (uint32_t)n, ctx->stream);
+            ctx->prof_end();
+            if (e != hipSuccess) return device_fail(ctx->hip_fail(e, "verify_head_identity"));
+        }
+        ctx->prof_begin("verify_many_device.query");
         e = verify_query_rounds(lay, d_proofs, d_recs, d_cap, (uint32_t)n, d_mcodes, d_qcodes, ctx->hasher_dev(), ctx->stream);
+        ctx->prof_end();
         if (e != hipSuccess) return device_fail(ctx->hip_fail(e, "verify_query_rounds"));
-        if (int rc = ctx->read_back(qcodes.data(), d_qcodes, n * nq * 4)) return device_fail(rc);
+        if (int rc = ctx->read_back(qcodes.data(), d_qcodes, n * (nq + (device_head ? 1 : 0)) * 4)) return device_fail(rc);
         host_stat(ctx, "verify_many_device.kernels", ms_since(t0));
 
-        // ---- phase 3: the first failing query of each proof, in the host verifier's words ----
+        // ---- phase 3: the first failing check of each proof, in the host verifier's words ----
         t0 = std::chrono::steady_clock::now();
         for (size_t k = 0; k < n; k++) {
-            if (!h_recs[k * RW + VREC_LIVE]) continue;
+            if (!(device_head ? staged[k] != 0 : h_recs[k * RW + VREC_LIVE] != 0)) continue;
             const size_t i = c0 + k;
+            if (device_head && qcodes[n * nq + k]) {
+                results[i] = QPGPU_EVERIFY;
+                head_reason(reason_row(i), qcodes[n * nq + k], v->pack, pack_why);
+                continue;
+            }
             results[i] = QPGPU_OK;
             for (size_t q = 0; q < nq; q++) {
                 const uint32_t code = qcodes[k * nq + q];

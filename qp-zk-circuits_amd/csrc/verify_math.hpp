@@ -5,7 +5,15 @@
 //   X = wrapper_circuit.cpp's XT     the same expressions over ExtensionTargets of the circuit builder — the in-circuit verifier
 //                                    (plonk/vanishing_poly.rs eval_vanishing_poly_circuit, gates/*.rs eval_unfiltered_circuit), so
 //                                    that the circuit enforces exactly what the host verifier checks.
+//   X = gl::e2 in a kernel           the identity kernel of batch verification (verify_head_kernels.hip): the same field
+//                                    elements on the device, one thread per (proof, gate).
 // X needs: X + X, X - X, X * X, scale(X, u64), sadd(X a, u64 s, X c) = s a + c, madd(X a, X b, X c) = a b + c, and konst<X>(u64).
+//
+// Host and device: everything up to gate_constraints_to is __host__ __device__ in a HIP unit and uses no heap. Constraints are
+// written through `out[k++] = value` in increasing k, so `out` may be a pointer (host: the terms are kept) or a sink that
+// weights each value as it arrives (device). The Poseidon / Poseidon2 tables come through tables(): the host's tables, or,
+// in the device pass of a unit that defines VMATH_DEVICE_TABLES and the arrays of namespace vmath_dev first, that unit's
+// device-resident copies. vanishing_at_zeta (strings, vectors, the pack) stays host only.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -13,13 +21,19 @@
 #include "gl64.hpp"
 #include "poseidon.hpp"
 
+#if defined(__HIPCC__)
+#define VM_HD __host__ __device__
+#else
+#define VM_HD
+#endif
+
 namespace gl {
-inline e2 operator+(e2 x, e2 y) { return e2_add(x, y); }
-inline e2 operator-(e2 x, e2 y) { return e2_sub(x, y); }
-inline e2 operator*(e2 x, e2 y) { return e2_mul(x, y); }
-inline e2 scale(e2 x, u64 s) { return e2_scale(x, s); }
-inline e2 sadd(e2 a, u64 s, e2 c) { return e2_add(e2_scale(a, s), c); }
-inline e2 madd(e2 a, e2 b, e2 c) { return e2_add(e2_mul(a, b), c); }
+GL_HD e2 operator+(e2 x, e2 y) { return e2_add(x, y); }
+GL_HD e2 operator-(e2 x, e2 y) { return e2_sub(x, y); }
+GL_HD e2 operator*(e2 x, e2 y) { return e2_mul(x, y); }
+GL_HD e2 scale(e2 x, u64 s) { return e2_scale(x, s); }
+GL_HD e2 sadd(e2 a, u64 s, e2 c) { return e2_add(e2_scale(a, s), c); }
+GL_HD e2 madd(e2 a, e2 b, e2 c) { return e2_add(e2_mul(a, b), c); }
 }  // namespace gl
 
 namespace vmath {
@@ -27,15 +41,32 @@ using gl::u64;
 
 template <class X> X konst(u64 c);
 template <> inline gl::e2 konst<gl::e2>(u64 c) { return gl::e2_from(c); }
+// konst as the shared text calls it: an element type of the host states konst<X> (above); gl::e2 is host and device
+template <class X> struct Konst { static X of(u64 c) { return konst<X>(c); } };
+template <> struct Konst<gl::e2> { VM_HD static gl::e2 of(u64 c) { return gl::e2_from(c); } };
+
+// bound of the local array that stands where the host once used a vector (the items of a RandomAccess copy): the pack parser
+// refuses a gate beyond it (circuit.cpp: validate), and the device head checks it again when it builds its gate table
+constexpr u64 MAX_RANDOM_ACCESS_BITS = 5;
+
+// the tables of the hash gates: plonky2's ALL_ROUND_CONSTANTS, its fast-partial-round tables, qp-poseidon-core's Poseidon2 set
+struct GateTables { const u64 *rc, *fp; const poseidon2::Params *p2; };
+VM_HD inline GateTables tables() {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(VMATH_DEVICE_TABLES)
+    return {vmath_dev::poseidon_rc, vmath_dev::poseidon_fp, &vmath_dev::poseidon2_qp};
+#else
+    return {poseidon::host_round_constants(), poseidon::host_fast_partial(), &poseidon2::qp_params()};
+#endif
+}
 
 // the extension ALGEBRA over the extension (wire pairs of the *Extension gates at zeta): c0 + c1 X, X^2 = 7, coefficients in X
 template <class X> struct AlgT { X c0, c1; };
-template <class X> AlgT<X> alg_mul(AlgT<X> a, AlgT<X> b) { return {madd(a.c0, b.c0, scale(a.c1 * b.c1, 7)), madd(a.c0, b.c1, a.c1 * b.c0)}; }
+template <class X> VM_HD AlgT<X> alg_mul(AlgT<X> a, AlgT<X> b) { return {madd(a.c0, b.c0, scale(a.c1 * b.c1, 7)), madd(a.c0, b.c1, a.c1 * b.c0)}; }
 
 // ---- gate constraints at one point of the extension field ----
-template <class X> X sbox7(X x) { const X x2 = x * x, x4 = x2 * x2; return (x * x2) * x4; }
-template <class X> void mds_ext(X (&s)[12]) {   // the MDS matrix has base-field entries: out[r] = sum_i circ[i] s[(i + r) % 12] + diag[r] s[r]
-    static const u64 CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
+template <class X> VM_HD X sbox7(X x) { const X x2 = x * x, x4 = x2 * x2; return (x * x2) * x4; }
+template <class X> VM_HD void mds_ext(X (&s)[12]) {   // the MDS matrix has base-field entries: out[r] = sum_i circ[i] s[(i + r) % 12] + diag[r] s[r]
+    constexpr u64 CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
     X t[12];
     for (int r = 0; r < 12; r++) {
         X acc = r == 0 ? scale(s[0], CIRC[0] + 8) : scale(s[r], CIRC[0]);
@@ -47,9 +78,10 @@ template <class X> void mds_ext(X (&s)[12]) {   // the MDS matrix has base-field
 
 // PoseidonGate (plonky2::gates::poseidon): wires 0..11 input, 12..23 output, 24 swap, 25..28 delta, 29..64 S-box inputs of
 // full rounds 1..3, 65..86 of the 22 partial rounds, 87..134 of the last four full rounds; 123 constraints.
-template <class X> void poseidon_gate(const X *w, X *out) {
-    auto E = [](u64 c) { return konst<X>(c); };
-    const u64 *rc = poseidon::host_round_constants(), *fp = poseidon::host_fast_partial();
+template <class X, class Out> VM_HD void poseidon_gate(const X *w, Out out) {
+    auto E = [](u64 c) { return Konst<X>::of(c); };
+    const GateTables T = tables();
+    const u64 *rc = T.rc, *fp = T.fp;
     size_t k = 0;
     const X swap = w[24];
     X st[12];
@@ -93,8 +125,8 @@ template <class X> void poseidon_gate(const X *w, X *out) {
 // (circuit.hpp P2GateLayout; default = upstream PoseidonGate's layout carried over, LAYOUT UNPINNED), permutation =
 // qp-poseidon-core's Poseidon2 (pinned by the reference's known-answer vectors). The linear layers have base-field entries, so
 // they act on an extension element coefficient-wise (scale); only the S-boxes multiply extension elements.
-template <class X> void p2_external(X (&s)[12], const poseidon2::Params &P) {
-    auto E = [](u64 c) { return konst<X>(c); };
+template <class X> VM_HD void p2_external(X (&s)[12], const poseidon2::Params &P) {
+    auto E = [](u64 c) { return Konst<X>::of(c); };
     X t[12];
     for (int b = 0; b < 3; b++)
         for (int i = 0; i < 4; i++) {
@@ -107,15 +139,15 @@ template <class X> void p2_external(X (&s)[12], const poseidon2::Params &P) {
         for (int b = 0; b < 3; b++) s[4 * b + i] = t[4 * b + i] + colsum;
     }
 }
-template <class X> void p2_internal(X (&s)[12], const poseidon2::Params &P) {
-    auto E = [](u64 c) { return konst<X>(c); };
+template <class X> VM_HD void p2_internal(X (&s)[12], const poseidon2::Params &P) {
+    auto E = [](u64 c) { return Konst<X>::of(c); };
     X total = E(0);
     for (int i = 0; i < 12; i++) total = total + s[i];
     for (int i = 0; i < 12; i++) s[i] = sadd(s[i], P.diag_m1[i], total);
 }
-template <class X> size_t poseidon2_gate(const P2GateLayout &lay, const X *w, X *out) {
-    auto E = [](u64 c) { return konst<X>(c); };
-    const poseidon2::Params &P = poseidon2::qp_params();
+template <class X, class Out> VM_HD size_t poseidon2_gate(const P2GateLayout &lay, const X *w, Out out) {
+    auto E = [](u64 c) { return Konst<X>::of(c); };
+    const poseidon2::Params &P = *tables().p2;
     size_t k = 0;
     X st[12];
     for (int i = 0; i < 12; i++) st[i] = w[lay.w_input + i];
@@ -152,12 +184,12 @@ template <class X> size_t poseidon2_gate(const P2GateLayout &lay, const X *w, X 
     return k;
 }
 
-// the unfiltered constraints of gate g in upstream order; returns how many were written
-template <class X> size_t gate_constraints(const GateInfo &g, const P2GateLayout &p2_layout, const X *consts, const X *w, const X pih[4], std::vector<X> &out) {
-    auto E = [](u64 c) { return konst<X>(c); };
+// the unfiltered constraints of gate g in upstream order, written to out[0], out[1], ... in that order; returns how many
+template <class X, class Out>
+VM_HD size_t gate_constraints_to(const GateInfo &g, const P2GateLayout &p2_layout, const X *consts, const X *w, const X pih[4], Out out) {
+    auto E = [](u64 c) { return Konst<X>::of(c); };
     using Alg = AlgT<X>;
     size_t k = 0;
-    out.assign((size_t)g.num_constraints + 8, E(0));
     switch (g.type) {
         case GATE_NOOP: break;
         case GATE_CONSTANT:
@@ -170,11 +202,11 @@ template <class X> size_t gate_constraints(const GateInfo &g, const P2GateLayout
             for (u64 i = 0; i < g.param0; i++) out[k++] = w[4 * i + 3] - ((w[4 * i] * w[4 * i + 1]) * consts[0] + w[4 * i + 2] * consts[1]);
             break;
         case GATE_POSEIDON:
-            poseidon_gate(w, out.data());
+            poseidon_gate(w, out);
             k = 123;
             break;
         case GATE_POSEIDON2:
-            k = poseidon2_gate(p2_layout, w, out.data());
+            k = poseidon2_gate(p2_layout, w, out);
             break;
         case GATE_BASE_SUM: {           // wire 0 = sum, wires 1..num_limbs = bits (little endian)
             X s = E(0);
@@ -217,7 +249,7 @@ template <class X> size_t gate_constraints(const GateInfo &g, const P2GateLayout
         case GATE_RANDOM_ACCESS: {      // per copy: access_index, claimed_element, 2^bits items; the bit wires follow the routed ones
             const u64 bits = g.param0, copies = g.param1, extra = g.param2, vec = 1ull << bits;
             const u64 routed = (2 + vec) * copies + extra;
-            std::vector<X> items(vec);
+            X items[(size_t)1 << MAX_RANDOM_ACCESS_BITS];
             for (u64 c = 0; c < copies; c++) {
                 const X *cw = w + (2 + vec) * c, *bw = w + routed + c * bits;
                 for (u64 i = 0; i < vec; i++) items[i] = cw[2 + i];
@@ -246,7 +278,7 @@ template <class X> size_t gate_constraints(const GateInfo &g, const P2GateLayout
             break;
         }
         case GATE_POSEIDON_MDS: {       // 12 algebra elements in (wires 0..24), 12 out (24..48): out - MDS * in
-            static const u64 CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
+            constexpr u64 CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
             for (int r = 0; r < 12; r++)
                 for (int comp = 0; comp < 2; comp++) {
                     X s = r == 0 ? scale(w[comp], 8) : E(0);
@@ -258,21 +290,23 @@ template <class X> size_t gate_constraints(const GateInfo &g, const P2GateLayout
         case GATE_COSET_INTERPOLATION: {   // shift, 2^bits values (algebra), evaluation point, value, intermediates, shifted point
             const u64 bits = g.param0, degree = g.param1, np = 1ull << bits, ni = (np - 2) / (degree - 1);
             const u64 s_ep = 1 + 2 * np, s_ev = s_ep + 2, s_int = s_ev + 2;
-            // barycentric weights of the subgroup of order np: 1 / prod_{j != i} (x_i - x_j) = x_i / np
-            std::vector<u64> dom(np), wt(np);
-            { const u64 om = gl::root_of_unity((unsigned)bits), ninv = gl::inv(np); u64 x = 1; for (u64 i = 0; i < np; i++) { dom[i] = x; wt[i] = gl::mul(x, ninv); x = gl::mul(x, om); } }
+            // barycentric weights of the subgroup of order np: 1 / prod_{j != i} (x_i - x_j) = x_i / np. The chunks below visit the
+            // points q = 0, 1, ... once each in increasing order, so the point x_q = om^q is carried along instead of tabulated
+            const u64 om = gl::root_of_unity((unsigned)bits), ninv = gl::inv(np);
+            u64 xq = 1;
             const X shift = w[0];
             const Alg ep = {w[s_ep], w[s_ep + 1]}, sp = {w[s_int + 4 * ni], w[s_int + 4 * ni + 1]};
             out[k++] = ep.c0 - sp.c0 * shift; out[k++] = ep.c1 - sp.c1 * shift;
             Alg ev = {E(0), E(0)}, pr = {E(1), E(0)};
             u64 lo = 0, hi = degree;
             for (u64 c = 0; c <= ni; c++) {
-                for (u64 q = lo; q < hi; q++) {      // partial_interpolate_ext_algebra
+                for (u64 q = lo; q < hi; q++, xq = gl::mul(xq, om)) {      // partial_interpolate_ext_algebra
+                    const u64 dom_q = xq, wt_q = gl::mul(xq, ninv);
                     Alg term = sp;
-                    term.c0 = term.c0 - E(dom[q]);
+                    term.c0 = term.c0 - E(dom_q);
                     const Alg t = alg_mul(Alg{w[1 + 2 * q], w[2 + 2 * q]}, pr);
                     ev = alg_mul(ev, term);
-                    ev.c0 = ev.c0 + scale(t.c0, wt[q]); ev.c1 = ev.c1 + scale(t.c1, wt[q]);
+                    ev.c0 = ev.c0 + scale(t.c0, wt_q); ev.c1 = ev.c1 + scale(t.c1, wt_q);
                     pr = alg_mul(pr, term);
                 }
                 if (c == ni) break;
@@ -280,7 +314,7 @@ template <class X> size_t gate_constraints(const GateInfo &g, const P2GateLayout
                 out[k++] = ie.c0 - ev.c0; out[k++] = ie.c1 - ev.c1;
                 out[k++] = ip.c0 - pr.c0; out[k++] = ip.c1 - pr.c1;
                 ev = ie; pr = ip;
-                lo = 1 + (degree - 1) * (c + 1); hi = std::min<u64>(lo + degree - 1, np);
+                lo = 1 + (degree - 1) * (c + 1); hi = lo + degree - 1 < np ? lo + degree - 1 : np;
             }
             out[k++] = w[s_ev] - ev.c0; out[k++] = w[s_ev + 1] - ev.c1;
             break;
@@ -291,15 +325,43 @@ template <class X> size_t gate_constraints(const GateInfo &g, const P2GateLayout
 }
 
 
+// the same into a vector of the host (num_constraints + 8 elements, zero where the gate writes nothing)
+template <class X> size_t gate_constraints(const GateInfo &g, const P2GateLayout &p2_layout, const X *consts, const X *w, const X pih[4], std::vector<X> &out) {
+    out.assign((size_t)g.num_constraints + 8, Konst<X>::of(0));
+    return gate_constraints_to(g, p2_layout, consts, w, pih, out.data());
+}
+
+// one chunk of the permutation argument's partial products: prev * prod_j (w_j + beta k_j zeta + gamma) - next * prod_j (w_j +
+// beta sigma_j + gamma) over the routed wires j in [lo, hi). o_sig: the sigma openings; zeta_beta = zeta * beta.
+template <class X>
+VM_HD X partial_product_term(const X &prev, const X &next, const X &zeta_beta, const X &beta, const X &gamma, const u64 *k_is, const X *o_w,
+                             const X *o_sig, size_t lo, size_t hi) {
+    X pn = prev, pd = next;
+    for (size_t j = lo; j < hi; j++) {
+        pn = pn * (sadd(zeta_beta, k_is[j], o_w[j]) + gamma);
+        pd = pd * (madd(o_sig[j], beta, o_w[j]) + gamma);
+    }
+    return pn - pd;
+}
+
+// compute_filter of gate gi with selector opening s: prod_{j in group, j != gate} (j - s), times (UNUSED - s) with several selectors
+template <class X> VM_HD X gate_filter(const GateInfo &g, u64 gi, const X &s, const X &one, u64 num_selectors) {
+    X f = one;
+    for (u64 j = g.group_start; j < g.group_end; j++) if (j != gi) f = f * (Konst<X>::of(j) - s);
+    if (num_selectors > 1) f = f * (Konst<X>::of(0xFFFFFFFFull) - s);
+    return f;
+}
+
 // eval_vanishing_poly at zeta: the Z(1) = 1 terms, the partial-product checks and the filtered gate constraints, reduced with
 // each alpha (Horner from the last term); out[k] for challenge k. l0 = L_0(zeta), the caller's (it needs a division).
-// betas / gammas / alphas: num_challenges elements each, lifted to X by the caller. Returns "" or what is inconsistent in the pack.
+// betas / gammas / alphas: num_challenges elements each, lifted to X by the caller. Returns "" or what is inconsistent in the
+// pack; that answer depends on the pack alone, not on the openings (the device head asks once per call, on openings of zeros).
 template <class X>
 std::string vanishing_at_zeta(const CircuitPack &c, const X &zeta, const X &l0, const X *o_cs, const X *o_w, const X *o_zs, const X *o_zn, const X *o_pp,
                               const X *betas, const X *gammas, const X *alphas, const X pih[4], std::vector<X> &out) {
     const size_t R = c.num_routed_wires, nch = c.num_challenges, npp = c.num_partial_products, nchunks = npp + 1, chunk = c.quotient_degree_factor;
     const size_t sig0 = c.num_selectors + c.num_constants;
-    const X one = konst<X>(1);
+    const X one = Konst<X>::of(1);
     std::vector<X> terms;
     terms.reserve(nch + nch * nchunks + c.num_gate_constraints);
     for (size_t k = 0; k < nch; k++) terms.push_back(l0 * (o_zs[k] - one));
@@ -308,23 +370,16 @@ std::string vanishing_at_zeta(const CircuitPack &c, const X &zeta, const X &l0, 
         for (size_t cc = 0; cc < nchunks; cc++) {
             const X prev = cc == 0 ? o_zs[k] : o_pp[k * npp + cc - 1];
             const X next = cc == nchunks - 1 ? o_zn[k] : o_pp[k * npp + cc];
-            X pn = prev, pd = next;
-            for (size_t j = cc * chunk; j < (cc + 1) * chunk && j < R; j++) {
-                pn = pn * (sadd(zeta_beta, c.k_is[j], o_w[j]) + gammas[k]);
-                pd = pd * (madd(o_cs[sig0 + j], betas[k], o_w[j]) + gammas[k]);
-            }
-            terms.push_back(pn - pd);
+            terms.push_back(partial_product_term(prev, next, zeta_beta, betas[k], gammas[k], c.k_is.data(), o_w, o_cs + sig0, cc * chunk,
+                                                 std::min((cc + 1) * chunk, R)));
         }
     }
-    std::vector<X> gate_terms(c.num_gate_constraints, konst<X>(0)), cst;
+    std::vector<X> gate_terms(c.num_gate_constraints, Konst<X>::of(0)), cst;
     const X *consts = o_cs + c.num_selectors;
     for (size_t gi = 0; gi < c.gates.size(); gi++) {
         const GateInfo &g = c.gates[gi];
         if (g.num_constraints == 0) continue;
-        const X s = o_cs[g.selector_index];
-        X f = one;            // compute_filter: prod_{j in group, j != gate} (j - s), times (UNUSED - s) with several selectors
-        for (u64 j = g.group_start; j < g.group_end; j++) if (j != gi) f = f * (konst<X>(j) - s);
-        if (c.num_selectors > 1) f = f * (konst<X>(0xFFFFFFFFull) - s);
+        const X f = gate_filter(g, gi, o_cs[g.selector_index], one, c.num_selectors);
         const size_t cnt = gate_constraints(g, c.p2_layout, consts, o_w, pih, cst);
         if (cnt != g.num_constraints || cnt > gate_terms.size())
             return "gate " + std::to_string(gi) + ": the pack declares " + std::to_string(g.num_constraints) + " constraints, the gate has " + std::to_string(cnt);
@@ -333,7 +388,7 @@ std::string vanishing_at_zeta(const CircuitPack &c, const X &zeta, const X &l0, 
     terms.insert(terms.end(), gate_terms.begin(), gate_terms.end());
     out.clear();
     for (size_t k = 0; k < nch; k++) {
-        X acc = konst<X>(0);
+        X acc = Konst<X>::of(0);
         for (size_t j = terms.size(); j-- > 0;) acc = madd(acc, alphas[k], terms[j]);
         out.push_back(acc);
     }

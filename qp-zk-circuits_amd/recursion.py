@@ -180,10 +180,12 @@ class PrivateBatchProver:
                  verify_on_device=False):
         """zero_knowledge / num_routed_wires: wormhole_private_batch_circuit_config (common/src/circuit.rs:396-402) — the one
         zero-knowledge layer of the stack, 60 routed wires. verify_on_device: commit runs the query rounds of the leaf proofs'
-        verification on `gpu` (Verifier.verify_many(gpu=...)); same verdicts and messages as the host verifier."""
+        verification on `gpu` (Verifier.verify_many(gpu=...)); "full": the head of verification too (device_head=True); same
+        verdicts and messages as the host verifier."""
         from . import aggregation, leaf as leaf_mod
         self.pkg, self.gpu, self.N, self.A = pkg, gpu, num_leaf_proofs, aggregation
         self.verify_gpu = gpu if verify_on_device else None
+        self.verify_device_head = verify_on_device == "full"
         self.own_leaf_prover = leaf_prover is None
         self.leaf_prover = leaf_prover or leaf_mod.LeafProver(pkg, gpu, leaf_circuit)
         self.leaf_verifier = pkg.Verifier(leaf_circuit.pack, circuit=self.leaf_prover.circ)
@@ -220,7 +222,7 @@ class PrivateBatchProver:
         rows = np.stack([A.proof_public_inputs(p, 21) for p in leaf_proofs]) if len(leaf_proofs) else np.zeros((0, 21), dtype=np.uint64)
         rows = np.ascontiguousarray(rows, dtype=np.uint64)
         A._call(A._lib().qpgpu_private_batch_preflight, rows.ctypes.data if rows.size else None, rows.shape[0], N)
-        for i, ok in enumerate(self.leaf_verifier.verify_many(list(leaf_proofs), gpu=self.verify_gpu)):
+        for i, ok in enumerate(self.leaf_verifier.verify_many(list(leaf_proofs), gpu=self.verify_gpu, device_head=self.verify_device_head and self.verify_gpu is not None)):
             if not ok:
                 raise ValueError("leaf proof %d failed verification against the pinned leaf verifier" % i)
         src = np.zeros(N, dtype=np.uint32); pre = np.zeros(4 * N, dtype=np.uint64)
@@ -260,10 +262,12 @@ class PublicBatchProver:
     (no shuffle), the aggregator address as a witness input that becomes the first four public inputs."""
 
     def __init__(self, pkg, gpu, private_prover, num_private_batch_proofs, verify=True, verify_on_device=False):
-        """verify_on_device: commit runs the query rounds of the private-batch proofs' verification on `gpu`."""
+        """verify_on_device: commit runs the query rounds of the private-batch proofs' verification on `gpu`; "full": the head
+        of verification too (Verifier.verify_many(device_head=True))."""
         from . import aggregation
         self.pkg, self.gpu, self.M, self.N, self.A = pkg, gpu, num_private_batch_proofs, private_prover.N, aggregation
         self.verify_gpu = gpu if verify_on_device else None
+        self.verify_device_head = verify_on_device == "full"
         self.private_verifier = private_prover.verifier
         self.inner_len = aggregation.private_batch_pi_len(self.N)
         self.circuit = WrapperCircuit(private_prover.circuit.pack, self.private_verifier, self.M, logic="public_batch", verify=verify)
@@ -288,7 +292,7 @@ class PublicBatchProver:
         rows = np.stack([A.proof_public_inputs(p, self.inner_len) for p in private_batch_proofs]) if len(private_batch_proofs) else np.zeros((0, self.inner_len), dtype=np.uint64)
         rows = np.ascontiguousarray(rows, dtype=np.uint64)
         A._call(A._lib().qpgpu_public_batch_preflight, rows.ctypes.data if rows.size else None, rows.shape[0], self.inner_len, self.M)
-        for i, ok in enumerate(self.private_verifier.verify_many(list(private_batch_proofs), gpu=self.verify_gpu)):
+        for i, ok in enumerate(self.private_verifier.verify_many(list(private_batch_proofs), gpu=self.verify_gpu, device_head=self.verify_device_head and self.verify_gpu is not None)):
             if not ok:
                 raise ValueError("private-batch proof %d failed verification against the pinned private-batch verifier" % i)
         padded = list(private_batch_proofs) + [self.dummy_private_batch_proof] * (self.M - len(private_batch_proofs))
