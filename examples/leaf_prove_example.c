@@ -12,7 +12,12 @@
  * printed from /proc/self/maps.
  *
  *   gcc -O2 -I include examples/leaf_prove_example.c -L qp-zk-circuits_amd -lqpgpu -lpthread -Wl,-rpath,$PWD/qp-zk-circuits_amd -o /tmp/leaf_prove_example
- *   /tmp/leaf_prove_example [min_degree_bits=0] [devices=0,0] [workers_per_device=2] [lockstep=4] [steps=2]
+ *   /tmp/leaf_prove_example [--zk] [min_degree_bits=0] [devices=0,0] [workers_per_device=2] [lockstep=4] [steps=2] [hash_hints=0]
+ *
+ * --zk: WormholeProver::new(wormhole_private_batch_circuit_config()) — the reference bench's other target, prover_create_proof_zk
+ * (wormhole/prover/benches/prover.rs:11-29): the circuit is built zero-knowledge (qpgpu_leaf_circuit_build_cfg), the blinding cells
+ * close the cell list and every worker draws them on the device per proof (qpgpu_pool_set_partial_cells_blinded). Two proofs of
+ * the same inputs then differ, so instead of comparing them every proof of the last step goes through the host verifier.
  */
 #define _GNU_SOURCE
 #include <stdio.h>
@@ -43,22 +48,29 @@ static void print_runtime_stack(void) {
 }
 
 int main(int argc, char **argv) {
+    int zk = 0;
+    for (int i = 1; i < argc; i++)
+        if (!strcmp(argv[i], "--zk")) { zk = 1; for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1]; argc--; i--; }
     const unsigned min_degree_bits = argc > 1 ? (unsigned)atoi(argv[1]) : 0;
     int devices[16]; unsigned n_devices = 0;
     { char buf[128]; snprintf(buf, sizeof buf, "%s", argc > 2 ? argv[2] : "0,0"); for (char *t = strtok(buf, ","); t && n_devices < 16; t = strtok(NULL, ",")) devices[n_devices++] = atoi(t); }
     const unsigned workers = argc > 3 ? (unsigned)atoi(argv[3]) : 2, lockstep = argc > 4 ? (unsigned)atoi(argv[4]) : 4, steps = argc > 5 ? (unsigned)atoi(argv[5]) : 2;
     const int hints = argc > 6 ? atoi(argv[6]) : 0;      /* 1: the front-end's hash hints ride along with commit's assignments (qpgpu_leaf.h) */
-    char err[QPGPU_LEAF_ERR_CAP];
+    char err[QPGPU_CONFIG_ERR_CAP];
 
     /* WormholeCircuit::new(config).build_prover(): host only */
     size_t words = 0;
     uint64_t target_map[QPGPU_LT_COUNT], info[QPGPU_LEAF_CIRCUIT_INFO_WORDS];
-    if (qpgpu_leaf_circuit_build(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, 0, NULL, NULL, 0, &words, NULL, NULL, err)) { fprintf(stderr, "build: %s\n", err); return 1; }
-    uint64_t *pack = malloc(words * 8);
-    if (qpgpu_leaf_circuit_build(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, 0, NULL, pack, words, &words, target_map, info, err)) { fprintf(stderr, "build: %s\n", err); return 1; }
+    qpgpu_circuit_config cfg;
+    size_t n_blinding = 0;
+    qpgpu_wormhole_circuit_config(zk ? QPGPU_LEVEL_PRIVATE_BATCH : QPGPU_LEVEL_LEAF, &cfg);
+    if (qpgpu_leaf_circuit_build_cfg(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, 0, NULL, &cfg, NULL, 0, &words, NULL, NULL, NULL, 0, &n_blinding, err)) { fprintf(stderr, "build: %s\n", err); return 1; }
+    uint64_t *pack = malloc(words * 8), *blinding_cells = malloc((n_blinding + 1) * 8);
+    if (qpgpu_leaf_circuit_build_cfg(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, 0, NULL, &cfg, pack, words, &words, target_map, info, blinding_cells, n_blinding, &n_blinding, err)) { fprintf(stderr, "build: %s\n", err); return 1; }
     printf("leaf circuit: 2^%llu rows (%llu before padding: %llu Arithmetic, %llu BaseSum, %llu Poseidon2, %llu Poseidon), %zu pack words\n",
            (unsigned long long)info[0], (unsigned long long)info[1], (unsigned long long)info[7], (unsigned long long)info[8], (unsigned long long)info[9],
            (unsigned long long)info[10], words);
+    if (zk) printf("zero knowledge: %zu blinding cells drawn on the device per proof, %llu routed wires\n", n_blinding, (unsigned long long)cfg.num_routed_wires);
 
     /* the reference bench's input */
     qpgpu_leaf_inputs in;
@@ -81,7 +93,7 @@ int main(int argc, char **argv) {
     size_t count = 0, n_hints = 0;
     if (qpgpu_leaf_commit(&in, target_map, cells, values, QPGPU_LT_COUNT, &count, pis, err)) { fprintf(stderr, "commit: %s\n", err); return 1; }
     if (hints) {    /* the hash chains' states, computed here on the host: stage s1 runs the 61 hash rows side by side and checks them */
-        if (qpgpu_leaf_circuit_hash_hint_cells(min_degree_bits, 0, NULL, cells + count, QPGPU_LEAF_HASH_HINTS, &n_hints, err) ||
+        if (qpgpu_leaf_circuit_hash_hint_cells_cfg(min_degree_bits, 0, NULL, &cfg, cells + count, QPGPU_LEAF_HASH_HINTS, &n_hints, err) ||
             qpgpu_leaf_hash_hints(&in, values + count, QPGPU_LEAF_HASH_HINTS, &n_hints, err)) { fprintf(stderr, "hash hints: %s\n", err); return 1; }
         count += n_hints;
     }
@@ -91,7 +103,14 @@ int main(int argc, char **argv) {
     if (qpgpu_pool_create_multi(devices, n_devices, pack, words, workers, lockstep, 0, &pool)) { fprintf(stderr, "no gfx950 device (the library has no CPU fallback) or pool creation failed\n"); return 2; }
     print_runtime_stack();
     if (qpgpu_pool_serialized(pool)) printf("pool: a queue-intercepting profiler is loaded, the workers take turns on the device\n");
-    if (qpgpu_pool_set_partial_cells(pool, cells, count)) { fprintf(stderr, "set_partial_cells: %s\n", qpgpu_pool_last_error(pool)); return 3; }
+    if (!zk) {
+        if (qpgpu_pool_set_partial_cells(pool, cells, count)) { fprintf(stderr, "set_partial_cells: %s\n", qpgpu_pool_last_error(pool)); return 3; }
+    } else {    /* [logical targets][hash hints][blinding cells]: the last n_blinding cells take no values from the host */
+        uint64_t *all = malloc((count + n_blinding) * 8);
+        memcpy(all, cells, count * 8); memcpy(all + count, blinding_cells, n_blinding * 8);
+        if (qpgpu_pool_set_partial_cells_blinded(pool, all, count + n_blinding, n_blinding)) { fprintf(stderr, "set_partial_cells_blinded: %s\n", qpgpu_pool_last_error(pool)); return 3; }
+        free(all);
+    }
     const size_t cap = qpgpu_pool_proof_size(pool);
     const unsigned per_step = n_devices * workers * lockstep;
     uint8_t *outs = malloc((size_t)per_step * cap);
@@ -104,26 +123,31 @@ int main(int argc, char **argv) {
         for (unsigned i = 0; i < per_step; i++) {
             size_t len = 0;
             if (qpgpu_pool_wait(pool, tickets[i], &len) || len != cap) { fprintf(stderr, "proof %u: %s\n", i, qpgpu_pool_last_error(pool)); return 5; }
-            if (memcmp(outs + (size_t)i * cap, outs, cap)) { fprintf(stderr, "proof %u differs from proof 0 of the same inputs\n", i); return 5; }
+            if (!zk && memcmp(outs + (size_t)i * cap, outs, cap)) { fprintf(stderr, "proof %u differs from proof 0 of the same inputs\n", i); return 5; }
+            if (zk && i && !memcmp(outs + (size_t)i * cap, outs, cap)) { fprintf(stderr, "proof %u equals proof 0: the blinding was not fresh\n", i); return 5; }
         }
     }
     const double dt = now() - t0;
     /* the proof's public inputs are the reference's 21, in its order (wormhole/inputs/src/lib.rs:68-80) */
+    for (unsigned i = 0; i < per_step; i++)
+        if (memcmp(outs + (size_t)i * cap + cap - 8 * QPGPU_LEAF_PUBLIC_INPUTS, pis, 8 * QPGPU_LEAF_PUBLIC_INPUTS)) { fprintf(stderr, "public inputs of proof %u differ\n", i); return 6; }
     if (memcmp(outs + cap - 8 * QPGPU_LEAF_PUBLIC_INPUTS, pis, 8 * QPGPU_LEAF_PUBLIC_INPUTS)) { fprintf(stderr, "public inputs differ\n"); return 6; }
     /* a flipped secret byte: that job alone fails, naming the target; its neighbours are proven */
     {
         qpgpu_leaf_inputs bad = in;
         uint64_t bc[QPGPU_LT_COUNT], bv[MAX_ASSIGNMENTS], bp[QPGPU_LEAF_PUBLIC_INPUTS], t_bad, t_good[2];
         size_t bn = 0, len = 0;
+        uint8_t *nb_outs = zk ? malloc(3 * cap) : outs;     /* (zero knowledge: the last step's proofs are kept for the verifier below) */
         bad.secret[3] ^= 1;
         if (qpgpu_leaf_commit(&bad, target_map, bc, bv, QPGPU_LT_COUNT, &bn, bp, err)) return 7;
         if (hints && qpgpu_leaf_hash_hints(&bad, bv + bn, QPGPU_LEAF_HASH_HINTS, &n_hints, err)) return 7;      /* honest hints of dishonest inputs */
-        if (qpgpu_pool_submit_partial(pool, values, pis, outs, cap, &t_good[0]) || qpgpu_pool_submit_partial(pool, bv, bp, outs + cap, cap, &t_bad) ||
-            qpgpu_pool_submit_partial(pool, values, pis, outs + 2 * cap, cap, &t_good[1])) return 7;
+        if (qpgpu_pool_submit_partial(pool, values, pis, nb_outs, cap, &t_good[0]) || qpgpu_pool_submit_partial(pool, bv, bp, nb_outs + cap, cap, &t_bad) ||
+            qpgpu_pool_submit_partial(pool, values, pis, nb_outs + 2 * cap, cap, &t_good[1])) return 7;
         if (qpgpu_pool_wait(pool, t_good[0], &len) || len != cap) { fprintf(stderr, "neighbour failed: %s\n", qpgpu_pool_last_error(pool)); return 7; }
         if (qpgpu_pool_wait(pool, t_bad, &len) != QPGPU_EUNSAT || !strstr(qpgpu_pool_last_error(pool), "set twice with different values")) { fprintf(stderr, "unsatisfiable job not reported\n"); return 7; }
         printf("unsatisfiable job alone: %s\n", qpgpu_pool_last_error(pool));
-        if (qpgpu_pool_wait(pool, t_good[1], &len) || len != cap || memcmp(outs + 2 * cap, outs, cap)) { fprintf(stderr, "neighbour failed: %s\n", qpgpu_pool_last_error(pool)); return 7; }
+        if (qpgpu_pool_wait(pool, t_good[1], &len) || len != cap || (!zk && memcmp(outs + 2 * cap, outs, cap))) { fprintf(stderr, "neighbour failed: %s\n", qpgpu_pool_last_error(pool)); return 7; }
+        if (zk) free(nb_outs);
     }
     /* the library's host verifier accepts the proof (verifier data = this circuit's constants/sigmas cap) */
     {
@@ -132,6 +156,11 @@ int main(int argc, char **argv) {
         char why[QPGPU_VERIFY_ERR_CAP];
         if (qpgpu_ctx_create(devices[0], &ctx) || qpgpu_circuit_load(ctx, pack, words, &c) || qpgpu_circuit_constants_sigmas_cap(c, cs_cap, 4 << 4)) return 8;
         if (qpgpu_verifier_create(pack, words, cs_cap, 4 << 4, 0, NULL, 0, &v, why) || qpgpu_verifier_verify(v, outs, cap, why)) { fprintf(stderr, "verifier: %s\n", why); return 8; }
+        if (zk) {
+            for (unsigned i = 1; i < per_step; i++)
+                if (qpgpu_verifier_verify(v, outs + (size_t)i * cap, cap, why)) { fprintf(stderr, "verifier, proof %u: %s\n", i, why); return 8; }
+            printf("verified=%u\n", per_step);
+        }
         qpgpu_verifier_free(v); qpgpu_circuit_free(c); qpgpu_ctx_destroy(ctx);
     }
     qpgpu_pool_destroy(pool);          /* drains every device's workers */
@@ -139,6 +168,7 @@ int main(int argc, char **argv) {
     for (size_t i = 0; i < cap; i++) h = (h ^ outs[i]) * 1099511628211ull;
     printf("ok devices=%u workers=%u lockstep=%u steps=%u proofs=%u proof_bytes=%zu fnv1a=%016llx commit+prove %.1f proofs/s%s\n", n_devices, workers, lockstep, steps,
            steps * per_step, cap, (unsigned long long)h, steps ? steps * per_step / dt : 0.0, hints ? " (hash hints)" : "");
+    free(blinding_cells);
     free(pack); free(outs); free(tickets);
     return 0;
 }

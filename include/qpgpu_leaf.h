@@ -32,6 +32,7 @@
 #define QPGPU_LEAF_H
 #include <stddef.h>
 #include <stdint.h>
+#include "qpgpu_wire.h"                      /* qpgpu_circuit_config */
 
 #ifdef __cplusplus
 extern "C" {
@@ -210,6 +211,24 @@ int qpgpu_leaf_check_constraints(const qpgpu_leaf_inputs *in, char *err);
 #define QPGPU_LEAF_FRAGMENT_FAKE_LEAF 4u
 int qpgpu_leaf_circuit_build(unsigned fragment, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, uint64_t *pack_out, size_t pack_cap_words,
                              size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out, char *err);
+/* WormholeCircuit::new(config) / WormholeProver::new(config) (wormhole/circuit/src/circuit.rs:115-152, wormhole/prover/src/lib.rs:137-149):
+ * the same circuit under a caller's CircuitConfig. cfg = NULL is qpgpu_wormhole_circuit_config(QPGPU_LEVEL_LEAF), and
+ * qpgpu_leaf_circuit_build is this entry with cfg = NULL. The config first goes through qpgpu_validate_circuit_config; a refusal is
+ * QPGPU_EINVAL with that function's message (the reference's wording). security_bits and use_base_arithmetic_gate are not modelled by
+ * the native builder: a value other than standard_recursion_config's (100, true) is QPGPU_EINVAL naming the field, as is any other
+ * value the builder cannot lay out (its message names it). The pack's header carries the config; a pack built from
+ * qpgpu_wormhole_circuit_config(level) passes qpgpu_pack_config_is_canonical(.., level).
+ * zero_knowledge = 1 (the reference's second leaf bench target, prover_create_proof_zk, under wormhole_private_batch_circuit_config):
+ * CircuitBuilder::blind's rows follow the circuit's own (upstream plonky2's counts), the prover salts the three
+ * blinded oracles, and blinding_cells_out receives the cells (row * num_wires + wire) that take one fresh random element per proof, in
+ * the builder's order: regular rows (num_wires cells each), then the first row of every Z pair (num_routed_wires cells each). They
+ * are what a caller appends LAST to its cell list — [logical targets][hash hints, if used][blinding cells] — and declares as
+ * n_blinding to qpgpu_generate_witness_partial_batch_blinded_dev / qpgpu_pool_set_partial_cells_blinded, which draw them on the
+ * device. blinding_cells_out = NULL asks for the count; for a config without zero knowledge the count is 0. info_out is as above
+ * (word 0 degree_bits, word 1 the rows before blinding and padding). err: QPGPU_CONFIG_ERR_CAP bytes. */
+int qpgpu_leaf_circuit_build_cfg(unsigned fragment, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg,
+                                 uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out,
+                                 uint64_t *blinding_cells_out, size_t blinding_cap, size_t *blinding_count, char *err);
 /* WormholeProver::commit (wormhole/prover/src/lib.rs:156-163) against such a circuit: qpgpu_leaf_fill_witness followed by
  * qpgpu_leaf_map_targets. cells_out / values_out (room for QPGPU_LT_COUNT) are what qpgpu_generate_witness_partial_dev and
  * qpgpu_pool_submit_partial take. Returns 0 or -1 with the reference's message in err. */
@@ -239,6 +258,11 @@ enum qpgpu_leaf_hash_site {
 /* the cells (row * num_wires + wire) of those 796 values in the FULL leaf circuit built with the same arguments as
  * qpgpu_leaf_circuit_build (cells_out may be NULL to ask for the count) */
 int qpgpu_leaf_circuit_hash_hint_cells(unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, uint64_t *cells_out, size_t cap, size_t *count, char *err);
+/* the same for the circuit qpgpu_leaf_circuit_build_cfg builds from these arguments. Blinding rows are laid after the circuit's own
+ * rows, so the cells of a zero-knowledge circuit are those of its twin without blinding: the call builds both and returns QPGPU_EINVAL
+ * should they ever differ. err: QPGPU_CONFIG_ERR_CAP bytes. */
+int qpgpu_leaf_circuit_hash_hint_cells_cfg(unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg, uint64_t *cells_out,
+                                           size_t cap, size_t *count, char *err);
 /* the 796 values for one set of inputs, computed on the host exactly as the rows' generators would from the same assignments (field
  * arithmetic on the inputs as given: inconsistent inputs give hints that disagree with nothing but the targets the circuit itself
  * would refuse). values_out: room for QPGPU_LEAF_HASH_HINTS. Returns 0, or -1 with a message (inputs qpgpu_leaf_fill_witness refuses).

@@ -105,6 +105,17 @@ extern "C" {
     // deployments that take BOTH prover and verifier data from it; with exported packs of the fork's own circuits these are not used
     pub fn qpgpu_leaf_circuit_build(fragment: u32, min_degree_bits: u32, inner_hasher: i32, p2_layout: *const u64, pack_out: *mut u64, pack_cap_words: usize,
                                     pack_words: *mut usize, target_map_out: *mut u64, info_out: *mut u64, err: *mut c_char) -> i32;
+    // WormholeProver::new(config) (wormhole/prover/src/lib.rs:137-149): the leaf circuit under a caller's CircuitConfig; cfg = null is
+    // wormhole_leaf_circuit_config(). A zero-knowledge config (wormhole_private_batch_circuit_config: the bench's prover_create_proof_zk)
+    // reports CircuitBuilder::blind's random wires in blinding_cells_out: append them LAST to the cell list and pass their count as
+    // n_blinding to qpgpu_pool_set_partial_cells_blinded / qpgpu_generate_witness_partial_batch_blinded_dev. err: 400 bytes.
+    pub fn qpgpu_wormhole_circuit_config(level: i32, out: *mut QpgpuCircuitConfig) -> i32;
+    pub fn qpgpu_validate_circuit_config(cfg: *const QpgpuCircuitConfig, err: *mut c_char) -> i32;
+    pub fn qpgpu_leaf_circuit_build_cfg(fragment: u32, min_degree_bits: u32, inner_hasher: i32, p2_layout: *const u64, cfg: *const QpgpuCircuitConfig,
+                                        pack_out: *mut u64, pack_cap_words: usize, pack_words: *mut usize, target_map_out: *mut u64, info_out: *mut u64,
+                                        blinding_cells_out: *mut u64, blinding_cap: usize, blinding_count: *mut usize, err: *mut c_char) -> i32;
+    pub fn qpgpu_leaf_circuit_hash_hint_cells_cfg(min_degree_bits: u32, inner_hasher: i32, p2_layout: *const u64, cfg: *const QpgpuCircuitConfig,
+                                                  cells_out: *mut u64, cap: usize, count: *mut usize, err: *mut c_char) -> i32;
     // optional: the leaf circuit's hash-chain states as extra assignments (796 cells / values appended to qpgpu_leaf_commit's) — the
     // same witness in 14 dependency levels instead of 120 (one proof 4.6 -> 3.7 ms); a hint that disagrees is QPGPU_EUNSAT
     pub fn qpgpu_leaf_circuit_hash_hint_cells(min_degree_bits: u32, inner_hasher: i32, p2_layout: *const u64, cells_out: *mut u64, cap: usize,
@@ -115,6 +126,17 @@ extern "C" {
                                        pack_words: *mut usize, target_map_out: *mut u64, map_cap: usize, map_count: *mut usize, info_out: *mut u64,
                                        err: *mut c_char) -> i32;
 }
+/// qpgpu_circuit_config (include/qpgpu_wire.h): plonky2's CircuitConfig + FriConfig (ConstantArityBits reduction) as plain data
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct QpgpuCircuitConfig {
+    pub num_wires: u64, pub num_routed_wires: u64, pub num_constants: u64, pub security_bits: u64, pub num_challenges: u64, pub max_quotient_degree_factor: u64,
+    pub use_base_arithmetic_gate: i32, pub zero_knowledge: i32,
+    pub rate_bits: u64, pub cap_height: u64, pub proof_of_work_bits: u64, pub num_query_rounds: u64,
+    pub reduction_arity_bits: u64, pub reduction_final_poly_bits: u64,
+}
+pub const QPGPU_LEVEL_LEAF: i32 = 0;
+pub const QPGPU_LEVEL_PRIVATE_BATCH: i32 = 1;
+pub const QPGPU_LEVEL_PUBLIC_BATCH: i32 = 2;
 #[repr(C)] pub struct QpgpuVerifier { _private: [u8; 0] }
 #[repr(C)] pub struct QpgpuPool { _private: [u8; 0] }
 pub const QPGPU_POOL_HOST_WITNESS: u32 = 1;

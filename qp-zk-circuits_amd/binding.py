@@ -230,6 +230,63 @@ def synth_circuit(degree_bits, num_wires=135, num_routed=80, num_public_inputs=2
     return pack[:got.value].copy() if got.value != words else pack, wires, pis
 
 
+class CircuitConfig(ctypes.Structure):
+    """qpgpu_circuit_config (include/qpgpu_wire.h): plonky2's CircuitConfig with its FriConfig as plain data."""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("num_wires", "num_routed_wires", "num_constants", "security_bits", "num_challenges", "max_quotient_degree_factor")] + \
+               [("use_base_arithmetic_gate", ctypes.c_int), ("zero_knowledge", ctypes.c_int)] + \
+               [(k, ctypes.c_uint64) for k in ("rate_bits", "cap_height", "proof_of_work_bits", "num_query_rounds", "reduction_arity_bits", "reduction_final_poly_bits")]
+
+    def replace(self, **fields):
+        """A copy with the named fields changed."""
+        other = CircuitConfig.from_buffer_copy(self)
+        for k, v in fields.items():
+            if k not in dict(self._fields_):
+                raise TypeError("CircuitConfig has no field %r" % k)
+            setattr(other, k, v)
+        return other
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+CONFIG_LEVELS = {"leaf": 0, "private_batch": 1, "public_batch": 2}
+CONFIG_ERR_CAP = 400
+
+
+def circuit_config(level="leaf", **fields):
+    """qpgpu_wormhole_circuit_config: the canonical config of a level ("leaf" / "public_batch": standard_recursion_config;
+    "private_batch": the zero-knowledge one, 60 routed wires), optionally with fields changed. Host only."""
+    lib = load_library()
+    lib.qpgpu_wormhole_circuit_config.argtypes = [ctypes.c_int, ctypes.c_void_p]
+    c = CircuitConfig()
+    if lib.qpgpu_wormhole_circuit_config(CONFIG_LEVELS[level] if isinstance(level, str) else level, ctypes.byref(c)) != 0:
+        raise ValueError("unknown circuit config level %r" % (level,))
+    return c.replace(**fields) if fields else c
+
+
+def as_circuit_config(config):
+    """None, a level name, a CircuitConfig, or any object / mapping with qpgpu_circuit_config's fields -> CircuitConfig or None."""
+    if config is None or isinstance(config, CircuitConfig):
+        return config
+    if isinstance(config, str):
+        if config not in CONFIG_LEVELS:
+            raise ValueError("unknown circuit config %r (one of %s, or a qpgpu_circuit_config-shaped object)" % (config, ", ".join(sorted(CONFIG_LEVELS))))
+        return circuit_config(config)
+    get = config.__getitem__ if hasattr(config, "__getitem__") else lambda k: getattr(config, k)
+    c = CircuitConfig()
+    for k, _ in CircuitConfig._fields_:
+        setattr(c, k, int(get(k)))
+    return c
+
+
+def validate_circuit_config(config):
+    """qpgpu_validate_circuit_config: None when every Wormhole circuit constructor would take the config, else the reference's message."""
+    lib = load_library()
+    lib.qpgpu_validate_circuit_config.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+    err = ctypes.create_string_buffer(CONFIG_ERR_CAP)
+    return None if lib.qpgpu_validate_circuit_config(ctypes.byref(as_circuit_config(config)), err) == 0 else err.value.decode()
+
+
 def pack_header(pack_words):
     """The fixed header of a circuit pack (csrc/circuit.hpp) as a dict. Host only."""
     names = ["degree_bits", "num_wires", "num_routed_wires", "num_constants", "num_selectors", "num_challenges",
@@ -436,7 +493,9 @@ class Circuit:
         """The same with the LAST n_blinding cells drawn on the device (RandomValueGenerator targets of a zero-knowledge circuit):
         values [batch, count - n_blinding]; seeds: batch x 32 bytes for reproducible tests, None = OS entropy per witness."""
         cl = np.ascontiguousarray(cells, dtype=np.uint64)
-        vl = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, cl.size - n_blinding)
+        vl = np.ascontiguousarray(values, dtype=np.uint64)
+        # (a circuit whose only assignments are its blinding cells: values [batch, 0])
+        vl = vl.reshape(-1, cl.size - n_blinding) if cl.size > n_blinding else vl.reshape(vl.shape[0] if vl.ndim == 2 else 1, 0)
         p = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64)
         batch = vl.shape[0]
         sd = None

@@ -25,8 +25,11 @@
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
+#include <string>
+#include <vector>
 #include "../../include/qpgpu.h"
 #include "../../include/qpgpu_leaf.h"
+#include "../../include/qpgpu_wire.h"
 #include "builder.hpp"
 #include "gadgets.hpp"
 #include "poseidon.hpp"
@@ -282,14 +285,51 @@ void logical_targets(const CircuitTargets &t, Target (&lt)[QPGPU_LT_COUNT]) {
 
 extern "C" {
 
-static int leaf_circuit_build_impl(unsigned fragment, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, uint64_t *pack_out, size_t pack_cap_words,
-                                   size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out, std::vector<uint64_t> *hint_cells, char *err) {
-    auto fail = [&](int code, const std::string &m) { if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "%s", m.c_str()); return code; };
+// WormholeProver::new(config) / WormholeCircuit::new(config) (wormhole/prover/src/lib.rs:137-149, circuit/src/circuit.rs:115-152): the
+// caller's CircuitConfig, or wormhole_leaf_circuit_config() for NULL, checked the way every Wormhole circuit constructor checks it
+// (validate_circuit_config, with its messages) and carried over into the builder's Config. The two fields the builder does not model
+// must hold standard_recursion_config's values: a config that asks for anything else is refused, not built as something it is not.
+static int leaf_builder_config(const qpgpu_circuit_config *user, cb::Config &cfg, char *err, size_t err_cap) {
+    auto fail = [&](const std::string &m) { if (err) std::snprintf(err, err_cap, "%s", m.c_str()); return QPGPU_EINVAL; };
+    qpgpu_circuit_config std_cfg;
+    qpgpu_wormhole_circuit_config(QPGPU_LEVEL_LEAF, &std_cfg);
+    const qpgpu_circuit_config c = user ? *user : std_cfg;
+    char why[QPGPU_CONFIG_ERR_CAP];
+    why[0] = 0;
+    if (qpgpu_validate_circuit_config(&c, why) != 0) return fail(why);
+    if (c.security_bits != std_cfg.security_bits)
+        return fail("leaf_circuit_build: circuit config security_bits (" + std::to_string(c.security_bits) + ") is not modelled by this builder; only " +
+                    std::to_string(std_cfg.security_bits) + " (standard_recursion_config) is accepted");
+    if ((c.use_base_arithmetic_gate != 0) != (std_cfg.use_base_arithmetic_gate != 0))
+        return fail("leaf_circuit_build: circuit config use_base_arithmetic_gate = false is not modelled by this builder; only true (standard_recursion_config) is accepted");
+    const struct { const char *name; uint64_t v; unsigned *to; } f[11] = {
+        {"num_wires", c.num_wires, &cfg.num_wires}, {"num_routed_wires", c.num_routed_wires, &cfg.num_routed_wires}, {"num_constants", c.num_constants, &cfg.num_constants},
+        {"num_challenges", c.num_challenges, &cfg.num_challenges}, {"max_quotient_degree_factor", c.max_quotient_degree_factor, &cfg.max_quotient_degree_factor},
+        {"fri_config.rate_bits", c.rate_bits, &cfg.rate_bits}, {"fri_config.cap_height", c.cap_height, &cfg.cap_height},
+        {"fri_config.proof_of_work_bits", c.proof_of_work_bits, &cfg.proof_of_work_bits}, {"fri_config.num_query_rounds", c.num_query_rounds, &cfg.num_query_rounds},
+        {"fri_config.reduction_strategy arity_bits", c.reduction_arity_bits, &cfg.arity_bits}, {"fri_config.reduction_strategy final_poly_bits", c.reduction_final_poly_bits, &cfg.final_poly_bits}};
+    for (const auto &x : f) {
+        if (x.v > 0xFFFFu) return fail(std::string("leaf_circuit_build: circuit config ") + x.name + " (" + std::to_string(x.v) + ") out of range");
+        *x.to = (unsigned)x.v;
+    }
+    // what the prover's transcript and FRI code take for granted about these three (Builder::validate covers the rest)
+    if (cfg.proof_of_work_bits > 32) return fail("leaf_circuit_build: circuit config fri_config.proof_of_work_bits (" + std::to_string(c.proof_of_work_bits) + ") must be <= 32");
+    if (cfg.arity_bits == 0 || cfg.arity_bits > 4) return fail("leaf_circuit_build: circuit config fri_config.reduction_strategy arity_bits (" + std::to_string(c.reduction_arity_bits) + ") must be 1..4");
+    if (cfg.final_poly_bits > 8) return fail("leaf_circuit_build: circuit config fri_config.reduction_strategy final_poly_bits (" + std::to_string(c.reduction_final_poly_bits) + ") must be <= 8");
+    cfg.zero_knowledge = c.zero_knowledge != 0;
+    return QPGPU_OK;
+}
+
+static int leaf_circuit_build_impl(unsigned fragment, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *user_cfg,
+                                   uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out,
+                                   std::vector<uint64_t> *hint_cells, std::vector<uint64_t> *blinding_cells, char *err, size_t err_cap) {
+    auto fail = [&](int code, const std::string &m) { if (err) std::snprintf(err, err_cap, "%s", m.c_str()); return code; };
     if (err) err[0] = 0;
     if (!pack_words) return fail(QPGPU_EINVAL, "leaf_circuit_build: null argument");
     if (inner_hasher != hasher::POSEIDON && inner_hasher != hasher::POSEIDON2) return fail(QPGPU_EINVAL, "leaf_circuit_build: unknown inner hasher");
     try {
-        cb::Config cfg;                     // wormhole_leaf_circuit_config = standard_recursion_config (common/src/circuit.rs:378-380)
+        cb::Config cfg;                     // NULL: wormhole_leaf_circuit_config = standard_recursion_config (common/src/circuit.rs:378-380)
+        { const int rc = leaf_builder_config(user_cfg, cfg, err, err_cap); if (rc != QPGPU_OK) return rc; }
         cfg.min_degree_bits = min_degree_bits;
         cfg.inner_hasher = inner_hasher;
         if (p2_layout) {
@@ -383,6 +423,12 @@ static int leaf_circuit_build_impl(unsigned fragment, unsigned min_degree_bits, 
             }
             for (Target t : b.hint_targets()) hint_cells->push_back(b.cell_of(t));      // then the running hash of the Merkle walk after every level
         }
+        if (blinding_cells) {
+            // CircuitBuilder::blind's RandomValueGenerator targets, in the builder's order; its rows come after everything the circuit laid
+            *blinding_cells = b.blinding_cells();
+            for (uint64_t c : *blinding_cells)
+                if (c / cfg.num_wires < b.rows_before_padding()) return fail(QPGPU_EINVAL, "leaf_circuit_build: a blinding cell lies inside the circuit's own rows");
+        }
         if (info_out) {
             // the figures the reference's GateProfiler prints (wormhole/circuit/src/profile.rs): gates per fragment, rows per gate type
             const std::map<uint64_t, size_t> gc = b.gate_counts();
@@ -398,25 +444,64 @@ static int leaf_circuit_build_impl(unsigned fragment, unsigned min_degree_bits, 
     return QPGPU_OK;
 }
 
-int qpgpu_leaf_circuit_build(unsigned fragment, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, uint64_t *pack_out, size_t pack_cap_words,
-                             size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out, char *err) {
-    return leaf_circuit_build_impl(fragment, min_degree_bits, inner_hasher, p2_layout, pack_out, pack_cap_words, pack_words, target_map_out, info_out, nullptr, err);
+int qpgpu_leaf_circuit_build_cfg(unsigned fragment, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg,
+                                 uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out,
+                                 uint64_t *blinding_cells_out, size_t blinding_cap, size_t *blinding_count, char *err) {
+    std::vector<uint64_t> blind;
+    const int rc = leaf_circuit_build_impl(fragment, min_degree_bits, inner_hasher, p2_layout, cfg, pack_out, pack_cap_words, pack_words, target_map_out, info_out, nullptr, &blind,
+                                           err, QPGPU_CONFIG_ERR_CAP);
+    if (rc != QPGPU_OK) return rc;
+    if (blinding_count) *blinding_count = blind.size();
+    if (blinding_cells_out) {
+        if (blinding_cap < blind.size()) { if (err) std::snprintf(err, QPGPU_CONFIG_ERR_CAP, "leaf_circuit_build: blinding cell buffer too small"); return QPGPU_EBUFSIZE; }
+        if (!blind.empty()) std::memcpy(blinding_cells_out, blind.data(), blind.size() * 8);
+    }
+    return QPGPU_OK;
 }
 
-int qpgpu_leaf_circuit_hash_hint_cells(unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, uint64_t *cells_out, size_t cap, size_t *count, char *err) {
+// the circuit under wormhole_leaf_circuit_config(): the entry above with cfg = NULL (err: QPGPU_LEAF_ERR_CAP bytes, as ever)
+int qpgpu_leaf_circuit_build(unsigned fragment, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, uint64_t *pack_out, size_t pack_cap_words,
+                             size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out, char *err) {
+    char why[QPGPU_CONFIG_ERR_CAP];
+    const int rc = qpgpu_leaf_circuit_build_cfg(fragment, min_degree_bits, inner_hasher, p2_layout, nullptr, pack_out, pack_cap_words, pack_words, target_map_out, info_out,
+                                                nullptr, 0, nullptr, why);
+    if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "%s", why);
+    return rc;
+}
+
+int qpgpu_leaf_circuit_hash_hint_cells_cfg(unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg, uint64_t *cells_out,
+                                           size_t cap, size_t *count, char *err) {
+    auto fail = [&](int code, const std::string &m) { if (err) std::snprintf(err, QPGPU_CONFIG_ERR_CAP, "%s", m.c_str()); return code; };
     if (err) err[0] = 0;
-    if (!count) { if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "leaf_circuit_hash_hint_cells: null argument"); return QPGPU_EINVAL; }
+    if (!count) return fail(QPGPU_EINVAL, "leaf_circuit_hash_hint_cells: null argument");
     std::vector<uint64_t> cells;
     size_t words = 0;
-    const int rc = leaf_circuit_build_impl(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, inner_hasher, p2_layout, nullptr, 0, &words, nullptr, nullptr, &cells, err);
+    const int rc = leaf_circuit_build_impl(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, inner_hasher, p2_layout, cfg, nullptr, 0, &words, nullptr, nullptr, &cells, nullptr, err, QPGPU_CONFIG_ERR_CAP);
     if (rc != QPGPU_OK) return rc;
     *count = cells.size();
-    if (cells.size() != QPGPU_LEAF_HASH_HINTS) { if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "leaf_circuit_hash_hint_cells: %zu cells where %d are expected", cells.size(), QPGPU_LEAF_HASH_HINTS); return QPGPU_EINVAL; }
+    if (cells.size() != QPGPU_LEAF_HASH_HINTS) return fail(QPGPU_EINVAL, "leaf_circuit_hash_hint_cells: " + std::to_string(cells.size()) + " cells where " + std::to_string(QPGPU_LEAF_HASH_HINTS) + " are expected");
+    if (cfg && cfg->zero_knowledge) {
+        // blind() adds its rows after the circuit's own: the hash rows of the zero-knowledge circuit are where the plain one has them.
+        // Checked on the twin built without blinding, not taken for granted.
+        qpgpu_circuit_config plain_cfg = *cfg;
+        plain_cfg.zero_knowledge = 0;
+        std::vector<uint64_t> plain;
+        const int rc2 = leaf_circuit_build_impl(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, inner_hasher, p2_layout, &plain_cfg, nullptr, 0, &words, nullptr, nullptr, &plain, nullptr, err, QPGPU_CONFIG_ERR_CAP);
+        if (rc2 != QPGPU_OK) return rc2;
+        if (plain != cells) return fail(QPGPU_EINVAL, "leaf_circuit_hash_hint_cells: the blinding rows moved a hash row of the circuit");
+    }
     if (cells_out) {
-        if (cap < cells.size()) { if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "leaf_circuit_hash_hint_cells: cell buffer too small"); return QPGPU_EBUFSIZE; }
+        if (cap < cells.size()) return fail(QPGPU_EBUFSIZE, "leaf_circuit_hash_hint_cells: cell buffer too small");
         std::memcpy(cells_out, cells.data(), cells.size() * 8);
     }
     return QPGPU_OK;
+}
+
+int qpgpu_leaf_circuit_hash_hint_cells(unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, uint64_t *cells_out, size_t cap, size_t *count, char *err) {
+    char why[QPGPU_CONFIG_ERR_CAP];
+    const int rc = qpgpu_leaf_circuit_hash_hint_cells_cfg(min_degree_bits, inner_hasher, p2_layout, nullptr, cells_out, cap, count, why);
+    if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "%s", why);
+    return rc;
 }
 
 // WormholeProver::commit (wormhole/prover/src/lib.rs:156-163): CircuitInputs -> the PartialWitness as (cell, value) pairs of a

@@ -1,6 +1,7 @@
 """Host-side mirror of the reference's leaf prover surface over include/qpgpu_leaf.h (ctypes only; the work is in libqpgpu.so):
 
-    WormholeCircuit::new(config).build_prover()   wormhole/circuit/src/circuit.rs:115-152,210-212   -> LeafCircuit(...)
+    WormholeCircuit::new(config).build_prover()   wormhole/circuit/src/circuit.rs:115-152,210-212   -> LeafCircuit(config=...)
+    WormholeProver::new(config)                   wormhole/prover/src/lib.rs:137-149                -> LeafProver(pkg, gpu, LeafCircuit(config=...))
     WormholeProver::commit(&inputs)               wormhole/prover/src/lib.rs:156-163,187-221        -> LeafCircuit.commit(inputs)
     WormholeProver::prove()                       wormhole/prover/src/lib.rs:171-175                -> LeafProver.prove(inputs)
 
@@ -11,7 +12,7 @@ import ctypes
 
 import numpy as np
 
-from .binding import QpGpuError, load_library
+from .binding import CONFIG_ERR_CAP, QpGpuError, as_circuit_config, load_library
 
 MAX_DEPTH, DIGEST_LEN, LT_COUNT, PUBLIC_INPUTS = 16, 110, 299, 21
 HASH_HINTS = 12 * 61 + 4 * 16          # QPGPU_LEAF_HASH_HINTS: 61 sponge states + the Merkle walk's running hash per level
@@ -56,6 +57,11 @@ def _lib():
         L.qpgpu_leaf_circuit_build.restype = c.c_int
         L.qpgpu_leaf_circuit_build.argtypes = [c.c_uint, c.c_uint, c.c_int, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t),
                                                c.c_void_p, c.c_void_p, c.c_char_p]
+        L.qpgpu_leaf_circuit_build_cfg.restype = c.c_int
+        L.qpgpu_leaf_circuit_build_cfg.argtypes = [c.c_uint, c.c_uint, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t),
+                                                   c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_char_p]
+        L.qpgpu_leaf_circuit_hash_hint_cells_cfg.restype = c.c_int
+        L.qpgpu_leaf_circuit_hash_hint_cells_cfg.argtypes = [c.c_uint, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_char_p]
         L.qpgpu_leaf_commit.restype = c.c_int
         L.qpgpu_leaf_commit.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_void_p, c.c_char_p]
         L.qpgpu_leaf_check_constraints.restype = c.c_int
@@ -130,60 +136,75 @@ def dummy_circuit_inputs():
 
 
 class LeafCircuit:
-    """WormholeCircuit::new(config) -> build_prover(): the circuit pack and the wire cell of every logical target. Host only."""
+    """WormholeCircuit::new(config) -> build_prover(): the circuit pack and the wire cell of every logical target. Host only.
 
-    def __init__(self, fragment=FRAGMENT_FULL, min_degree_bits=0, inner_hasher=0, p2_layout=None):
+    config: None (wormhole_leaf_circuit_config), the name of a canonical config ("leaf"; "private_batch" is the zero-knowledge one the
+    reference's prover_create_proof_zk bench target uses), a binding.CircuitConfig, or any object / mapping with qpgpu_circuit_config's
+    fields. A config the reference's validate_circuit_config refuses raises QpGpuError with its message."""
+
+    def __init__(self, fragment=FRAGMENT_FULL, min_degree_bits=0, inner_hasher=0, p2_layout=None, config=None):
         L = _lib()
-        n = ctypes.c_size_t()
-        err = ctypes.create_string_buffer(160)
+        n = ctypes.c_size_t(); nb = ctypes.c_size_t()
+        err = ctypes.create_string_buffer(CONFIG_ERR_CAP)
         lay = None if p2_layout is None else np.ascontiguousarray(p2_layout, dtype=np.uint64)
         layp = None if lay is None else lay.ctypes.data
-        rc = L.qpgpu_leaf_circuit_build(fragment, min_degree_bits, inner_hasher, layp, None, 0, ctypes.byref(n), None, None, err)
+        self.config = as_circuit_config(config)
+        cfgp = None if self.config is None else ctypes.byref(self.config)
+        rc = L.qpgpu_leaf_circuit_build_cfg(fragment, min_degree_bits, inner_hasher, layp, cfgp, None, 0, ctypes.byref(n), None, None, None, 0, ctypes.byref(nb), err)
         if rc != 0:
             raise QpGpuError(rc, err.value.decode())
         self.pack = np.empty(n.value, dtype=np.uint64)
         self.target_map = np.empty(LT_COUNT, dtype=np.uint64)
+        self.blinding_cells = np.empty(nb.value, dtype=np.uint64)       # CircuitBuilder::blind's random wires, drawn on the device per proof
         info = np.zeros(len(INFO_FIELDS), dtype=np.uint64)
-        rc = L.qpgpu_leaf_circuit_build(fragment, min_degree_bits, inner_hasher, layp, self.pack.ctypes.data, self.pack.size, ctypes.byref(n),
-                                        self.target_map.ctypes.data, info.ctypes.data, err)
+        rc = L.qpgpu_leaf_circuit_build_cfg(fragment, min_degree_bits, inner_hasher, layp, cfgp, self.pack.ctypes.data, self.pack.size, ctypes.byref(n),
+                                            self.target_map.ctypes.data, info.ctypes.data, self.blinding_cells.ctypes.data, self.blinding_cells.size, ctypes.byref(nb), err)
         if rc != 0:
             raise QpGpuError(rc, err.value.decode())
         self.info = {k: int(v) for k, v in zip(INFO_FIELDS, info)}
         self.fragment = fragment
+        self.zero_knowledge = bool(self.pack[14])                       # header word 14 (csrc/circuit.hpp)
         self._build_args = (min_degree_bits, inner_hasher, layp, lay)
         self._hint_cells = None
 
     @property
     def hash_hint_cells(self):
-        """The cells of the 61 Poseidon2 rows' outputs, call sites in tag order (qpgpu_leaf_circuit_hash_hint_cells); full circuit only."""
+        """The cells of the 61 Poseidon2 rows' outputs, call sites in tag order (qpgpu_leaf_circuit_hash_hint_cells_cfg); full circuit only."""
         if self._hint_cells is None:
             if self.fragment != FRAGMENT_FULL:
                 raise ValueError("hash hints exist for the full leaf circuit only")
             cells = np.empty(HASH_HINTS, dtype=np.uint64)
-            n = ctypes.c_size_t(); err = ctypes.create_string_buffer(160)
-            rc = _lib().qpgpu_leaf_circuit_hash_hint_cells(self._build_args[0], self._build_args[1], self._build_args[2], cells.ctypes.data, cells.size, ctypes.byref(n), err)
+            n = ctypes.c_size_t(); err = ctypes.create_string_buffer(CONFIG_ERR_CAP)
+            rc = _lib().qpgpu_leaf_circuit_hash_hint_cells_cfg(self._build_args[0], self._build_args[1], self._build_args[2], None if self.config is None else ctypes.byref(self.config),
+                                                               cells.ctypes.data, cells.size, ctypes.byref(n), err)
             if rc != 0:
                 raise QpGpuError(rc, err.value.decode())
             self._hint_cells = cells[:n.value].copy()
         return self._hint_cells
 
-    def commit(self, inputs, hash_hints=False):
+    def commit(self, inputs, hash_hints=False, device_blinding=False):
         """WormholeProver::commit: (cells, values, public_inputs[21]); raises ValueError with the reference's message. hash_hints=True
         appends the 732 sponge-state elements of the circuit's hash call sites and the Merkle walk's 16 running hashes, computed on the host (qpgpu_leaf_hash_hints): the same witness,
-        with the 61 hash rows generated side by side and checked instead of one after the other."""
+        with the 61 hash rows generated side by side and checked instead of one after the other. device_blinding=True (zero-knowledge
+        circuits): the blinding cells are appended to the cell list WITHOUT values, [logical targets][hash hints][blinding cells] — stage s1
+        draws them on the device (n_blinding = self.blinding_cells.size of Circuit.generate_witness_partial_batch_blinded_dev and
+        ProvingPool.set_partial_cells)."""
         cells = np.empty(LT_COUNT, dtype=np.uint64); values = np.empty(LT_COUNT, dtype=np.uint64); pis = np.empty(PUBLIC_INPUTS, dtype=np.uint64)
         n = ctypes.c_size_t(); err = ctypes.create_string_buffer(160)
         rc = _lib().qpgpu_leaf_commit(ctypes.byref(inputs), self.target_map.ctypes.data, cells.ctypes.data, values.ctypes.data, LT_COUNT,
                                       ctypes.byref(n), pis.ctypes.data, err)
         if rc != 0:
             raise ValueError(err.value.decode())
+        cells, values = [cells[:n.value]], [values[:n.value]]
         if hash_hints:
             hv = np.empty(HASH_HINTS, dtype=np.uint64)
             hn = ctypes.c_size_t()
             if _lib().qpgpu_leaf_hash_hints(ctypes.byref(inputs), hv.ctypes.data, hv.size, ctypes.byref(hn), err) != 0:
                 raise ValueError(err.value.decode())
-            return np.concatenate([cells[:n.value], self.hash_hint_cells]), np.concatenate([values[:n.value], hv[:hn.value]]), self.public_inputs(pis)
-        return cells[:n.value].copy(), values[:n.value].copy(), self.public_inputs(pis)
+            cells.append(self.hash_hint_cells); values.append(hv[:hn.value])
+        if device_blinding:
+            cells.append(self.blinding_cells)
+        return np.concatenate(cells), np.concatenate(values), self.public_inputs(pis)
 
     def public_inputs(self, pis21):
         """The circuit's own public inputs out of the leaf's 21 (a fragment circuit registers only some of them)."""
@@ -197,10 +218,13 @@ class LeafCircuit:
 
 
 class LeafProver:
-    """WormholeProver over a loaded LeafCircuit: commit (host) -> stage s1 on the device -> stages s2..s12."""
+    """WormholeProver over a loaded LeafCircuit: commit (host) -> stage s1 on the device -> stages s2..s12. For a zero-knowledge
+    circuit stage s1 also draws the blinding rows' random wires on the device (fresh OS entropy per proof) and the proof's three
+    blinded oracles are salted. blinding_seed (tests only): an integer that fixes both, the salts through
+    Circuit.set_blinding_seed and the draw through the per-witness key, so that a proof's bytes can be reproduced."""
 
-    def __init__(self, pkg, gpu, circuit, witness_check=False, hash_hints=False):
-        self.pkg, self.gpu, self.circuit, self.hash_hints = pkg, gpu, circuit, hash_hints
+    def __init__(self, pkg, gpu, circuit, witness_check=False, hash_hints=False, blinding_seed=None):
+        self.pkg, self.gpu, self.circuit, self.hash_hints, self.blinding_seed = pkg, gpu, circuit, hash_hints, blinding_seed
         self.circ = pkg.Circuit(gpu, circuit.pack)
         if witness_check:
             self.circ.set_witness_check(True)
@@ -209,16 +233,45 @@ class LeafProver:
         self.d_wires = gpu.alloc(self.shape[0] * self.shape[1] * 8)
 
     def generate_witness(self, inputs):
-        cells, values, pis = self.circuit.commit(inputs, hash_hints=self.hash_hints)
-        self.circ.generate_witness_partial_dev(cells, values, pis, self.d_wires)
+        nb = self.circuit.blinding_cells.size
+        cells, values, pis = self.circuit.commit(inputs, hash_hints=self.hash_hints, device_blinding=nb > 0)
+        if nb == 0:
+            self.circ.generate_witness_partial_dev(cells, values, pis, self.d_wires)
+            return pis
+        key = None if self.blinding_seed is None else int(self.blinding_seed).to_bytes(32, "little")
+        st = self.circ.generate_witness_partial_batch_blinded_dev(cells, values[None], pis[None], self.d_wires, nb, key)
+        if st[0] != 0:
+            raise QpGpuError(st[0], self.gpu.last_error())
         return pis
 
     def prove(self, inputs):
         pis = self.generate_witness(inputs)
+        if self.circuit.zero_knowledge and self.blinding_seed is not None:
+            self.circ.set_blinding_seed(int(self.blinding_seed) & 0xFFFFFFFFFFFFFFFF)
         return self.circ.prove_dev(self.d_wires, pis), pis
 
     def witness(self):
         return self.d_wires.download().reshape(self.shape)
+
+    def pool(self, workers=2, max_batch=4, devices=None):
+        """A ProvingPool over the prover's circuit with its cell list resolved: [logical targets][hash hints, if used][blinding cells],
+        the blinding cells (zero-knowledge circuits) drawn on the device per proof. Jobs go in through submit(); the caller closes it."""
+        x = dummy_circuit_inputs() if self.circuit.fragment == FRAGMENT_FULL else LeafInputs()
+        nb = int(self.circuit.blinding_cells.size)
+        cells = self.circuit.commit(x, hash_hints=self.hash_hints, device_blinding=nb > 0)[0]      # the list is the same for every input
+        pool = self.pkg.ProvingPool(self.circuit.pack, workers=workers, max_batch=max_batch, devices=devices)
+        try:
+            pool.set_partial_cells(cells, n_blinding=nb)
+        except Exception:
+            pool.close()
+            raise
+        return pool
+
+    def submit(self, pool, inputs):
+        """commit(inputs) queued on a pool made by pool(): the ticket for pool.wait(), which raises QpGpuError(-4) for inputs the
+        circuit has no witness for — that ticket alone."""
+        _, values, pis = self.circuit.commit(inputs, hash_hints=self.hash_hints)
+        return pool.submit_partial(values, pis)
 
     def close(self):
         self.d_wires.free(scrub=True)
