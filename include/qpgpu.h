@@ -416,6 +416,46 @@ int qpgpu_synth_circuit(unsigned degree_bits, unsigned num_wires, unsigned num_r
                         uint64_t seed, uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words,
                         uint64_t *wires_out, uint64_t *pis_out);
 
+/* ---- test hooks ---- */
+/*
+ * qpgpu_field_probe: ONE Goldilocks primitive of the device code (qp-zk-circuits_amd/csrc/gl64.hpp, and the NTT's register
+ * transforms) on caller-chosen operands, so that a test can force the carry / borrow branches that pseudo-random data reaches
+ * about once in 2^32 operations. a, b and out are HOST pointers (the hook copies); index i of n reads a[i * wa ..], b[i * wb ..]
+ * and writes out[i * wo ..]; out holds the raw 64-bit results, not canonicalised by the probe. on_device = 1: one thread per
+ * index, 256 per block, consecutive indices in consecutive lanes of a wave. on_device = 0: the same table through the host
+ * versions of the primitives (ctx may be NULL; no GPU needed). QPGPU_EINVAL: bad op / param, a NULL pointer (b only where it is
+ * read), n = 0 or above 2^24, out_words < n * wo, an operand outside what the primitive's signature takes (see below), or an
+ * operation the host path does not have.
+ *
+ *   op                         (wa, wb, wo)   out
+ *   CANON NEG SQR MUL7 INV      (1, 0, 1)     f(a)                         INV: a^(p-2), canonical; CANON canonical
+ *   MUL_EPS                     (1, 0, 1)     a * (2^32 - 1)               a < 2^32
+ *   ADD SUB MUL                 (1, 1, 1)     a op b
+ *   REDUCE128                   (1, 1, 1)     a + b * 2^64                 any (lo, hi)
+ *   REDUCE96                    (1, 1, 1)     a + b * 2^64                 b < 2^32
+ *   ADD_CANONICAL               (1, 1, 1)     a + b                        b < p
+ *   POW                         (1, 1, 1)     a^b, canonical               b is an integer exponent
+ *   MUL_POW2                    (1, 0, 1)     a * 2^param                  param < 192: gl::mul_pow2<param>
+ *   MUL_POW2_DYN                (1, 0, 1)     a * 2^param                  param < 96: the NTT's mul_pow2_dyn, constant shift
+ *   MUL_GROUP                   (N, N, N)     a[k] * b[k], k < N           param = N in {1, 2, 12}: gl::mul_group<N>
+ *   ACC                         (T, T, 1)     sum of a[t] * b[t], t < T    param = T in 1..4096: acc_zero, T x acc_mul, acc_reduce
+ *   E2_ADD E2_SUB E2_MUL        (2, 2, 2)     extension elements as word pairs [a, b] = a + b x, x^2 = 7
+ *   E2_SCALE                    (2, 1, 2)     a * b, b in the base field
+ *   E2_POW                      (2, 1, 2)     a^b, canonical
+ *   E2_INV                      (2, 0, 2)     1 / a, canonical
+ *   DIF_REGS                    (2^K, 0, 2^K) param = K | INV << 8, K in 1..6: dif_regs<K, INV>; device only
+ *   DIF_SPARSE                  (2^K, 0, 2^K) param = K | INV << 8 | LV << 16: dif_sparse<K, INV, LV> for the instances the LDE
+ *                                             kernels use, (K, INV, LV) = (4, 0, 1) and (5, 0, 2); device only
+ */
+enum {
+    QPGPU_FP_CANON = 0, QPGPU_FP_ADD, QPGPU_FP_SUB, QPGPU_FP_NEG, QPGPU_FP_MUL, QPGPU_FP_SQR, QPGPU_FP_REDUCE128, QPGPU_FP_REDUCE96,
+    QPGPU_FP_MUL_EPS, QPGPU_FP_ADD_CANONICAL, QPGPU_FP_MUL7, QPGPU_FP_INV, QPGPU_FP_POW, QPGPU_FP_MUL_POW2, QPGPU_FP_MUL_POW2_DYN,
+    QPGPU_FP_MUL_GROUP, QPGPU_FP_ACC, QPGPU_FP_E2_ADD, QPGPU_FP_E2_SUB, QPGPU_FP_E2_MUL, QPGPU_FP_E2_SCALE, QPGPU_FP_E2_INV,
+    QPGPU_FP_E2_POW, QPGPU_FP_DIF_REGS, QPGPU_FP_DIF_SPARSE, QPGPU_FP_OP_COUNT
+};
+int qpgpu_field_probe(qpgpu_ctx *ctx, unsigned op, unsigned param, const uint64_t *a, const uint64_t *b, size_t n,
+                      uint64_t *out, size_t out_words, int on_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,7 @@ def load_library():
         "qpgpu_fri_proof_size": (c.c_size_t, [c.POINTER(vp), c.c_uint32, vp]),
         "qpgpu_fri_prove": (c.c_int, [vp, c.POINTER(vp), c.c_uint32, vp, c.c_uint32, vp, vp, vp, c.c_size_t,
                                       c.POINTER(c.c_size_t)]),
+        "qpgpu_field_probe": (c.c_int, [vp, c.c_uint, c.c_uint, u64p, u64p, c.c_size_t, u64p, c.c_size_t, c.c_int]),
         "qpgpu_synth_pack_words": (c.c_size_t, [c.c_uint, c.c_uint, c.c_uint]),
         "qpgpu_synth_pack_words_ex": (c.c_size_t, [c.c_uint, c.c_uint, c.c_uint, c.c_uint]),
         "qpgpu_synth_p2_sites": (c.c_size_t, [c.c_uint, c.c_uint, c.c_uint, u64p, c.c_size_t]),
@@ -195,6 +196,52 @@ def poseidon_constants():
     rc = np.empty(360, dtype=np.uint64); fp = np.empty(n, dtype=np.uint64)
     lib.qpgpu_poseidon_constants(rc.ctypes.data, fp.ctypes.data, n)
     return rc, fp
+
+
+# ---- test hook: the field probe (include/qpgpu.h, QPGPU_FP_*) ----
+FP_OPS = ("canon", "add", "sub", "neg", "mul", "sqr", "reduce128", "reduce96", "mul_eps", "add_canonical", "mul7", "inv", "pow",
+          "mul_pow2", "mul_pow2_dyn", "mul_group", "acc", "e2_add", "e2_sub", "e2_mul", "e2_scale", "e2_inv", "e2_pow", "dif_regs",
+          "dif_sparse")
+FP = {name: i for i, name in enumerate(FP_OPS)}
+
+
+def field_probe_shape(op, param=0):
+    """(words of a, words of b, words of out) per index, as the header's table has them."""
+    name = FP_OPS[op]
+    if name in ("mul_group", "acc"):
+        return (param, param, param if name == "mul_group" else 1)
+    if name in ("e2_add", "e2_sub", "e2_mul"):
+        return (2, 2, 2)
+    if name in ("e2_scale", "e2_pow"):
+        return (2, 1, 2)
+    if name == "e2_inv":
+        return (2, 0, 2)
+    if name in ("dif_regs", "dif_sparse"):
+        return (1 << (param & 0xFF), 0, 1 << (param & 0xFF))
+    return (1, 1 if name in ("add", "sub", "mul", "reduce128", "reduce96", "add_canonical", "pow") else 0, 1)
+
+
+def _field_probe(ctx, op, a, b, param, on_device):
+    op = FP[op] if isinstance(op, str) else int(op)
+    wa, wb, wo = field_probe_shape(op, param)
+    a = np.ascontiguousarray(a, dtype=np.uint64).ravel()
+    b = np.ascontiguousarray(b, dtype=np.uint64).ravel() if b is not None else None
+    n = a.size // wa if wa else 0
+    if wa == 0 or a.size != n * wa or (wb and (b is None or b.size != n * wb)):
+        raise ValueError("field_probe: operand lengths do not match the operation's words per index")
+    out = np.empty(n * wo, dtype=np.uint64)
+    rc = load_library().qpgpu_field_probe(ctx, op, param, a.ctypes.data, b.ctypes.data if b is not None else None, n,
+                                          out.ctypes.data, out.size, 1 if on_device else 0)
+    return rc, out
+
+
+def field_probe_host(op, a, b=None, param=0):
+    """qpgpu_field_probe through the host versions of the field primitives: no context, no GPU. op: a name of FP_OPS or its
+    number. Returns the raw result words (flat)."""
+    rc, out = _field_probe(None, op, a, b, param, False)
+    if rc != 0:
+        raise QpGpuError(rc, "qpgpu_field_probe: bad argument or an operation the host path does not have")
+    return out
 
 
 def synth_flags(poseidon=False, base_sum=False, ext_arith=False, recursion=False, hints=False, poseidon2=False, p2_alt_layout=False):
@@ -945,6 +992,12 @@ class QpGpu(_Stage3):
     def to_device(self, arr):
         arr = np.ascontiguousarray(arr)
         return DeviceBuffer(self, arr.nbytes).upload(arr)
+
+    def field_probe(self, op, a, b=None, param=0):
+        """qpgpu_field_probe on the device: one primitive of the device field code, one thread per index (test hook)."""
+        rc, out = _field_probe(self.ctx, op, a, b, param, True)
+        self._check(rc)
+        return out
 
     # ---- stage s2 ----
     def ntt_host(self, data, log_n, inverse=False, coset_shift=0, bitrev=False):

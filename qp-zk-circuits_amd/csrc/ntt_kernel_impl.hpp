@@ -25,7 +25,8 @@ using gl::u64;
 
 namespace {
 
-__device__ __forceinline__ u64 mul_pow2_dyn(u64 x, int s) {
+// GL_HD: the field probe (field_probe.hip) runs the same text on the host too
+GL_HD u64 mul_pow2_dyn(u64 x, int s) {
     // s is a compile-time constant after unrolling; the chain folds to one arm.
     switch (s >> 5) {
         default:

@@ -133,3 +133,52 @@ def test_matrix_build_vs_oracle(gpu, orc):
     assert np.array_equal(cap, cap_want)
     assert np.array_equal(d_dig.download().reshape(-1, 4), dig_want)
     d_cols.free(); d_dig.free()
+
+
+def steered_states(pkg, count=512):
+    """Permutation states whose FIRST-ROUND S-box inputs are chosen words: x = (target - rc[i]) mod p puts `target` into lane i
+    after the first constant layer. Per state a subset of the lanes is steered, to m 2^32 (squares with a zero low half: the
+    reduce128 borrow), to 2^32 - 1 or to p - 1; the other lanes stay random."""
+    rc, _ = pkg.poseidon_constants()
+    rng = np.random.default_rng(4242)
+    states = rng.integers(0, P, (count, 12), dtype=np.uint64)
+    targets = np.zeros((count, 12), dtype=object)
+    for j in range(count):
+        kind = j % 4                                          # 0: m 2^32, 1: 2^32 - 1, 2: p - 1, 3: a mix of the three
+        lanes = range(12) if j % 16 < 4 else rng.choice(12, int(rng.integers(1, 12)), replace=False)
+        for i in lanes:
+            k = kind if kind < 3 else int(rng.integers(0, 3))
+            t = (int(rng.integers(1 << 16, 1 << 32)) << 32) % P if k == 0 else (2**32 - 1 if k == 1 else P - 1)
+            states[j, i] = (t - int(rc[i])) % P
+            targets[j, i] = t
+    # the steering itself, checked here: state + first-round constant is the target
+    for j in range(0, count, 37):
+        for i in range(12):
+            if targets[j, i]:
+                assert (int(states[j, i]) + int(rc[i])) % P == targets[j, i]
+    return states
+
+
+def test_steered_sbox_inputs_on_the_plain_build(gpu, orc, pkg):
+    """512 states: far below the thread count of the throughput build, so the plain S-box products run (gl::mul: the borrow and
+    the carry of reduce128 inline). Against the oracle's permutation."""
+    states = steered_states(pkg)
+    got = gpu.poseidon_permute(states)
+    for s, g in zip(states, got):
+        assert np.array_equal(g, orc.poseidon(s))
+
+
+def test_steered_states_as_poseidon2_preimages(gpu, orc, pkg):
+    """The same words as 12-element preimages of the pad-10 Poseidon2 sponge (qpgpu_poseidon2_hash_pad10_dev) against the
+    oracle's sponge under the pinned parameters."""
+    import ctypes
+    states = steered_states(pkg)
+    got = gpu.poseidon2_hash_pad10(states)
+    params = np.zeros(orc.lib.orc_p2_params_size() // 8, dtype=np.uint64)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    orc.lib.orc_p2_qp_params(vp(params))
+    want = np.empty(4, dtype=np.uint64)
+    for s, g in zip(states, got):
+        row = np.ascontiguousarray(s)
+        orc.lib.orc_p2_hash_pad10(vp(params), vp(row), 12, vp(want))
+        assert np.array_equal(g, want)

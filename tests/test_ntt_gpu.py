@@ -197,3 +197,60 @@ def test_empty_and_bad_arguments(gpu, pkg):
     assert gpu.ntt_host(np.zeros((0, 8), dtype=np.uint64), 3).shape == (0, 8)
     with pytest.raises(pkg.QpGpuError):
         gpu.ntt_host(np.zeros((1, 1 << 24), dtype=np.uint64), 24)  # beyond the supported size: loud error
+
+
+# ---- structured columns: the operands of tests/field_vectors.py through the real transforms ----
+STRUCTURED = ("m_2p32", "pm1_0_1", "all_eps", "pm1_2p32", "edge_cycle")
+
+
+def structured_columns(log_n):
+    """Columns whose butterflies and twiddle products meet the words random data does not: multiples of 2^32 (products with a
+    zero low half), p-1 / 0 / 1 in turn, all 2^32 - 1, p-1 at even and 2^32 at odd indices, and the edge set E of the field
+    probe in a cycle (with its non-canonical words: reduced on load; the oracle gets the reduced column)."""
+    from field_vectors import E
+    n = 1 << log_n
+    rng = np.random.default_rng(900 + log_n)
+    idx = np.arange(n)
+    cols = np.stack([rng.integers(0, 1 << 32, n, dtype=np.uint64) << np.uint64(32),
+                     np.resize(np.array([P - 1, 0, 1], dtype=np.uint64), n),
+                     np.full(n, 2**32 - 1, dtype=np.uint64),
+                     np.where(idx % 2 == 0, np.uint64(P - 1), np.uint64(1 << 32)),
+                     np.resize(np.array(E, dtype=np.uint64), n)])
+    assert cols.shape[0] == len(STRUCTURED) and int(cols[0].max()) < P
+    return cols, np.where(cols >= np.uint64(P), cols - np.uint64(P), cols)
+
+
+def padded_coset_fft(orc, red, log_n, rate_bits):
+    pad = np.zeros((red.shape[0], 1 << (log_n + rate_bits)), dtype=np.uint64)
+    pad[:, : 1 << log_n] = red
+    return np.stack([np.asarray(orc.coset_fft(np.ascontiguousarray(c), log_n + rate_bits, MULT_GEN), dtype=np.uint64) for c in pad])
+
+
+@pytest.mark.parametrize("log_n", [5, 6, 7, 11, 12, 13, 16])
+def test_structured_columns_vs_oracle(gpu, orc, log_n):
+    """Forward, inverse, the coset transform with MULT_GEN and bit-reversed output order, bit for bit."""
+    a, red = structured_columns(log_n)
+    want = orc.fft_batch(red, log_n)
+    assert np.array_equal(gpu.ntt_host(a, log_n), want)
+    assert np.array_equal(gpu.ntt_host(a, log_n, inverse=True), orc.fft_batch(red, log_n, inverse=True))
+    assert np.array_equal(gpu.ntt_host(want, log_n, inverse=True), red)
+    coset = np.stack([np.asarray(orc.coset_fft(c, log_n, MULT_GEN), dtype=np.uint64) for c in red])
+    assert np.array_equal(gpu.ntt_host(a, log_n, coset_shift=MULT_GEN), coset)
+    assert np.array_equal(gpu.ntt_host(a, log_n, bitrev=True), want[:, bitrev_perm(log_n)])
+
+
+@pytest.mark.parametrize("log_n,rate_bits", [(5, 3), (12, 3), (13, 3), (11, 1)])
+def test_structured_columns_lde_vs_oracle(gpu, orc, log_n, rate_bits):
+    """The same columns as coefficients of a zero-padded coset LDE: natural order (the generic passes, dif_sparse in the first
+    one at 2^13) and leaf order, which at 2^11..2^13 coefficients is the column-resident kernel ((11, 1): its smallest shape)."""
+    a, red = structured_columns(log_n)
+    want = padded_coset_fft(orc, red, log_n, rate_bits)
+    d_c = gpu.to_device(a)
+    d_o = gpu.alloc(a.nbytes << rate_bits)
+    gpu.lde_dev(d_c, d_o, log_n, rate_bits, a.shape[0], coset_shift=MULT_GEN)
+    gpu.sync()
+    assert np.array_equal(d_o.download().reshape(a.shape[0], -1), want)
+    gpu.lde_dev(d_c, d_o, log_n, rate_bits, a.shape[0], coset_shift=MULT_GEN, bitrev=True)
+    gpu.sync()
+    assert np.array_equal(d_o.download().reshape(a.shape[0], -1), want[:, bitrev_perm(log_n + rate_bits)])
+    d_c.free(); d_o.free()

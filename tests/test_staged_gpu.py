@@ -132,3 +132,36 @@ def test_stage_api_argument_errors(pkg, gpu):
     with pytest.raises(pkg.QpGpuError):
         pkg.fri_prove(gpu, [o], [([3, 4], [(0, 0, 2)])], ch, [4, 4], cap_height=2)  # reduction deeper than the degree
     o.close()
+
+
+def test_openings_at_edge_points(pkg, gpu):
+    """qpgpu_oracle_eval on structured rows at edge points of the extension field, against Horner in Python integers over
+    F[x]/(x^2 - 7). Rows (coefficients, degree 2^8): random, all p - 1, multiples of 2^32, a delta, the field probe's edge set
+    reduced mod p in a cycle, random again. Points: (p-1, p-1), (0, 1), (1, 0), (2^32, 2^32 - 1), (p - 2^32, 7) and three random
+    ones. Only (1, 0) lies in the base field (an element of the subgroup, off the coset g<w>); evaluation alone is asked for, no
+    FRI at these points, so nothing divides by zero."""
+    from field_vectors import E
+    n = 256
+    rng = np.random.default_rng(808)
+    rows = np.stack([rng.integers(0, P, n, dtype=np.uint64),
+                     np.full(n, P - 1, dtype=np.uint64),
+                     (rng.integers(0, 1 << 32, n, dtype=np.uint64) << np.uint64(32)),
+                     np.zeros(n, dtype=np.uint64),
+                     np.resize(np.array([e % P for e in E], dtype=np.uint64), n),
+                     rng.integers(0, P, n, dtype=np.uint64)])
+    rows[3, 5] = 1
+    assert int(rows.max()) < P
+    points = [(P - 1, P - 1), (0, 1), (1, 0), (2**32, 2**32 - 1), (P - 2**32, 7)]
+    points += [tuple(int(v) for v in rng.integers(0, P, 2, dtype=np.uint64)) for _ in range(3)]
+    o = pkg.PolyOracle(gpu, rows, rate_bits=3, cap_height=4, coeffs=True)
+    try:
+        assert np.array_equal(o.read(), rows)
+        for z in points:
+            got = o.eval(list(z))
+            for j in range(rows.shape[0]):
+                a, b = 0, 0
+                for c in rows[j][::-1]:
+                    a, b = (a * z[0] + 7 * b * z[1] + int(c)) % P, (a * z[1] + b * z[0]) % P
+                assert [int(v) for v in got[j]] == [a, b], (z, j)
+    finally:
+        o.close()
