@@ -12,12 +12,17 @@
  * printed from /proc/self/maps.
  *
  *   gcc -O2 -I include examples/leaf_prove_example.c -L qp-zk-circuits_amd -lqpgpu -lpthread -Wl,-rpath,$PWD/qp-zk-circuits_amd -o /tmp/leaf_prove_example
- *   /tmp/leaf_prove_example [--zk] [min_degree_bits=0] [devices=0,0] [workers_per_device=2] [lockstep=4] [steps=2] [hash_hints=0]
+ *   /tmp/leaf_prove_example [--zk] [min_degree_bits=0] [devices=0,0] [workers_per_device=2] [lockstep=4] [steps=2] [hash_hints=0] [copies=1]
  *
  * --zk: WormholeProver::new(wormhole_private_batch_circuit_config()) — the reference bench's other target, prover_create_proof_zk
  * (wormhole/prover/benches/prover.rs:11-29): the circuit is built zero-knowledge (qpgpu_leaf_circuit_build_cfg), the blinding cells
  * close the cell list and every worker draws them on the device per proof (qpgpu_pool_set_partial_cells_blinded). Two proofs of
  * the same inputs then differ, so instead of comparing them every proof of the last step goes through the host verifier.
+ *
+ * copies > 1: the density-matched leaf (qpgpu_leaf_circuit_build_dense: `copies` statements of the leaf circuit in one trace, the first
+ * of them public — a measurement object, not a protocol object; 41 copies fill 2^13 rows). Every copy is fed the bench's input through
+ * qpgpu_leaf_commit_dense; the unsatisfiable job below has its flipped secret in the LAST copy only. copies = 1 is the plain circuit
+ * word for word.
  */
 #define _GNU_SOURCE
 #include <stdio.h>
@@ -56,20 +61,24 @@ int main(int argc, char **argv) {
     { char buf[128]; snprintf(buf, sizeof buf, "%s", argc > 2 ? argv[2] : "0,0"); for (char *t = strtok(buf, ","); t && n_devices < 16; t = strtok(NULL, ",")) devices[n_devices++] = atoi(t); }
     const unsigned workers = argc > 3 ? (unsigned)atoi(argv[3]) : 2, lockstep = argc > 4 ? (unsigned)atoi(argv[4]) : 4, steps = argc > 5 ? (unsigned)atoi(argv[5]) : 2;
     const int hints = argc > 6 ? atoi(argv[6]) : 0;      /* 1: the front-end's hash hints ride along with commit's assignments (qpgpu_leaf.h) */
+    const int copies_arg = argc > 7 ? atoi(argv[7]) : 1;
+    if (copies_arg < 1 || copies_arg > 4096) { fprintf(stderr, "usage: copies must be a count from 1 to 4096 (41 fill 2^13 rows), got '%s'\n", argv[7]); return 64; }
+    const unsigned copies = (unsigned)copies_arg;
     char err[QPGPU_CONFIG_ERR_CAP];
 
-    /* WormholeCircuit::new(config).build_prover(): host only */
+    /* WormholeCircuit::new(config).build_prover(): host only (one copy through the dense entry is qpgpu_leaf_circuit_build_cfg's circuit) */
     size_t words = 0;
-    uint64_t target_map[QPGPU_LT_COUNT], info[QPGPU_LEAF_CIRCUIT_INFO_WORDS];
+    uint64_t *target_map = malloc(((size_t)copies * QPGPU_LT_COUNT + 1) * 8), info[QPGPU_LEAF_CIRCUIT_INFO_WORDS];
     qpgpu_circuit_config cfg;
     size_t n_blinding = 0;
     qpgpu_wormhole_circuit_config(zk ? QPGPU_LEVEL_PRIVATE_BATCH : QPGPU_LEVEL_LEAF, &cfg);
-    if (qpgpu_leaf_circuit_build_cfg(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, 0, NULL, &cfg, NULL, 0, &words, NULL, NULL, NULL, 0, &n_blinding, err)) { fprintf(stderr, "build: %s\n", err); return 1; }
+    if (qpgpu_leaf_circuit_build_dense(copies, min_degree_bits, 0, NULL, &cfg, NULL, 0, &words, NULL, NULL, NULL, 0, &n_blinding, err)) { fprintf(stderr, "build: %s\n", err); return 1; }
     uint64_t *pack = malloc(words * 8), *blinding_cells = malloc((n_blinding + 1) * 8);
-    if (qpgpu_leaf_circuit_build_cfg(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, 0, NULL, &cfg, pack, words, &words, target_map, info, blinding_cells, n_blinding, &n_blinding, err)) { fprintf(stderr, "build: %s\n", err); return 1; }
+    if (qpgpu_leaf_circuit_build_dense(copies, min_degree_bits, 0, NULL, &cfg, pack, words, &words, target_map, info, blinding_cells, n_blinding, &n_blinding, err)) { fprintf(stderr, "build: %s\n", err); return 1; }
     printf("leaf circuit: 2^%llu rows (%llu before padding: %llu Arithmetic, %llu BaseSum, %llu Poseidon2, %llu Poseidon), %zu pack words\n",
            (unsigned long long)info[0], (unsigned long long)info[1], (unsigned long long)info[7], (unsigned long long)info[8], (unsigned long long)info[9],
            (unsigned long long)info[10], words);
+    if (copies > 1) printf("dense: %u copies of the leaf circuit's statement, copy 0 public (a measurement object)\n", copies);
     if (zk) printf("zero knowledge: %zu blinding cells drawn on the device per proof, %llu routed wires\n", n_blinding, (unsigned long long)cfg.num_routed_wires);
 
     /* the reference bench's input */
@@ -88,14 +97,17 @@ int main(int argc, char **argv) {
     if (qpgpu_leaf_check_constraints(&in, err)) { fprintf(stderr, "inputs: %s\n", err); return 1; }
 
     /* WormholeProver::commit */
-    enum { MAX_ASSIGNMENTS = QPGPU_LT_COUNT + QPGPU_LEAF_HASH_HINTS };
-    uint64_t cells[MAX_ASSIGNMENTS], values[MAX_ASSIGNMENTS], pis[QPGPU_LEAF_PUBLIC_INPUTS];
+    const size_t max_assignments = (size_t)copies * (QPGPU_LT_COUNT + QPGPU_LEAF_HASH_HINTS), all_hints = (size_t)copies * QPGPU_LEAF_HASH_HINTS;
+    uint64_t *cells = malloc(max_assignments * 8), *values = malloc(max_assignments * 8), pis[QPGPU_LEAF_PUBLIC_INPUTS];
+    const qpgpu_leaf_inputs **ins = malloc(copies * sizeof *ins);
     size_t count = 0, n_hints = 0;
-    if (qpgpu_leaf_commit(&in, target_map, cells, values, QPGPU_LT_COUNT, &count, pis, err)) { fprintf(stderr, "commit: %s\n", err); return 1; }
-    if (hints) {    /* the hash chains' states, computed here on the host: stage s1 runs the 61 hash rows side by side and checks them */
-        if (qpgpu_leaf_circuit_hash_hint_cells_cfg(min_degree_bits, 0, NULL, &cfg, cells + count, QPGPU_LEAF_HASH_HINTS, &n_hints, err) ||
-            qpgpu_leaf_hash_hints(&in, values + count, QPGPU_LEAF_HASH_HINTS, &n_hints, err)) { fprintf(stderr, "hash hints: %s\n", err); return 1; }
-        count += n_hints;
+    for (unsigned c = 0; c < copies; c++) ins[c] = &in;
+    if (qpgpu_leaf_commit_dense(ins, copies, target_map, cells, values, (size_t)copies * QPGPU_LT_COUNT, &count, pis, err)) { fprintf(stderr, "commit: %s\n", err); return 1; }
+    if (hints) {    /* the hash chains' states, computed here on the host: stage s1 runs the 61 hash rows of every copy side by side and checks them */
+        if (qpgpu_leaf_circuit_hash_hint_cells_dense(copies, min_degree_bits, 0, NULL, &cfg, cells + count, all_hints, &n_hints, err)) { fprintf(stderr, "hash hints: %s\n", err); return 1; }
+        for (unsigned c = 0; c < copies; c++)     /* [hash hints, copy-major] */
+            if (qpgpu_leaf_hash_hints(ins[c], values + count + (size_t)c * QPGPU_LEAF_HASH_HINTS, QPGPU_LEAF_HASH_HINTS, &n_hints, err)) { fprintf(stderr, "hash hints: %s\n", err); return 1; }
+        count += all_hints;
     }
 
     /* one pool over all the devices; every worker resolves the cell list once */
@@ -132,15 +144,17 @@ int main(int argc, char **argv) {
     for (unsigned i = 0; i < per_step; i++)
         if (memcmp(outs + (size_t)i * cap + cap - 8 * QPGPU_LEAF_PUBLIC_INPUTS, pis, 8 * QPGPU_LEAF_PUBLIC_INPUTS)) { fprintf(stderr, "public inputs of proof %u differ\n", i); return 6; }
     if (memcmp(outs + cap - 8 * QPGPU_LEAF_PUBLIC_INPUTS, pis, 8 * QPGPU_LEAF_PUBLIC_INPUTS)) { fprintf(stderr, "public inputs differ\n"); return 6; }
-    /* a flipped secret byte: that job alone fails, naming the target; its neighbours are proven */
+    /* a flipped secret byte (in the last copy alone): that job alone fails, naming the target; its neighbours are proven */
     {
         qpgpu_leaf_inputs bad = in;
-        uint64_t bc[QPGPU_LT_COUNT], bv[MAX_ASSIGNMENTS], bp[QPGPU_LEAF_PUBLIC_INPUTS], t_bad, t_good[2];
+        uint64_t *bc = malloc(max_assignments * 8), *bv = malloc(max_assignments * 8), bp[QPGPU_LEAF_PUBLIC_INPUTS], t_bad, t_good[2];
         size_t bn = 0, len = 0;
         uint8_t *nb_outs = zk ? malloc(3 * cap) : outs;     /* (zero knowledge: the last step's proofs are kept for the verifier below) */
         bad.secret[3] ^= 1;
-        if (qpgpu_leaf_commit(&bad, target_map, bc, bv, QPGPU_LT_COUNT, &bn, bp, err)) return 7;
-        if (hints && qpgpu_leaf_hash_hints(&bad, bv + bn, QPGPU_LEAF_HASH_HINTS, &n_hints, err)) return 7;      /* honest hints of dishonest inputs */
+        ins[copies - 1] = &bad;
+        if (qpgpu_leaf_commit_dense(ins, copies, target_map, bc, bv, (size_t)copies * QPGPU_LT_COUNT, &bn, bp, err)) return 7;
+        for (unsigned c = 0; hints && c < copies; c++)      /* honest hints of dishonest inputs */
+            if (qpgpu_leaf_hash_hints(ins[c], bv + bn + (size_t)c * QPGPU_LEAF_HASH_HINTS, QPGPU_LEAF_HASH_HINTS, &n_hints, err)) return 7;
         if (qpgpu_pool_submit_partial(pool, values, pis, nb_outs, cap, &t_good[0]) || qpgpu_pool_submit_partial(pool, bv, bp, nb_outs + cap, cap, &t_bad) ||
             qpgpu_pool_submit_partial(pool, values, pis, nb_outs + 2 * cap, cap, &t_good[1])) return 7;
         if (qpgpu_pool_wait(pool, t_good[0], &len) || len != cap) { fprintf(stderr, "neighbour failed: %s\n", qpgpu_pool_last_error(pool)); return 7; }
@@ -148,6 +162,7 @@ int main(int argc, char **argv) {
         printf("unsatisfiable job alone: %s\n", qpgpu_pool_last_error(pool));
         if (qpgpu_pool_wait(pool, t_good[1], &len) || len != cap || (!zk && memcmp(outs + 2 * cap, outs, cap))) { fprintf(stderr, "neighbour failed: %s\n", qpgpu_pool_last_error(pool)); return 7; }
         if (zk) free(nb_outs);
+        free(bc); free(bv);
     }
     /* the library's host verifier accepts the proof (verifier data = this circuit's constants/sigmas cap) */
     {
@@ -168,7 +183,7 @@ int main(int argc, char **argv) {
     for (size_t i = 0; i < cap; i++) h = (h ^ outs[i]) * 1099511628211ull;
     printf("ok devices=%u workers=%u lockstep=%u steps=%u proofs=%u proof_bytes=%zu fnv1a=%016llx commit+prove %.1f proofs/s%s\n", n_devices, workers, lockstep, steps,
            steps * per_step, cap, (unsigned long long)h, steps ? steps * per_step / dt : 0.0, hints ? " (hash hints)" : "");
-    free(blinding_cells);
+    free(blinding_cells); free(target_map); free(cells); free(values); free(ins);
     free(pack); free(outs); free(tickets);
     return 0;
 }

@@ -235,6 +235,29 @@ int qpgpu_leaf_circuit_build_cfg(unsigned fragment, unsigned min_degree_bits, in
 int qpgpu_leaf_commit(const qpgpu_leaf_inputs *in, const uint64_t *target_map, uint64_t *cells_out, uint64_t *values_out, size_t cap,
                       size_t *count, uint64_t public_inputs_out[QPGPU_LEAF_PUBLIC_INPUTS], char *err);
 
+/* ---- the density-matched leaf: a MEASUREMENT AND TEST OBJECT, not a protocol object and not the fork's circuit ------------------------
+ * The restated leaf circuit has about 205 live gate rows; the reference's degree-13 circuit is far denser (common/src/circuit.rs:464-467,
+ * wormhole/circuit/src/profile.rs:121), and the row order of the fork's builder cannot be read offline. To load the device path at the
+ * reference's row occupancy, qpgpu_leaf_circuit_build_dense lays `copies` independent statements of the leaf circuit into one trace:
+ *   copy 0 is WormholeCircuit::new exactly as qpgpu_leaf_circuit_build_cfg builds it; its 21 targets are the circuit's public inputs;
+ *   copies 1 .. copies-1 are the same five fragments plus connect_shared_targets, statement for statement, over fresh virtual targets,
+ *     laid after copy 0 in copy-major order; their 21 would-be public-input targets are ordinary private targets;
+ *   the public-input hash, the PublicInputGate, the constant rows, padding and blind() are laid once for the whole circuit.
+ * So the proof states copy 0's public inputs and proves that all `copies` statements hold, of which one is public. Nothing in the protocol
+ * asks for such a proof; it is what a live 2^13-row leaf costs on this backend (41 copies fit 2^13 rows: 8 039 of 8 192).
+ * Every argument has the meaning it has in qpgpu_leaf_circuit_build_cfg. target_map_out: copies * QPGPU_LT_COUNT words, copy-major.
+ * info_out: as there (word 1: the rows before blinding and padding; the per-fragment gate counts are copy 0's). copies = 1 returns the
+ * pack, target map and blinding cells of qpgpu_leaf_circuit_build_cfg(QPGPU_LEAF_FRAGMENT_FULL, ..) word for word. QPGPU_EINVAL, naming the
+ * argument: copies = 0, or so many copies that the rows exceed what the builder lays out (2^20). err: QPGPU_CONFIG_ERR_CAP bytes. */
+int qpgpu_leaf_circuit_build_dense(unsigned copies, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg,
+                                   uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out,
+                                   uint64_t *blinding_cells_out, size_t blinding_cap, size_t *blinding_count, char *err);
+/* qpgpu_leaf_commit for every copy: ins[c] feeds copy c (pointers may repeat), target_map is qpgpu_leaf_circuit_build_dense's, cells_out /
+ * values_out have room for copies * QPGPU_LT_COUNT pairs (cap), copy-major; the public inputs are those of ins[0]. Returns 0, or -1 with
+ * the reference's message prefixed with the copy ("copy 2: ...") in err (QPGPU_LEAF_ERR_CAP bytes). */
+int qpgpu_leaf_commit_dense(const qpgpu_leaf_inputs *const *ins, unsigned copies, const uint64_t *target_map, uint64_t *cells_out, uint64_t *values_out, size_t cap,
+                            size_t *count, uint64_t public_inputs_out[QPGPU_LEAF_PUBLIC_INPUTS], char *err);
+
 /* ---- hash hints: the serial part of the leaf witness, handed in by the front-end ------------------------------------------------
  * The leaf circuit hashes in chains: 61 Poseidon2 gate rows at 8 call sites, every Merkle level waiting for the one below it. On the
  * device a row's generator is one dependent chain (about 19 us with its launch), 45 levels deep; a host core computes the same
@@ -269,6 +292,11 @@ int qpgpu_leaf_circuit_hash_hint_cells_cfg(unsigned min_degree_bits, int inner_h
  * The values are as sensitive as qpgpu_leaf_commit's (the first sponge states are functions of the spend secret alone): wipe them after
  * the submit, as the library wipes its own copies. */
 int qpgpu_leaf_hash_hints(const qpgpu_leaf_inputs *in, uint64_t *values_out, size_t cap, size_t *count, char *err);
+/* the hash-hint cells of the dense circuit qpgpu_leaf_circuit_build_dense builds from these arguments: copies * QPGPU_LEAF_HASH_HINTS cells,
+ * copy-major; the values are qpgpu_leaf_hash_hints of each copy's inputs, one after the other. The cell list of a dense circuit stays
+ * [logical targets, copy-major][hash hints, copy-major][blinding cells]. */
+int qpgpu_leaf_circuit_hash_hint_cells_dense(unsigned copies, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg,
+                                             uint64_t *cells_out, size_t cap, size_t *count, char *err);
 
 #ifdef __cplusplus
 }

@@ -116,6 +116,17 @@ extern "C" {
                                         blinding_cells_out: *mut u64, blinding_cap: usize, blinding_count: *mut usize, err: *mut c_char) -> i32;
     pub fn qpgpu_leaf_circuit_hash_hint_cells_cfg(min_degree_bits: u32, inner_hasher: i32, p2_layout: *const u64, cfg: *const QpgpuCircuitConfig,
                                                   cells_out: *mut u64, cap: usize, count: *mut usize, err: *mut c_char) -> i32;
+    // the density-matched leaf (a measurement and test object, NOT a protocol object): `copies` independent statements of the leaf circuit in
+    // one trace, copy 0's 21 targets public, the others private; target_map_out has copies * QPGPU_LT_COUNT words, copy-major. copies = 1
+    // is qpgpu_leaf_circuit_build_cfg's full circuit word for word.
+    pub fn qpgpu_leaf_circuit_build_dense(copies: u32, min_degree_bits: u32, inner_hasher: i32, p2_layout: *const u64, cfg: *const QpgpuCircuitConfig,
+                                          pack_out: *mut u64, pack_cap_words: usize, pack_words: *mut usize, target_map_out: *mut u64, info_out: *mut u64,
+                                          blinding_cells_out: *mut u64, blinding_cap: usize, blinding_count: *mut usize, err: *mut c_char) -> i32;
+    pub fn qpgpu_leaf_circuit_hash_hint_cells_dense(copies: u32, min_degree_bits: u32, inner_hasher: i32, p2_layout: *const u64, cfg: *const QpgpuCircuitConfig,
+                                                    cells_out: *mut u64, cap: usize, count: *mut usize, err: *mut c_char) -> i32;
+    // ins: `copies` pointers to qpgpu_leaf_inputs (they may repeat); the public inputs are those of ins[0]
+    pub fn qpgpu_leaf_commit_dense(ins: *const *const c_void, copies: u32, target_map: *const u64, cells_out: *mut u64, values_out: *mut u64, cap: usize,
+                                   count: *mut usize, public_inputs_out: *mut u64, err: *mut c_char) -> i32;
     // optional: the leaf circuit's hash-chain states as extra assignments (796 cells / values appended to qpgpu_leaf_commit's) — the
     // same witness in 14 dependency levels instead of 120 (one proof 4.6 -> 3.7 ms); a hint that disagrees is QPGPU_EUNSAT
     pub fn qpgpu_leaf_circuit_hash_hint_cells(min_degree_bits: u32, inner_hasher: i32, p2_layout: *const u64, cells_out: *mut u64, cap: usize,

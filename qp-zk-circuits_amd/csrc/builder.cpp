@@ -489,6 +489,7 @@ std::string Builder::build(CircuitPack &pack) {
     if (built_) return "build: already built";
     const uint32_t NW = cfg_.num_wires, R = cfg_.num_routed_wires;
     // CircuitBuilder::build: hash the public inputs and route the hash into a PublicInputGate
+    hash_tag_ = -1;      // the public-input hash is no call site of the circuit's own: its Poseidon2 rows (if any) carry no tag
     const HashOutTarget pih = hash_n_to_hash_no_pad(public_inputs_);
     const uint32_t pi_row = add_gate(spec_index(GATE_PUBLIC_INPUT, 0, 0, 0));
     for (uint32_t i = 0; i < 4; i++) connect(pih.elements[i], wire(pi_row, i));

@@ -47,6 +47,7 @@ struct qpgpu_circuit {
     gl::u64 *d_check = nullptr;          // [max_batch][2]: first bad row, permutation flag
     gl::u64 blinding_seed = 0;           // test hook: proof b of the next batch uses the key derived from blinding_seed + b
     WitnessPlan *wplan = nullptr;    // stage s1, built on first use (witness_plan.cpp)
+    int witness_wide_rows = -1;      // QPGPU_WITNESS_WIDE_ROWS as read at load: 0 never, 1 always, -1 (unset) the measured threshold (witness.hpp)
 
     template <class T> int alloc(T **p, size_t count, bool secret = false) {
         void *v = nullptr;

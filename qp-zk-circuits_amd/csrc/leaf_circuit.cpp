@@ -70,13 +70,17 @@ std::vector<Target> salt_constants(Builder &b, const char *salt) {
 }
 
 // ---- target creation, in CircuitTargets::new's order ----
-ZkMerkleProofTargets zk_merkle_proof_targets(Builder &b) {
+// `pub`: the 21 public-input targets are registered (the circuit's statement: copy 0); otherwise they are ordinary private
+// targets created at the same places (copies 1.. of the dense circuit, qpgpu_leaf_circuit_build_dense)
+Target input_target(Builder &b, bool pub) { return pub ? b.add_virtual_public_input() : b.add_virtual_target(); }
+HashOutTarget input_hash(Builder &b, bool pub) { return pub ? b.add_virtual_hash_public_input() : b.add_virtual_hash(); }
+ZkMerkleProofTargets zk_merkle_proof_targets(Builder &b, bool pub) {
     ZkMerkleProofTargets t;
     // ZkLeafTargets::new: the four public inputs first ("registered first for consistent ordering")
-    t.leaf.asset_id = b.add_virtual_public_input();
-    t.leaf.output_amount_1 = b.add_virtual_public_input();
-    t.leaf.output_amount_2 = b.add_virtual_public_input();
-    t.leaf.volume_fee_bps = b.add_virtual_public_input();
+    t.leaf.asset_id = input_target(b, pub);
+    t.leaf.output_amount_1 = input_target(b, pub);
+    t.leaf.output_amount_2 = input_target(b, pub);
+    t.leaf.volume_fee_bps = input_target(b, pub);
     for (auto &e : t.leaf.to_account) e = b.add_virtual_target();
     for (auto &e : t.leaf.transfer_count) e = b.add_virtual_target();
     t.leaf.input_amount = b.add_virtual_target();
@@ -87,20 +91,20 @@ ZkMerkleProofTargets zk_merkle_proof_targets(Builder &b) {
     for (auto &p : t.positions) p = b.add_virtual_target();
     return t;
 }
-CircuitTargets circuit_targets(Builder &b) {
+CircuitTargets circuit_targets(Builder &b, bool pub = true) {
     CircuitTargets t;
-    t.zk_merkle_proof = zk_merkle_proof_targets(b);       // first, so that asset_id is public input 0
-    t.nullifier.hash = b.add_virtual_hash_public_input();
+    t.zk_merkle_proof = zk_merkle_proof_targets(b, pub);  // first, so that asset_id is public input 0
+    t.nullifier.hash = input_hash(b, pub);
     t.nullifier.secret = b.add_virtual_hash();
     for (auto &e : t.nullifier.transfer_count) e = b.add_virtual_target();
     t.unspendable_account.account_id = b.add_virtual_hash();
     t.unspendable_account.secret = b.add_virtual_hash();
-    for (auto &e : t.exit_accounts.exit_account_1) e = b.add_virtual_public_input();
-    for (auto &e : t.exit_accounts.exit_account_2) e = b.add_virtual_public_input();
-    t.block_header.block_hash = b.add_virtual_hash_public_input();
+    for (auto &e : t.exit_accounts.exit_account_1) e = input_target(b, pub);
+    for (auto &e : t.exit_accounts.exit_account_2) e = input_target(b, pub);
+    t.block_header.block_hash = input_hash(b, pub);
     HeaderTargets &h = t.block_header.header;
     for (auto &e : h.parent_hash) e = b.add_virtual_target();
-    h.block_number = b.add_virtual_public_input();
+    h.block_number = input_target(b, pub);
     for (auto &e : h.state_root) e = b.add_virtual_target();
     for (auto &e : h.extrinsics_root) e = b.add_virtual_target();
     for (auto &e : h.zk_tree_root) e = b.add_virtual_target();
@@ -250,7 +254,7 @@ void connect_shared_targets(const CircuitTargets &t, Builder &b) {
     }
 }
 
-void logical_targets(const CircuitTargets &t, Target (&lt)[QPGPU_LT_COUNT]) {
+void logical_targets(const CircuitTargets &t, Target *lt) {
     auto set4 = [&](unsigned base, const Target *e) { for (int i = 0; i < 4; i++) lt[base + i] = e[i]; };
     set4(QPGPU_LT_NULLIFIER_HASH, t.nullifier.hash.elements);
     set4(QPGPU_LT_NULLIFIER_SECRET, t.nullifier.secret.elements);
@@ -320,12 +324,22 @@ static int leaf_builder_config(const qpgpu_circuit_config *user, cb::Config &cfg
     return QPGPU_OK;
 }
 
+// copies > 1 (qpgpu_leaf_circuit_build_dense): the full circuit's five fragments and connect_shared_targets laid `copies` times over
+// fresh targets, copy-major; copy 0's 21 targets are the public inputs, the other copies' are private. target_map_out then has
+// copies * QPGPU_LT_COUNT words, hint_cells copies * QPGPU_LEAF_HASH_HINTS.
+constexpr int HASH_TAG_STRIDE = 32;                 // hash call-site tags of copy c: c * HASH_TAG_STRIDE + qpgpu_leaf_hash_site
+constexpr unsigned MAX_BUILDER_ROWS = 1u << 20;     // Builder::build's limit, which is below the prover's (circuit.cpp: 2^24)
 static int leaf_circuit_build_impl(unsigned fragment, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *user_cfg,
                                    uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out,
-                                   std::vector<uint64_t> *hint_cells, std::vector<uint64_t> *blinding_cells, char *err, size_t err_cap) {
+                                   std::vector<uint64_t> *hint_cells, std::vector<uint64_t> *blinding_cells, char *err, size_t err_cap, unsigned copies = 1) {
     auto fail = [&](int code, const std::string &m) { if (err) std::snprintf(err, err_cap, "%s", m.c_str()); return code; };
     if (err) err[0] = 0;
     if (!pack_words) return fail(QPGPU_EINVAL, "leaf_circuit_build: null argument");
+    if (copies == 0) return fail(QPGPU_EINVAL, "leaf_circuit_build_dense: copies must be at least 1");
+    if (copies > 1 && fragment != QPGPU_LEAF_FRAGMENT_FULL) return fail(QPGPU_EINVAL, "leaf_circuit_build_dense: fragment must be the full circuit (QPGPU_LEAF_FRAGMENT_FULL)");
+    // every copy lays its QPGPU_LEAF_HASH_ROWS hash rows at least: refused before anything is built
+    if ((uint64_t)copies * QPGPU_LEAF_HASH_ROWS > MAX_BUILDER_ROWS)
+        return fail(QPGPU_EINVAL, "leaf_circuit_build_dense: copies (" + std::to_string(copies) + ") gives more than 2^20 rows, the largest circuit the builder lays out");
     if (inner_hasher != hasher::POSEIDON && inner_hasher != hasher::POSEIDON2) return fail(QPGPU_EINVAL, "leaf_circuit_build: unknown inner hasher");
     try {
         cb::Config cfg;                     // NULL: wormhole_leaf_circuit_config = standard_recursion_config (common/src/circuit.rs:378-380)
@@ -340,8 +354,8 @@ static int leaf_circuit_build_impl(unsigned fragment, unsigned min_degree_bits, 
             l.first_round_wires = (uint32_t)p2_layout[7]; l.constraint_order = (uint32_t)p2_layout[8]; l.end_wire = (uint32_t)p2_layout[9];
         }
         Builder b(cfg);
-        Target lt[QPGPU_LT_COUNT];
-        for (Target &t : lt) t = cb::NO_TARGET;
+        std::vector<Target> lt_all((size_t)copies * QPGPU_LT_COUNT, cb::NO_TARGET);
+        Target *lt = lt_all.data();                        // copy 0's (the only copy of every entry but the dense one)
         size_t gates_after_targets = 0, g1 = 0, g2 = 0, g3 = 0, g4 = 0;
         if (fragment == QPGPU_LEAF_FRAGMENT_FULL) {
             const CircuitTargets targets = circuit_targets(b);
@@ -356,6 +370,19 @@ static int leaf_circuit_build_impl(unsigned fragment, unsigned min_degree_bits, 
             connect_shared_targets(targets, b);
             g4 = b.num_gates();
             logical_targets(targets, lt);
+            // the dense circuit's further statements: the same calls in the same order over fresh private targets. Constants are the
+            // builder's (one target per value), so the constant rows, like the public-input hash, are laid once by build().
+            for (unsigned c = 1; c < copies; c++) {
+                b.set_hash_tag_base((int)c * HASH_TAG_STRIDE);
+                const CircuitTargets tc = circuit_targets(b, false);
+                unspendable_account_circuit(tc.unspendable_account, b);
+                zk_merkle_proof_circuit(tc.zk_merkle_proof, b);
+                b.range_check(tc.block_header.header.block_number, 32);
+                connect_shared_targets(tc, b);
+                logical_targets(tc, lt + (size_t)c * QPGPU_LT_COUNT);
+                if (b.num_gates() > MAX_BUILDER_ROWS)
+                    return fail(QPGPU_EINVAL, "leaf_circuit_build_dense: copies (" + std::to_string(copies) + ") gives more than 2^20 rows, the largest circuit the builder lays out");
+            }
         } else if (fragment == QPGPU_LEAF_FRAGMENT_BLOCK_HEADER) {
             // BlockHeaderTargets::new + BlockHeader::circuit (block_header/mod.rs:122-126): the unconditional binding, as the
             // reference's fragment tests compose it (wormhole/tests/src/circuit/block_header_tests.rs:8-19)
@@ -402,7 +429,7 @@ static int leaf_circuit_build_impl(unsigned fragment, unsigned min_degree_bits, 
         } else return fail(QPGPU_EINVAL, "leaf_circuit_build: unknown fragment");
         CircuitPack pack;
         const std::string why = b.build(pack);
-        if (!why.empty()) return fail(QPGPU_EINVAL, "leaf_circuit_build: " + why);
+        if (!why.empty()) return fail(QPGPU_EINVAL, copies > 1 ? "leaf_circuit_build_dense: copies (" + std::to_string(copies) + "): " + why : "leaf_circuit_build: " + why);
         const std::vector<uint64_t> words = pack.serialize();
         *pack_words = words.size();
         if (pack_out) {
@@ -410,18 +437,22 @@ static int leaf_circuit_build_impl(unsigned fragment, unsigned min_degree_bits, 
             std::memcpy(pack_out, words.data(), words.size() * 8);
         }
         if (target_map_out) {
-            for (unsigned i = 0; i < QPGPU_LT_COUNT; i++) { const u64 c = lt[i] == cb::NO_TARGET ? cb::NO_CELL : b.cell_of(lt[i]); target_map_out[i] = c == cb::NO_CELL ? UINT64_MAX : c; }
+            for (size_t i = 0; i < lt_all.size(); i++) { const u64 c = lt_all[i] == cb::NO_TARGET ? cb::NO_CELL : b.cell_of(lt_all[i]); target_map_out[i] = c == cb::NO_CELL ? UINT64_MAX : c; }
         }
         if (hint_cells) {
             // the 12 output cells of every Poseidon2 row, hash call sites in the order of their tags, rows of a site in sponge order
             std::vector<std::pair<int, uint32_t>> rows = b.poseidon2_rows();
             std::stable_sort(rows.begin(), rows.end(), [](const std::pair<int, uint32_t> &x, const std::pair<int, uint32_t> &y) { return x.first < y.first; });
             hint_cells->clear();
-            for (const auto &r : rows) {
-                if (r.first < 0) continue;                     // (the public-input hash of a Poseidon2-hashed circuit: not a call site of the leaf)
-                for (uint32_t i = 0; i < 12; i++) hint_cells->push_back(b.poseidon2_output_cell(r.second, i));
+            const std::vector<Target> &walk = b.hint_targets();
+            if (walk.size() != (size_t)copies * 4 * MAX_DEPTH) return fail(QPGPU_EINVAL, "leaf_circuit_build: unexpected number of Merkle-walk hint targets");
+            size_t k = 0;
+            while (k < rows.size() && rows[k].first < 0) k++;   // (the public-input hash of a Poseidon2-hashed circuit: not a call site of the leaf)
+            for (unsigned c = 0; c < copies; c++) {             // copy-major: a copy's sponge states (its tags sort together), then its walk
+                for (; k < rows.size() && rows[k].first < (int)(c + 1) * HASH_TAG_STRIDE; k++)
+                    for (uint32_t i = 0; i < 12; i++) hint_cells->push_back(b.poseidon2_output_cell(rows[k].second, i));
+                for (size_t i = 0; i < 4 * MAX_DEPTH; i++) hint_cells->push_back(b.cell_of(walk[(size_t)c * 4 * MAX_DEPTH + i]));   // the running hash after every level
             }
-            for (Target t : b.hint_targets()) hint_cells->push_back(b.cell_of(t));      // then the running hash of the Merkle walk after every level
         }
         if (blinding_cells) {
             // CircuitBuilder::blind's RandomValueGenerator targets, in the builder's order; its rows come after everything the circuit laid
@@ -444,12 +475,12 @@ static int leaf_circuit_build_impl(unsigned fragment, unsigned min_degree_bits, 
     return QPGPU_OK;
 }
 
-int qpgpu_leaf_circuit_build_cfg(unsigned fragment, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg,
-                                 uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out,
-                                 uint64_t *blinding_cells_out, size_t blinding_cap, size_t *blinding_count, char *err) {
+static int leaf_circuit_build_blinded(unsigned copies, unsigned fragment, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg,
+                                      uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out,
+                                      uint64_t *blinding_cells_out, size_t blinding_cap, size_t *blinding_count, char *err) {
     std::vector<uint64_t> blind;
     const int rc = leaf_circuit_build_impl(fragment, min_degree_bits, inner_hasher, p2_layout, cfg, pack_out, pack_cap_words, pack_words, target_map_out, info_out, nullptr, &blind,
-                                           err, QPGPU_CONFIG_ERR_CAP);
+                                           err, QPGPU_CONFIG_ERR_CAP, copies);
     if (rc != QPGPU_OK) return rc;
     if (blinding_count) *blinding_count = blind.size();
     if (blinding_cells_out) {
@@ -457,6 +488,22 @@ int qpgpu_leaf_circuit_build_cfg(unsigned fragment, unsigned min_degree_bits, in
         if (!blind.empty()) std::memcpy(blinding_cells_out, blind.data(), blind.size() * 8);
     }
     return QPGPU_OK;
+}
+
+int qpgpu_leaf_circuit_build_cfg(unsigned fragment, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg,
+                                 uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out,
+                                 uint64_t *blinding_cells_out, size_t blinding_cap, size_t *blinding_count, char *err) {
+    return leaf_circuit_build_blinded(1, fragment, min_degree_bits, inner_hasher, p2_layout, cfg, pack_out, pack_cap_words, pack_words, target_map_out, info_out,
+                                      blinding_cells_out, blinding_cap, blinding_count, err);
+}
+
+// The density-matched leaf: `copies` independent statements of the leaf circuit in one trace, the first of them public (see the header:
+// a measurement and test object, not a protocol object). copies = 1 is qpgpu_leaf_circuit_build_cfg's full circuit word for word.
+int qpgpu_leaf_circuit_build_dense(unsigned copies, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg,
+                                   uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, uint64_t *info_out,
+                                   uint64_t *blinding_cells_out, size_t blinding_cap, size_t *blinding_count, char *err) {
+    return leaf_circuit_build_blinded(copies, QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, inner_hasher, p2_layout, cfg, pack_out, pack_cap_words, pack_words, target_map_out, info_out,
+                                      blinding_cells_out, blinding_cap, blinding_count, err);
 }
 
 // the circuit under wormhole_leaf_circuit_config(): the entry above with cfg = NULL (err: QPGPU_LEAF_ERR_CAP bytes, as ever)
@@ -469,24 +516,25 @@ int qpgpu_leaf_circuit_build(unsigned fragment, unsigned min_degree_bits, int in
     return rc;
 }
 
-int qpgpu_leaf_circuit_hash_hint_cells_cfg(unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg, uint64_t *cells_out,
-                                           size_t cap, size_t *count, char *err) {
+int qpgpu_leaf_circuit_hash_hint_cells_dense(unsigned copies, unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg,
+                                             uint64_t *cells_out, size_t cap, size_t *count, char *err) {
     auto fail = [&](int code, const std::string &m) { if (err) std::snprintf(err, QPGPU_CONFIG_ERR_CAP, "%s", m.c_str()); return code; };
     if (err) err[0] = 0;
     if (!count) return fail(QPGPU_EINVAL, "leaf_circuit_hash_hint_cells: null argument");
     std::vector<uint64_t> cells;
     size_t words = 0;
-    const int rc = leaf_circuit_build_impl(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, inner_hasher, p2_layout, cfg, nullptr, 0, &words, nullptr, nullptr, &cells, nullptr, err, QPGPU_CONFIG_ERR_CAP);
+    const int rc = leaf_circuit_build_impl(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, inner_hasher, p2_layout, cfg, nullptr, 0, &words, nullptr, nullptr, &cells, nullptr, err, QPGPU_CONFIG_ERR_CAP, copies);
     if (rc != QPGPU_OK) return rc;
     *count = cells.size();
-    if (cells.size() != QPGPU_LEAF_HASH_HINTS) return fail(QPGPU_EINVAL, "leaf_circuit_hash_hint_cells: " + std::to_string(cells.size()) + " cells where " + std::to_string(QPGPU_LEAF_HASH_HINTS) + " are expected");
+    if (cells.size() != (size_t)copies * QPGPU_LEAF_HASH_HINTS)
+        return fail(QPGPU_EINVAL, "leaf_circuit_hash_hint_cells: " + std::to_string(cells.size()) + " cells where " + std::to_string((size_t)copies * QPGPU_LEAF_HASH_HINTS) + " are expected");
     if (cfg && cfg->zero_knowledge) {
         // blind() adds its rows after the circuit's own: the hash rows of the zero-knowledge circuit are where the plain one has them.
         // Checked on the twin built without blinding, not taken for granted.
         qpgpu_circuit_config plain_cfg = *cfg;
         plain_cfg.zero_knowledge = 0;
         std::vector<uint64_t> plain;
-        const int rc2 = leaf_circuit_build_impl(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, inner_hasher, p2_layout, &plain_cfg, nullptr, 0, &words, nullptr, nullptr, &plain, nullptr, err, QPGPU_CONFIG_ERR_CAP);
+        const int rc2 = leaf_circuit_build_impl(QPGPU_LEAF_FRAGMENT_FULL, min_degree_bits, inner_hasher, p2_layout, &plain_cfg, nullptr, 0, &words, nullptr, nullptr, &plain, nullptr, err, QPGPU_CONFIG_ERR_CAP, copies);
         if (rc2 != QPGPU_OK) return rc2;
         if (plain != cells) return fail(QPGPU_EINVAL, "leaf_circuit_hash_hint_cells: the blinding rows moved a hash row of the circuit");
     }
@@ -495,6 +543,11 @@ int qpgpu_leaf_circuit_hash_hint_cells_cfg(unsigned min_degree_bits, int inner_h
         std::memcpy(cells_out, cells.data(), cells.size() * 8);
     }
     return QPGPU_OK;
+}
+
+int qpgpu_leaf_circuit_hash_hint_cells_cfg(unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, const qpgpu_circuit_config *cfg, uint64_t *cells_out,
+                                           size_t cap, size_t *count, char *err) {
+    return qpgpu_leaf_circuit_hash_hint_cells_dense(1, min_degree_bits, inner_hasher, p2_layout, cfg, cells_out, cap, count, err);
 }
 
 int qpgpu_leaf_circuit_hash_hint_cells(unsigned min_degree_bits, int inner_hasher, const uint64_t *p2_layout, uint64_t *cells_out, size_t cap, size_t *count, char *err) {
@@ -519,6 +572,32 @@ int qpgpu_leaf_commit(const qpgpu_leaf_inputs *in, const uint64_t *target_map, u
     const int rc = qpgpu_leaf_fill_witness(in, public_inputs_out, targets, values, QPGPU_LT_COUNT, &n, err);
     if (rc == 0) *count = qpgpu_leaf_map_targets(targets, values, n, target_map, QPGPU_LT_COUNT, cells_out, values_out);
     std::memset(values, 0, sizeof values);          // the assignments carry the spend secret
+    return rc;
+}
+
+// qpgpu_leaf_commit for every copy of a dense circuit: ins[c] fills copy c's targets (target_map + c * QPGPU_LT_COUNT); the circuit's
+// public inputs are copy 0's. A refusal carries the reference's message behind the index of the copy whose inputs it refuses.
+int qpgpu_leaf_commit_dense(const qpgpu_leaf_inputs *const *ins, unsigned copies, const uint64_t *target_map, uint64_t *cells_out, uint64_t *values_out, size_t cap,
+                            size_t *count, uint64_t public_inputs_out[QPGPU_LEAF_PUBLIC_INPUTS], char *err) {
+    if (err) err[0] = 0;
+    if (!ins || !copies || !target_map || !cells_out || !values_out || !count || cap / QPGPU_LT_COUNT < copies) {
+        if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "leaf_commit_dense: null argument, copies = 0 or room for fewer than copies * %d assignments", QPGPU_LT_COUNT);
+        return -1;
+    }
+    size_t total = 0;
+    int rc = 0;
+    for (unsigned c = 0; c < copies && rc == 0; c++) {
+        uint64_t pis[QPGPU_LEAF_PUBLIC_INPUTS];
+        char why[QPGPU_LEAF_ERR_CAP];
+        size_t n = 0;
+        why[0] = 0;
+        if (!ins[c]) { rc = -1; std::snprintf(why, sizeof why, "null inputs"); }
+        else rc = qpgpu_leaf_commit(ins[c], target_map + (size_t)c * QPGPU_LT_COUNT, cells_out + total, values_out + total, cap - total, &n, c == 0 && public_inputs_out ? public_inputs_out : pis, why);
+        if (rc != 0 && err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "copy %u: %s", c, why);
+        total += n;
+    }
+    if (rc != 0) { std::memset(values_out, 0, total * 8); total = 0; }     // (what earlier copies left there carries their spend secrets)
+    *count = total;
     return rc;
 }
 

@@ -240,6 +240,9 @@ int qpgpu_circuit_load_batch(qpgpu_ctx *ctx, const uint64_t *pack_words, size_t 
         if (e != hipSuccess) return fail(ctx->hip_fail(e, "hipHostMalloc(stage)"));
         c->stage.h = (u64 *)hp;
     }
+    // routing knob of stage s1, read here like the staging hook above: which generator form the hash-gate rows of a wide dependency
+    // level get (witness_plan.cpp: generate_batch). 0: always the lane-cooperative one, 1: always a thread per row, unset: by width.
+    if (const char *e = getenv("QPGPU_WITNESS_WIDE_ROWS")) if (*e == '0' || *e == '1') c->witness_wide_rows = *e - '0';
     // everything a batch reads back ends up in its proofs: their total size bounds any single read
     if ((rc = ctx->reserve_read_back((size_t)B * qpgpu_proof_size(c) + (1u << 16))) != QPGPU_OK) return fail(rc);
     CK(plan_transforms(c));

@@ -34,6 +34,12 @@ hipError_t wk_run_combined(const WitnessArgs &a, uint32_t first, uint32_t n_gene
 // between them (level l = insts[level_start[l] .. level_start[l+1]), its PoseidonGate rows from level_poseidon[l] on).
 constexpr uint32_t WITNESS_RUN_GENERIC_CAP = 1024, WITNESS_RUN_POSEIDON_CAP = 32;   // widest level a run takes
 hipError_t wk_run_levels(const WitnessArgs &a, const uint32_t *d_level_start, const uint32_t *d_level_poseidon, uint32_t l0, uint32_t l1, uint32_t batch, hipStream_t st);
+// One level whose hash-gate rows are many (rows x batch at or above WITNESS_WIDE_ROWS_DEFAULT, or QPGPU_WITNESS_WIDE_ROWS=1): the
+// ordinary instances as in wk_run_combined, the hash-gate rows a thread each instead of 16 lanes each. Same wires, bit for bit.
+// The default is the smallest rows x batch from which the thread-per-row form was not slower on any measured shape, rounded up to a
+// power of two (profiles/leaf_dense.txt); 0 = never by default, the kernel stays behind the knob.
+constexpr uint64_t WITNESS_WIDE_ROWS_DEFAULT = 0;
+hipError_t wk_run_wide(const WitnessArgs &a, uint32_t first, uint32_t n_generic, uint32_t n_hash, uint32_t batch, hipStream_t st);
 hipError_t wk_run_poseidon(const WitnessArgs &a, uint32_t first, uint32_t count, uint32_t batch, hipStream_t st);   // PoseidonGate instances, 16 lanes each
 hipError_t wk_fill_copies(const WitnessArgs &a, uint32_t batch, hipStream_t st);
 // wires[b * batch_stride + idx[i]] = vals[b * val_stride + i] (flat cell index = column * n + row); out[i] = wires[idx[i]]

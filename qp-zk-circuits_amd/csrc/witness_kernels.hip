@@ -354,6 +354,138 @@ __global__ void __launch_bounds__(256) witness_combined_kernel(WitnessArgs a, u3
     witness_poseidon_body(a, first + n_generic, n_poseidon, (blockIdx.x - generic_blocks) * blockDim.x + threadIdx.x, rc_lds);
 }
 
+// ---- wide levels: one thread per hash-gate row -------------------------------------------------------------------------------
+// The lane-cooperative generators above spend 16 lanes on a row: about three times the vector work of a thread that keeps the
+// whole state, for a fifth of its latency. That is the right trade while a level holds a handful of rows. A level of thousands
+// (a dense circuit whose hash rows are hinted, a Merkle-path level of a wrapper, times the lockstep batch) fills the machine
+// either way, and then the work a row costs is what the level costs. Here a thread runs a whole row with the state in
+// registers: the same inputs (routed wires through src_of, the others in place), the same wires written, every one of them
+// canonical — S-box inputs and outputs are field elements, so the two forms agree bit for bit on every input.
+__device__ __forceinline__ void witness_poseidon2_row_wide(const WitnessArgs &a, u64 *wires, const u32 row, const u64 *p2w) {
+    const P2GateLayout &lay = a.p2_layout;
+    const u64 *rc_ext = p2w, *rc_int = p2w + 96, *diag = p2w + 118;
+    const u64 n = a.n;
+    const u32 R = a.num_routed;
+    auto RD = [&](u32 col) -> u64 { return col < R ? wires[a.src_of[(u64)row * R + col]] : wires[(u64)col * n + row]; };
+    auto WR = [&](u32 col, u64 v) { wires[(u64)col * n + row] = gl::canon(v); };
+    u64 s[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = RD(lay.w_input + i);
+    if (lay.has_swap()) {
+        const u64 swap = gl::canon(RD(lay.w_swap));
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const u64 delta = swap ? gl::canon(gl::sub(s[i + 4], s[i])) : 0;
+            WR(lay.w_delta + i, delta);
+            s[i] = gl::add(s[i], delta); s[i + 4] = gl::sub(s[i + 4], delta);
+        }
+    }
+    poseidon2::ext_layer_qp(s);                     // the gate's parameter set is qp-poseidon-core's: block circ(2, 3, 1, 1), no multiplications
+    u32 wf = lay.w_full0;
+#pragma unroll 1
+    for (int r = 0; r < 4; r++) {
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = gl::canon(gl::add(s[i], rc_ext[r * 12 + i]));
+        if (r || lay.first_round_wires) {
+#pragma unroll
+            for (int i = 0; i < 12; i++) WR(wf + i, s[i]);
+            wf += 12;
+        }
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = poseidon::sbox7(s[i]);
+        poseidon2::ext_layer_qp(s);
+    }
+#pragma unroll 1
+    for (int r = 0; r < 22; r++) {
+        s[0] = gl::canon(gl::add(s[0], rc_int[r]));
+        WR(lay.w_partial + r, s[0]);
+        s[0] = poseidon::sbox7(s[0]);
+        u64 sum = s[0];
+#pragma unroll
+        for (int i = 1; i < 12; i++) sum = gl::add(sum, s[i]);
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = gl::add(gl::mul(s[i], diag[i]), sum);
+    }
+#pragma unroll 1
+    for (int r = 0; r < 4; r++) {
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = gl::canon(gl::add(s[i], rc_ext[(4 + r) * 12 + i]));
+#pragma unroll
+        for (int i = 0; i < 12; i++) WR(lay.w_full1 + 12 * r + i, s[i]);
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = poseidon::sbox7(s[i]);
+        poseidon2::ext_layer_qp(s);
+    }
+#pragma unroll
+    for (int i = 0; i < 12; i++) WR(lay.w_output + i, s[i]);
+}
+// PoseidonGate row, the textbook schedule the cooperative body runs (its partial-round S-box inputs are the gate's wires)
+__device__ __forceinline__ void witness_poseidon_row_wide(const WitnessArgs &a, u64 *wires, const u32 row, const u64 *rc) {
+    const u64 n = a.n;
+    const u32 R = a.num_routed;
+    auto RD = [&](u32 col) -> u64 { return col < R ? wires[a.src_of[(u64)row * R + col]] : wires[(u64)col * n + row]; };
+    auto WR = [&](u32 col, u64 v) { wires[(u64)col * n + row] = gl::canon(v); };
+    u64 s[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = RD(i);
+    const u64 swap = gl::canon(RD(24));
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const u64 delta = swap ? gl::canon(gl::sub(s[i + 4], s[i])) : 0;
+        WR(25 + i, delta);
+        s[i] = gl::add(s[i], delta); s[i + 4] = gl::sub(s[i + 4], delta);
+    }
+#pragma unroll 1
+    for (int r = 0; r < poseidon::HALF_FULL; r++) {
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = gl::canon(gl::add(s[i], rc[r * 12 + i]));
+        if (r) {
+#pragma unroll
+            for (int i = 0; i < 12; i++) WR(29 + 12 * (r - 1) + i, s[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = poseidon::sbox7(s[i]);
+        poseidon::mds_layer(s);
+    }
+#pragma unroll 1
+    for (int r = 0; r < poseidon::PARTIAL; r++) {
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = gl::add(s[i], rc[(poseidon::HALF_FULL + r) * 12 + i]);
+        s[0] = gl::canon(s[0]);
+        WR(65 + r, s[0]);
+        s[0] = poseidon::sbox7(s[0]);
+        poseidon::mds_layer(s);
+    }
+#pragma unroll 1
+    for (int r = 0; r < poseidon::HALF_FULL; r++) {
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = gl::canon(gl::add(s[i], rc[(poseidon::HALF_FULL + poseidon::PARTIAL + r) * 12 + i]));
+#pragma unroll
+        for (int i = 0; i < 12; i++) WR(87 + 12 * r + i, s[i]);
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = poseidon::sbox7(s[i]);
+        poseidon::mds_layer(s);
+    }
+#pragma unroll
+    for (int i = 0; i < 12; i++) WR(12 + i, s[i]);
+}
+// One wide dependency level in one launch, arranged as witness_combined_kernel arranges a narrow one: the first `generic_blocks`
+// workgroups run the level's ordinary instances, the rest its hash-gate rows — here a thread per (row, witness), the witness in
+// blockIdx.y. A thread past the last row stages constants with its workgroup and stores nothing. Workgroups of one wave: a
+// level of a few thousand rows then spreads over every compute unit.
+constexpr u32 WITNESS_WIDE_BLOCK = 64;
+__global__ void __launch_bounds__(WITNESS_WIDE_BLOCK) witness_hash_rows_wide_kernel(WitnessArgs a, u32 first, u32 n_generic, u32 n_hash, u32 generic_blocks) {
+    __shared__ u64 rc_lds[WITNESS_CONST_WORDS];
+    if (blockIdx.x < generic_blocks) { witness_level_body(a, first, n_generic, blockIdx.x * blockDim.x + threadIdx.x); return; }
+    stage_round_constants(a, rc_lds);
+    const u32 t = (blockIdx.x - generic_blocks) * blockDim.x + threadIdx.x;
+    if (t >= n_hash) return;
+    const WitnessInst in = a.insts[first + n_generic + t];
+    u64 *wires = a.wires + (u64)blockIdx.y * a.batch_stride;
+    if (a.gates[in.gate].type == 14) witness_poseidon2_row_wide(a, wires, in.row, rc_lds + poseidon::ROUNDS * 12);
+    else witness_poseidon_row_wide(a, wires, in.row, rc_lds);
+}
+
 // A run of narrow dependency levels in one launch. A level of a deep circuit is a handful of generator instances (a serial
 // chain of reducing / arithmetic operations, a Merkle path's hashes), and one launch per level costs 20-40 us of launch and
 // drain latency against a few us of work. Here one workgroup per witness walks levels [l0, l1): waves 0-7 take the level's
@@ -460,6 +592,12 @@ hipError_t wk_run_combined(const WitnessArgs &a, uint32_t first, uint32_t n_gene
     if (n_generic == 0) return wk_run_poseidon(a, first, n_poseidon, batch, st);
     const uint32_t gb = (n_generic + 255) / 256, pb = (n_poseidon + 15) / 16;
     hipLaunchKernelGGL(witness_combined_kernel, dim3(gb + pb, batch), dim3(256), 0, st, a, first, n_generic, n_poseidon, gb);
+    return hipGetLastError();
+}
+hipError_t wk_run_wide(const WitnessArgs &a, uint32_t first, uint32_t n_generic, uint32_t n_hash, uint32_t batch, hipStream_t st) {
+    if (batch == 0 || (n_generic == 0 && n_hash == 0)) return hipSuccess;
+    const uint32_t gb = (n_generic + WITNESS_WIDE_BLOCK - 1) / WITNESS_WIDE_BLOCK, hb = (n_hash + WITNESS_WIDE_BLOCK - 1) / WITNESS_WIDE_BLOCK;
+    hipLaunchKernelGGL(witness_hash_rows_wide_kernel, dim3(gb + hb, batch), dim3(WITNESS_WIDE_BLOCK), 0, st, a, first, n_generic, n_hash, gb);
     return hipGetLastError();
 }
 hipError_t wk_run_levels(const WitnessArgs &a, const uint32_t *d_level_start, const uint32_t *d_level_poseidon, uint32_t l0, uint32_t l1, uint32_t batch, hipStream_t st) {

@@ -695,7 +695,11 @@ int generate_batch(qpgpu_circuit *c, uint64_t *d_wires, uint32_t batch, const ui
         if (seg.second - seg.first > 1) { QP_HIP(ctx, wk_run_levels(a, plan.d_level_start, plan.d_level_poseidon, seg.first, seg.second, batch, ctx->stream)); continue; }
         const size_t l = seg.first;
         const uint32_t lo = plan.level_start[l], mid = plan.level_poseidon[l], hi = plan.level_start[l + 1];
-        if (combined) QP_HIP(ctx, wk_run_combined(a, lo, mid - lo, hi - mid, batch, ctx->stream));
+        // a level whose hash-gate rows, over the whole batch, are many: a thread per row (QPGPU_WITNESS_WIDE_ROWS=0 never, =1 always,
+        // unset: from WITNESS_WIDE_ROWS_DEFAULT rows x batch on; runs of narrow levels above keep their kernel either way)
+        const bool wide = hi > mid && (c->witness_wide_rows == 1 || (c->witness_wide_rows < 0 && WITNESS_WIDE_ROWS_DEFAULT != 0 && (u64)(hi - mid) * batch >= WITNESS_WIDE_ROWS_DEFAULT));
+        if (wide) QP_HIP(ctx, wk_run_wide(a, lo, mid - lo, hi - mid, batch, ctx->stream));
+        else if (combined) QP_HIP(ctx, wk_run_combined(a, lo, mid - lo, hi - mid, batch, ctx->stream));
         else {
             QP_HIP(ctx, wk_run_level(a, lo, mid - lo, batch, ctx->stream));
             QP_HIP(ctx, wk_run_poseidon(a, mid, hi - mid, batch, ctx->stream));

@@ -14,6 +14,8 @@ import numpy as np
 
 from .binding import CONFIG_ERR_CAP, QpGpuError, as_circuit_config, load_library
 
+EINVAL = -1                            # QPGPU_EINVAL (include/qpgpu.h)
+
 MAX_DEPTH, DIGEST_LEN, LT_COUNT, PUBLIC_INPUTS = 16, 110, 299, 21
 HASH_HINTS = 12 * 61 + 4 * 16          # QPGPU_LEAF_HASH_HINTS: 61 sponge states + the Merkle walk's running hash per level
 FRAGMENT_FULL, FRAGMENT_BLOCK_HEADER, FRAGMENT_UNSPENDABLE_ACCOUNT, FRAGMENT_NULLIFIER, FRAGMENT_FAKE_LEAF = 0, 1, 2, 3, 4
@@ -62,6 +64,13 @@ def _lib():
                                                    c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_char_p]
         L.qpgpu_leaf_circuit_hash_hint_cells_cfg.restype = c.c_int
         L.qpgpu_leaf_circuit_hash_hint_cells_cfg.argtypes = [c.c_uint, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_char_p]
+        L.qpgpu_leaf_circuit_build_dense.restype = c.c_int
+        L.qpgpu_leaf_circuit_build_dense.argtypes = [c.c_uint, c.c_uint, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t),
+                                                     c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_char_p]
+        L.qpgpu_leaf_circuit_hash_hint_cells_dense.restype = c.c_int
+        L.qpgpu_leaf_circuit_hash_hint_cells_dense.argtypes = [c.c_uint, c.c_uint, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_char_p]
+        L.qpgpu_leaf_commit_dense.restype = c.c_int
+        L.qpgpu_leaf_commit_dense.argtypes = [c.c_void_p, c.c_uint, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_void_p, c.c_char_p]
         L.qpgpu_leaf_commit.restype = c.c_int
         L.qpgpu_leaf_commit.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_void_p, c.c_char_p]
         L.qpgpu_leaf_check_constraints.restype = c.c_int
@@ -142,7 +151,7 @@ class LeafCircuit:
     reference's prover_create_proof_zk bench target uses), a binding.CircuitConfig, or any object / mapping with qpgpu_circuit_config's
     fields. A config the reference's validate_circuit_config refuses raises QpGpuError with its message."""
 
-    def __init__(self, fragment=FRAGMENT_FULL, min_degree_bits=0, inner_hasher=0, p2_layout=None, config=None):
+    def __init__(self, fragment=FRAGMENT_FULL, min_degree_bits=0, inner_hasher=0, p2_layout=None, config=None, copies=1):
         L = _lib()
         n = ctypes.c_size_t(); nb = ctypes.c_size_t()
         err = ctypes.create_string_buffer(CONFIG_ERR_CAP)
@@ -150,15 +159,24 @@ class LeafCircuit:
         layp = None if lay is None else lay.ctypes.data
         self.config = as_circuit_config(config)
         cfgp = None if self.config is None else ctypes.byref(self.config)
-        rc = L.qpgpu_leaf_circuit_build_cfg(fragment, min_degree_bits, inner_hasher, layp, cfgp, None, 0, ctypes.byref(n), None, None, None, 0, ctypes.byref(nb), err)
+        if copies != 1 and fragment != FRAGMENT_FULL:
+            raise QpGpuError(EINVAL, "LeafCircuit: copies other than 1 exist for the full circuit only (fragment must be FRAGMENT_FULL)")
+
+        def build(pack, pack_cap, tmap, info, blind, blind_cap):
+            # copies = 1 is qpgpu_leaf_circuit_build_cfg's circuit (word for word through either entry); the dense entry has no fragment
+            if copies == 1:
+                return L.qpgpu_leaf_circuit_build_cfg(fragment, min_degree_bits, inner_hasher, layp, cfgp, pack, pack_cap, ctypes.byref(n), tmap, info, blind, blind_cap, ctypes.byref(nb), err)
+            return L.qpgpu_leaf_circuit_build_dense(copies, min_degree_bits, inner_hasher, layp, cfgp, pack, pack_cap, ctypes.byref(n), tmap, info, blind, blind_cap, ctypes.byref(nb), err)
+
+        rc = build(None, 0, None, None, None, 0)
         if rc != 0:
             raise QpGpuError(rc, err.value.decode())
+        self.copies = copies
         self.pack = np.empty(n.value, dtype=np.uint64)
-        self.target_map = np.empty(LT_COUNT, dtype=np.uint64)
+        self.target_map = np.empty(copies * LT_COUNT, dtype=np.uint64)       # copy-major
         self.blinding_cells = np.empty(nb.value, dtype=np.uint64)       # CircuitBuilder::blind's random wires, drawn on the device per proof
         info = np.zeros(len(INFO_FIELDS), dtype=np.uint64)
-        rc = L.qpgpu_leaf_circuit_build_cfg(fragment, min_degree_bits, inner_hasher, layp, cfgp, self.pack.ctypes.data, self.pack.size, ctypes.byref(n),
-                                            self.target_map.ctypes.data, info.ctypes.data, self.blinding_cells.ctypes.data, self.blinding_cells.size, ctypes.byref(nb), err)
+        rc = build(self.pack.ctypes.data, self.pack.size, self.target_map.ctypes.data, info.ctypes.data, self.blinding_cells.ctypes.data, self.blinding_cells.size)
         if rc != 0:
             raise QpGpuError(rc, err.value.decode())
         self.info = {k: int(v) for k, v in zip(INFO_FIELDS, info)}
@@ -167,16 +185,48 @@ class LeafCircuit:
         self._build_args = (min_degree_bits, inner_hasher, layp, lay)
         self._hint_cells = None
 
+    @classmethod
+    def dense(cls, degree_bits, inner_hasher=0, p2_layout=None, config=None):
+        """The density-matched leaf (qpgpu_leaf_circuit_build_dense: a measurement and test object, k statements of which one is public):
+        the largest `copies` whose rows, blinding rows included, fit 2^degree_bits, padded to 2^degree_bits. Sizes are asked for with
+        pack_out = NULL (a dozen host-only builds)."""
+        L = _lib()
+        lay = None if p2_layout is None else np.ascontiguousarray(p2_layout, dtype=np.uint64)
+        cfg = as_circuit_config(config)
+
+        def fits(k):
+            n = ctypes.c_size_t(); info = np.zeros(len(INFO_FIELDS), dtype=np.uint64); err = ctypes.create_string_buffer(CONFIG_ERR_CAP)
+            rc = L.qpgpu_leaf_circuit_build_dense(k, 0, inner_hasher, None if lay is None else lay.ctypes.data, None if cfg is None else ctypes.byref(cfg),
+                                                  None, 0, ctypes.byref(n), None, info.ctypes.data, None, 0, None, err)
+            if rc != 0 and k == 1:
+                raise QpGpuError(rc, err.value.decode())
+            return rc == 0 and int(info[0]) <= degree_bits
+
+        if not fits(1):
+            raise QpGpuError(EINVAL, "LeafCircuit.dense: one copy of the leaf circuit does not fit 2^%d rows" % degree_bits)
+        lo, hi = 1, 2                                                   # fits(lo), and hi is the first candidate not known to fit
+        while fits(hi):
+            lo, hi = hi, 2 * hi
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+        return cls(copies=lo, min_degree_bits=degree_bits, inner_hasher=inner_hasher, p2_layout=p2_layout, config=config)
+
     @property
     def hash_hint_cells(self):
-        """The cells of the 61 Poseidon2 rows' outputs, call sites in tag order (qpgpu_leaf_circuit_hash_hint_cells_cfg); full circuit only."""
+        """The cells of the 61 Poseidon2 rows' outputs, call sites in tag order, then the Merkle walk's running hashes — per copy, copy-major
+        (qpgpu_leaf_circuit_hash_hint_cells_cfg / _dense); full circuit only."""
         if self._hint_cells is None:
             if self.fragment != FRAGMENT_FULL:
                 raise ValueError("hash hints exist for the full leaf circuit only")
-            cells = np.empty(HASH_HINTS, dtype=np.uint64)
+            cells = np.empty(self.copies * HASH_HINTS, dtype=np.uint64)
             n = ctypes.c_size_t(); err = ctypes.create_string_buffer(CONFIG_ERR_CAP)
-            rc = _lib().qpgpu_leaf_circuit_hash_hint_cells_cfg(self._build_args[0], self._build_args[1], self._build_args[2], None if self.config is None else ctypes.byref(self.config),
-                                                               cells.ctypes.data, cells.size, ctypes.byref(n), err)
+            cfgp = None if self.config is None else ctypes.byref(self.config)
+            if self.copies == 1:
+                rc = _lib().qpgpu_leaf_circuit_hash_hint_cells_cfg(self._build_args[0], self._build_args[1], self._build_args[2], cfgp, cells.ctypes.data, cells.size, ctypes.byref(n), err)
+            else:
+                rc = _lib().qpgpu_leaf_circuit_hash_hint_cells_dense(self.copies, self._build_args[0], self._build_args[1], self._build_args[2], cfgp,
+                                                                     cells.ctypes.data, cells.size, ctypes.byref(n), err)
             if rc != 0:
                 raise QpGpuError(rc, err.value.decode())
             self._hint_cells = cells[:n.value].copy()
@@ -188,20 +238,33 @@ class LeafCircuit:
         with the 61 hash rows generated side by side and checked instead of one after the other. device_blinding=True (zero-knowledge
         circuits): the blinding cells are appended to the cell list WITHOUT values, [logical targets][hash hints][blinding cells] — stage s1
         draws them on the device (n_blinding = self.blinding_cells.size of Circuit.generate_witness_partial_batch_blinded_dev and
-        ProvingPool.set_partial_cells)."""
-        cells = np.empty(LT_COUNT, dtype=np.uint64); values = np.empty(LT_COUNT, dtype=np.uint64); pis = np.empty(PUBLIC_INPUTS, dtype=np.uint64)
+        ProvingPool.set_partial_cells).
+        A circuit of several copies takes a list of `copies` inputs (qpgpu_leaf_commit_dense: inputs[c] feeds copy c, the public inputs are
+        inputs[0]'s; one LeafInputs alone feeds every copy); the lists are copy-major: [logical targets, per copy][hash hints, per copy][blinding cells]."""
+        ins = list(inputs) if isinstance(inputs, (list, tuple)) else [inputs] * self.copies
+        if len(ins) != self.copies:
+            raise ValueError("commit: %d inputs for a circuit of %d copies" % (len(ins), self.copies))
+        cap = self.copies * LT_COUNT
+        cells = np.empty(cap, dtype=np.uint64); values = np.empty(cap, dtype=np.uint64); pis = np.empty(PUBLIC_INPUTS, dtype=np.uint64)
         n = ctypes.c_size_t(); err = ctypes.create_string_buffer(160)
-        rc = _lib().qpgpu_leaf_commit(ctypes.byref(inputs), self.target_map.ctypes.data, cells.ctypes.data, values.ctypes.data, LT_COUNT,
-                                      ctypes.byref(n), pis.ctypes.data, err)
+        if self.copies == 1:
+            rc = _lib().qpgpu_leaf_commit(ctypes.byref(ins[0]), self.target_map.ctypes.data, cells.ctypes.data, values.ctypes.data, LT_COUNT,
+                                          ctypes.byref(n), pis.ctypes.data, err)
+        else:
+            ptrs = (ctypes.c_void_p * self.copies)(*[ctypes.addressof(x) for x in ins])
+            rc = _lib().qpgpu_leaf_commit_dense(ptrs, self.copies, self.target_map.ctypes.data, cells.ctypes.data, values.ctypes.data, cap,
+                                                ctypes.byref(n), pis.ctypes.data, err)
         if rc != 0:
             raise ValueError(err.value.decode())
         cells, values = [cells[:n.value]], [values[:n.value]]
         if hash_hints:
-            hv = np.empty(HASH_HINTS, dtype=np.uint64)
-            hn = ctypes.c_size_t()
-            if _lib().qpgpu_leaf_hash_hints(ctypes.byref(inputs), hv.ctypes.data, hv.size, ctypes.byref(hn), err) != 0:
-                raise ValueError(err.value.decode())
-            cells.append(self.hash_hint_cells); values.append(hv[:hn.value])
+            hv = np.empty(self.copies * HASH_HINTS, dtype=np.uint64)
+            for c, x in enumerate(ins):
+                hn = ctypes.c_size_t()
+                if _lib().qpgpu_leaf_hash_hints(ctypes.byref(x), hv[c * HASH_HINTS:].ctypes.data, HASH_HINTS, ctypes.byref(hn), err) != 0:
+                    raise ValueError(("copy %d: " % c if self.copies > 1 else "") + err.value.decode())
+                assert hn.value == HASH_HINTS
+            cells.append(self.hash_hint_cells); values.append(hv)
         if device_blinding:
             cells.append(self.blinding_cells)
         return np.concatenate(cells), np.concatenate(values), self.public_inputs(pis)

@@ -4,14 +4,17 @@
       Wall time of the wires-shaped commitment of one lockstep batch (2^21 leaves x 135 columns, cap height 4) and of its leaf level
       alone, host timers around a synchronised loop.
 
-  leaf_time.py --config {leaf,zk} [--min-degree-bits N] [--hints] [--proofs N] [--workers W] [--max-batch B] [--pool-proofs N] [--batch-probe B]
+  leaf_time.py --config {leaf,zk} [--min-degree-bits N] [--copies K|dense] [--hints] [--proofs N] [--workers W] [--max-batch B] [--pool-proofs N] [--batch-probe B]
       The leaf PROVER under a CircuitConfig (WormholeProver::new(config)): "leaf" is wormhole_leaf_circuit_config(), "zk" the
       zero-knowledge wormhole_private_batch_circuit_config() of the reference's prover_create_proof_zk bench target. Prints one JSON
       line: single-proof latency of commit -> stage s1 -> s2..s12 (median, host timer), the share of stage s1 (host timer around the
       synchronised witness call, which for a zero-knowledge circuit includes the draw and the scatter of the blinding cells, and the
       library's own "witness_generate" profile region, which covers the generator levels only), the rate of a pool of W workers in
       lockstep batches of B, dependency levels, blinding rows and cells, and the device memory one proof of a B-proof lockstep handle
-      takes (free-memory difference around loading it)."""
+      takes (free-memory difference around loading it).
+      --copies K: the density-matched leaf of K copies (LeafCircuit(copies=K): a measurement object, K statements of which one is public);
+      --copies dense: as many copies as fit 2^min-degree-bits rows. With copies, stage s1 is also timed for one witness and for a lockstep
+      batch of --max-batch with QPGPU_WITNESS_WIDE_ROWS at 0 and at 1, alternated inside this one call on freshly loaded handles."""
 import json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,6 +37,7 @@ def prover_mode(argv):
     ap.add_argument("--config", choices=("leaf", "zk"), required=True)
     ap.add_argument("--min-degree-bits", type=int, default=0)
     ap.add_argument("--hints", action="store_true")
+    ap.add_argument("--copies", default="1")
     ap.add_argument("--proofs", type=int, default=20)
     ap.add_argument("--workers", type=int, default=6)
     ap.add_argument("--max-batch", type=int, default=8)
@@ -41,9 +45,10 @@ def prover_mode(argv):
     ap.add_argument("--batch-probe", type=int, default=64)
     a = ap.parse_args(argv)
     L = pkg.leaf
-    c = L.LeafCircuit(min_degree_bits=a.min_degree_bits, config="private_batch" if a.config == "zk" else "leaf")
+    cfg = "private_batch" if a.config == "zk" else "leaf"
+    c = L.LeafCircuit.dense(a.min_degree_bits, config=cfg) if a.copies == "dense" else L.LeafCircuit(min_degree_bits=a.min_degree_bits, config=cfg, copies=int(a.copies))
     x = L.dummy_circuit_inputs()
-    out = {"config": a.config, "hash_hints": a.hints, "degree_bits": c.info["degree_bits"], "rows_before_padding": c.info["rows_before_padding"],
+    out = {"config": a.config, "copies": c.copies, "rows_poseidon2": c.info["rows_poseidon2"], "hash_hints": a.hints, "degree_bits": c.info["degree_bits"], "rows_before_padding": c.info["rows_before_padding"],
            "blinding_cells": int(c.blinding_cells.size), "zero_knowledge": c.zero_knowledge}
     if c.zero_knowledge:
         routed = int(c.config.num_routed_wires)
@@ -53,7 +58,7 @@ def prover_mode(argv):
         pr = L.LeafProver(pkg, gpu, c, hash_hints=a.hints)
         for _ in range(3):
             pr.prove(x)
-        out["dependency_levels"] = pr.circ.witness_info()[1]
+        out["generator_instances"], out["dependency_levels"] = pr.circ.witness_info()[:2]
         lat, s1 = [], []
         for _ in range(a.proofs):
             gpu.sync(); t0 = time.perf_counter()
@@ -70,6 +75,10 @@ def prover_mode(argv):
         out["witness_generate_region_ms"] = round(ms / max(n, 1), 3)
         gpu.profile(False)
         pr.close()
+        if c.copies > 1 and not c.zero_knowledge:
+            from witness_wide_rows_ab import wide_rows_ab      # tools/ is this script's directory
+            cells, values, pis = c.commit(x, hash_hints=a.hints)
+            out["stage_s1_wide_rows_ab_ms"] = wide_rows_ab(pkg, gpu, c.pack, c.info["degree_bits"], cells, values, pis, a.max_batch)
         free0 = device_free_bytes()
         big = pkg.Circuit(gpu, c.pack, max_batch=a.batch_probe)
         cells = c.commit(x, hash_hints=a.hints, device_blinding=c.zero_knowledge)[0]
