@@ -170,7 +170,8 @@ int orc_verify(const orc_circuit *c, const uint8_t *proof, size_t len) {
             size_t lvl = L;
             for (size_t r = 0; r < c->n_arity; r++) {
                 unsigned ab = (unsigned)c->arity[r]; size_t arity = (size_t)1 << ab;
-                gl_t ev[32 * 2];
+                gl_t ev[256 * 2];                                /* the stage ABI reduces by up to 8 bits a round */
+                if (ab > 8) { rc = 6; break; }
                 r_vec(&q, ev, 2 * arity);
                 size_t plen = r_u8(&q); if (plen > 60) { rc = 6; break; }
                 r_vec(&q, path, plen * 4);
@@ -182,7 +183,7 @@ int orc_verify(const orc_circuit *c, const uint8_t *proof, size_t len) {
                 gl_t g = gl_root_of_unity(ab);
                 size_t rev_within = bitrev32((uint32_t)within, ab);
                 gl_t coset_start = gl_mul(subgroup_x, gl_pow(g, arity - rev_within));
-                gl2_t pts_y[32]; gl_t pts_x[32];
+                gl2_t pts_y[256]; gl_t pts_x[256];
                 for (size_t i = 0; i < arity; i++) {
                     size_t src = bitrev32((uint32_t)i, ab);
                     pts_y[i] = gl2_make(ev[2 * src], ev[2 * src + 1]);

@@ -116,6 +116,8 @@ std::string CircuitPack::validate() const {
     uint64_t sum = 0;
     for (auto a : arity_bits) { if (a == 0 || a > 4) return "unsupported FRI arity"; sum += a; }
     if (sum > degree_bits) return "FRI reductions exceed degree";
+    // the last round's tree is the smallest: it must still hold the cap (a Merkle path has log2 leaves - cap_height siblings)
+    if (degree_bits + rate_bits - sum < cap_height) return "FRI reductions take a round's tree below the cap height";
     for (const auto &g : gates) {
         if (g.type > GATE_POSEIDON2) return "unknown gate type";
         if (g.type == GATE_POSEIDON2) {

@@ -149,6 +149,30 @@ def test_refusals_carry_the_references_message(pkg):
         pkg.leaf.LeafCircuit(config="no_such_level")
 
 
+def test_reduction_strategy_knobs(pkg):
+    """reduction_arity_bits 1..4 and reduction_final_poly_bits 0..8 are taken, and the pack carries ConstantArityBits' list for
+    them; 0, 5 and 9 are refused by the builder and by LeafCircuit with a message naming the field and the value."""
+    import fri_schedules as fs
+    for ab in (1, 2, 3, 4):
+        for fin in (0, 2, 5, 8):
+            cfg = pkg.circuit_config("leaf", reduction_arity_bits=ab, reduction_final_poly_bits=fin)
+            assert pkg.validate_circuit_config(cfg) is None
+            rc, err, pack, *_ = build_cfg(pkg, 0, cfg)
+            assert rc == 0, err
+            h = pkg.pack_header(pack)
+            assert [int(x) for x in pack[18:18 + h["num_arity_rounds"]]] == fs.constant_arity(h["degree_bits"], 3, 4, ab, fin), (ab, fin)
+    # the reference's config policy does not look at the reduction strategy; the builder's own range check refuses by name
+    for field, value, needle in (("reduction_arity_bits", 0, b"arity_bits (0) must be 1..4"), ("reduction_arity_bits", 5, b"arity_bits (5) must be 1..4"),
+                                 ("reduction_final_poly_bits", 9, b"final_poly_bits (9) must be <= 8")):
+        cfg = pkg.circuit_config("leaf", **{field: value})
+        assert pkg.validate_circuit_config(cfg) is None
+        rc, err, *_ = build_cfg(pkg, 0, cfg)
+        assert rc == EINVAL and needle in err, (field, value, err)
+        with pytest.raises(pkg.QpGpuError) as e:
+            pkg.leaf.LeafCircuit(config=cfg)
+        assert e.value.code == EINVAL and needle.decode() in str(e.value)
+
+
 def test_hint_cells_are_those_of_the_plain_circuit(pkg):
     L = pkg.leaf
     cfg = reduced_zk_config(pkg)

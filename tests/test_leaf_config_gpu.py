@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import fri_schedules as fs
 import leaf_cases as lc
 import oracle_binding as ob
 from test_leaf_config import blind_counts, reduced_zk_config
@@ -149,11 +150,17 @@ def test_lockstep_pool_fails_the_bad_ticket_alone(pkg, gpu, L, zk):
     pr.close(); ver.close()
 
 
-@pytest.mark.parametrize("knobs", [dict(rate_bits=4), dict(cap_height=2, num_query_rounds=10), dict(proof_of_work_bits=8)], ids=lambda k: "-".join("%s=%d" % kv for kv in k.items()))
+@pytest.mark.parametrize("knobs", [dict(rate_bits=4), dict(cap_height=2, num_query_rounds=10), dict(proof_of_work_bits=8),
+                                   dict(reduction_arity_bits=2), dict(reduction_arity_bits=3, reduction_final_poly_bits=2),
+                                   dict(reduction_arity_bits=1, reduction_final_poly_bits=0, cap_height=2)], ids=lambda k: "-".join("%s=%d" % kv for kv in k.items()))
 def test_non_zero_knowledge_knobs_match_the_oracle(pkg, gpu, orc, L, knobs):
     c = L.LeafCircuit(config=pkg.circuit_config("leaf", **knobs))
     h = pkg.pack_header(c.pack)
-    assert h["degree_bits"] == 8 and all(h[k] == v for k, v in knobs.items())
+    assert h["degree_bits"] == 8 and all(h[k] == v for k, v in knobs.items() if k in h)
+    cfg = c.config
+    arity = [int(x) for x in c.pack[18:18 + h["num_arity_rounds"]]]
+    assert arity == fs.constant_arity(8, cfg.rate_bits, cfg.cap_height, cfg.reduction_arity_bits, cfg.reduction_final_poly_bits)
+    assert arity == {2: [2, 2], 3: [3, 3], 1: [1] * 8}.get(knobs.get("reduction_arity_bits"), [4])
     pr = L.LeafProver(pkg, gpu, c)
     ver = pkg.Verifier(c.pack, circuit=pr.circ)
     oc = ob.OracleCircuit(orc, c.pack)

@@ -227,3 +227,76 @@ def test_fill_private_batch_witness(pkg, lib, inner):
     bad = pre.copy(); bad[1, 2] = P
     rc, _, _, msg, _ = fill(lib, pack, proofs, 2, bad, 2)
     assert rc == -1 and msg.startswith("failed to set dummy nullifier preimage target at slot 1, limb 2")
+
+
+# ---- inner circuits under FRI reduction schedules other than constant arity 16 (tests/fri_schedules.py) ----
+
+def _field_words(pkg, pack, proof):
+    """every field element of a proof in byte order (the one-byte sibling counts left out), any schedule, any width"""
+    import fri_schedules as fs
+    _, fri, lay = fs.fri_of_proof(pkg, pack, proof, np.zeros(4, dtype=np.uint64))
+    h = pkg.pack_header(pack)
+    base = proof.index(fri)
+    L, cap = h["degree_bits"] + h["rate_bits"], h["cap_height"]
+    ncs = h["num_selectors"] + h["num_constants"] + h["num_routed_wires"]
+    nch = h["num_challenges"]
+    widths = [ncs, h["num_wires"], nch * (1 + h["num_partial_products"]), nch * h["quotient_degree_factor"]]
+    out = bytearray(proof[:base + lay.queries_pos])
+    pos = base + lay.queries_pos
+    for _ in range(lay.num_queries):
+        opens = [(w, L - cap) for w in widths] + [(2 << ab, plen) for ab, (_, plen) in zip(lay.arity_bits, lay.rounds)]
+        for w, plen in opens:
+            out += proof[pos:pos + 8 * w]; pos += 8 * w
+            assert proof[pos] == plen; pos += 1
+            out += proof[pos:pos + 32 * plen]; pos += 32 * plen
+    assert pos == base + lay.final_pos
+    out += proof[pos:]
+    return np.frombuffer(bytes(out), dtype="<u8")
+
+
+@pytest.mark.parametrize("label", ["twos", "threes", "ones"])
+def test_targets_under_other_fri_schedules(pkg, lib, orc, label):
+    """The target shape of an inner circuit that folds by 4, by 8 or by 2: cap sizes, evaluations per step and sibling counts
+    computed from the pack (exact equalities), equal to the shape read from an honest proof; the target values are every field
+    element of the proof, each FRI evaluation and each sibling of each round once."""
+    import fri_schedules as fs
+    row = fs.BY_LABEL[label]
+    pack, wires, pis = fs.synth_case(pkg, row, seed=62)
+    oc = OracleCircuit(orc, pack)
+    proof = oc.prove(wires, pis)
+    assert oc.verify(proof) == 0
+    oc.close()
+    h = pkg.pack_header(pack)
+    arity, cap_h, L = row["arity_bits"], row["cap_height"], row["degree_bits"] + row["rate_bits"]
+    ncs = h["num_selectors"] + h["num_constants"] + h["num_routed_wires"]
+    nch, npp, nq = h["num_challenges"], h["num_challenges"] * h["num_partial_products"], h["num_challenges"] * h["quotient_degree_factor"]
+    t = target_shape(lib, pack)
+    cap = 1 << cap_h
+    assert t[:13].tolist() == [3, cap, cap, cap, h["num_selectors"] + h["num_constants"], h["num_routed_wires"], h["num_wires"], nch, nch, npp, nq, 0, 0]
+    n_caps = int(t[13])
+    assert n_caps == len(arity) and t[14:14 + n_caps].tolist() == [cap] * n_caps
+    assert int(t[14 + n_caps]) == h["num_query_rounds"] == 28
+    r0, round_len = 15 + n_caps, 1 + 2 * 4 + 1 + 2 * n_caps
+    want, lvl = [4, ncs, L - cap_h, h["num_wires"], L - cap_h, nch + npp, L - cap_h, nq, L - cap_h, n_caps], L
+    for ab in arity:
+        lvl -= ab
+        want += [1 << ab, lvl - cap_h]
+    for q in range(28):
+        assert t[r0 + q * round_len:r0 + (q + 1) * round_len].tolist() == want, q
+    assert t[r0 + 28 * round_len:].tolist() == [1 << (row["degree_bits"] - sum(arity))]
+    rc, s, _ = bytes_shape(lib, pack, proof)
+    assert rc == 0 and np.array_equal(s, t)
+    T = lib.qpgpu_proof_target_count(pack.ctypes.data, pack.size)
+    assert T == (len(proof) - 28 * (4 + n_caps)) // 8
+    vals = np.zeros(T, dtype=np.uint64); n = ctypes.c_size_t(); err = ctypes.create_string_buffer(ERR)
+    assert lib.qpgpu_proof_target_values(pack.ctypes.data, pack.size, proof, len(proof), 0, b"leaf proof", vals.ctypes.data, T, ctypes.byref(n), err) == 0, err.value
+    words = _field_words(pkg, pack, proof)
+    assert n.value == T == words.size and sorted(vals.tolist()) == sorted(words.tolist())
+    # a sibling count one off at the last round (0 under `ones`: claim one) is a shape mismatch, by name
+    bad = bytearray(proof)
+    _, fri, lay = fs.fri_of_proof(pkg, pack, proof, np.zeros(4, dtype=np.uint64))
+    at = proof.index(fri) + lay.queries_pos + lay.rounds[-1][0] + (16 << arity[-1])
+    assert bad[at] == lay.rounds[-1][1]
+    bad[at] += 1
+    rc, s2, msg = bytes_shape(lib, pack, bytes(bad))
+    assert rc != 0 or ensure(lib, t, s2)[0] != 0

@@ -5,6 +5,7 @@ chunks) come from the oracle's stage trace, standing in for the Rust code that w
 import numpy as np
 import pytest
 
+import fri_schedules as fs
 from oracle_binding import OracleCircuit
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +27,9 @@ def parse_pack(pack):
     return h
 
 
-def staged_proof(pkg, gpu, orc, oc, pack, wires, pis, seed=0):
+def staged_proof(pkg, gpu, orc, oc, pack, wires, pis, seed=0, fri_out=None):
+    """fri_out: a dict that receives the FriProof bytes, a copy of the challenger as it stood when FRI began, and the leaf
+    widths of the four oracles (what fri_schedules.python_fri_check replays)."""
     h = parse_pack(pack)
     d, nch, zk = h["degree_bits"], h["num_challenges"], bool(h["zero_knowledge"])
     n = 1 << d
@@ -53,6 +56,9 @@ def staged_proof(pkg, gpu, orc, oc, pack, wires, pis, seed=0):
     opens = [o.eval(zeta) for o in oracles]
     zs_next = o_zs.eval(g_zeta, 0, nch)
     ch.observe(np.concatenate(opens)); ch.observe(zs_next)
+    if fri_out is not None:
+        fri_out["challenger"] = fs.copy_challenger(pkg, ch)
+        fri_out["leaf_widths"] = [o.num_polys + (4 if zk and i else 0) for i, o in enumerate(oracles)]
     fri = pkg.fri_prove(gpu, oracles, [(zeta, [(0, 0, o_cs.num_polys), (1, 0, o_w.num_polys), (2, 0, o_zs.num_polys), (3, 0, o_q.num_polys)]),
                                        (g_zeta, [(2, 0, nch)])],
                         ch, h["arity_bits"], proof_of_work_bits=h["proof_of_work_bits"], num_query_rounds=h["num_query_rounds"], **kw)
@@ -63,6 +69,8 @@ def staged_proof(pkg, gpu, orc, oc, pack, wires, pis, seed=0):
         (np.asarray(pis, dtype=np.uint64) % np.uint64(P)).tobytes()
     for o in oracles:
         o.close()
+    if fri_out is not None:
+        fri_out["fri"] = fri
     return got, want
 
 
@@ -75,6 +83,84 @@ def test_staged_flow_reproduces_the_proof(pkg, gpu, orc):
         assert got == want, f"staged proof differs at byte {next(i for i in range(len(got)) if got[i] != want[i])}"
         assert oc.verify(got) == 0
         oc.close()
+
+
+# (label, degree_bits, rate_bits, cap_height, arity_bits, replay in Python integers?): reductions of 5..8 bits are the stage ABI's
+# alone (the pack loader stops at 4), so the pack is rewritten for the oracle only and the device never loads it as a circuit
+STAGE_SCHEDULES = [("five", 9, 3, 4, [5], True),
+                   ("eight", 9, 3, 4, [8], False),            # FRI leaves of 512 elements, 16 of them: the cap itself, path length 0
+                   ("six_one", 10, 3, 4, [6, 1], False)] + \
+                  [(s["label"], s["degree_bits"], s["rate_bits"], s["cap_height"], s["arity_bits"], True) for s in (fs.BY_LABEL["falling"], fs.BY_LABEL["ones"])]
+
+
+@pytest.mark.parametrize("label,d,rate_bits,cap_height,arity_bits,replay", STAGE_SCHEDULES, ids=[c[0] for c in STAGE_SCHEDULES])
+def test_staged_flow_under_other_schedules(pkg, gpu, orc, label, d, rate_bits, cap_height, arity_bits, replay):
+    """qpgpu_fri_prove under reduction schedules away from arity 16, byte for byte against the oracle; for three of them the FRI
+    commit phase is replayed in Python integers as well (fri_schedules.python_fri_check): every query of the device's FriProof
+    folds, round by round, into the final polynomial under plain Lagrange interpolation."""
+    pack, wires, pis = pkg.synth_circuit(d, seed=65, num_wires=24, num_routed=16, num_public_inputs=3)
+    pack = fs.with_schedule(pack, arity_bits, cap_height=cap_height, rate_bits=rate_bits)
+    oc = OracleCircuit(orc, pack)
+    out = {}
+    try:
+        got, want = staged_proof(pkg, gpu, orc, oc, pack, wires, pis, fri_out=out)
+        assert len(got) == len(want)
+        assert got == want, f"staged proof differs at byte {next(i for i in range(len(got)) if got[i] != want[i])}"
+        assert oc.verify(got) == 0
+    finally:
+        oc.close()
+    if replay:
+        h = parse_pack(pack)
+        lay = fs.FriLayout(d, rate_bits, cap_height, arity_bits, h["num_query_rounds"], out["leaf_widths"])
+        betas, indices = fs.replay_transcript(out["challenger"], out["fri"], lay)
+        assert len(indices) == h["num_query_rounds"] and len(betas) == len(arity_bits)
+        assert fs.python_fri_check(out["fri"], lay, betas, indices) == []
+
+
+def _fri_prove_raw(pkg, gpu, oracle, challenger, arity_bits, cap_height):
+    """qpgpu_fri_prove itself on one oracle's first two polynomials at the point (3, 4), without the size query pkg.fri_prove
+    makes first: (return code, bytes written)."""
+    import ctypes
+    B = pkg.binding
+    hs = (ctypes.c_void_p * 1)(oracle.h)
+    bs = (B._FriBatch * 1)()
+    bs[0].point[0], bs[0].point[1], bs[0].num_ranges = 3, 4, 1
+    bs[0].ranges[0].oracle, bs[0].ranges[0].first, bs[0].ranges[0].count = 0, 0, 2
+    prm = B._FriParams(oracle.rate_bits, cap_height, 4, 5, len(arity_bits))
+    for i, a in enumerate(arity_bits):
+        prm.reduction_arity_bits[i] = a
+    out = np.zeros(1 << 16, dtype=np.uint8)
+    ln = ctypes.c_size_t(0)
+    rc = gpu.lib.qpgpu_fri_prove(gpu.ctx, hs, 1, ctypes.byref(bs), 1, ctypes.byref(prm), ctypes.byref(challenger.state), out.ctypes.data,
+                                 out.size, ctypes.byref(ln))
+    return rc, out[:ln.value].tobytes()
+
+
+def test_stage_api_refuses_bad_schedules(pkg, gpu):
+    """Schedules qpgpu_fri_prove must refuse, through the binding (which asks qpgpu_fri_proof_size first) and at the entry
+    itself: deeper than the degree, a tree below the cap, a round of 0 or 9 bits. Each is QPGPU_EINVAL; the context and the
+    oracle keep working (a good call follows, and its FriProof replays in Python integers)."""
+    rng = np.random.default_rng(66)
+    vals = rng.integers(0, P, size=(2, 64), dtype=np.uint64)                   # degree_bits 6, rate 3: the LDE has 2^9 points
+    o = pkg.PolyOracle(gpu, vals, rate_bits=3, cap_height=4)
+    try:
+        # sum 7 > 6 twice; sum 6 leaves a tree of 2^3 leaves under a cap of 2^4; rounds of 0 and 9 bits
+        for bad in ([4, 3], [3, 3, 1], [3, 3], [0], [2, 0], [9], [1, 9]):
+            with pytest.raises(pkg.QpGpuError):
+                pkg.fri_prove(gpu, [o], [([3, 4], [(0, 0, 2)])], pkg.Challenger(), bad, cap_height=4)
+            rc, out = _fri_prove_raw(pkg, gpu, o, pkg.Challenger(), bad, 4)
+            assert rc == -1 and out == b"", (bad, rc)
+        lay = fs.FriLayout(6, 3, 4, [3, 2], 5, [2])
+        ch = pkg.Challenger()
+        rc, fri = _fri_prove_raw(pkg, gpu, o, ch, [3, 2], 4)
+        assert rc == 0 and len(fri) == lay.total
+        ch2 = pkg.Challenger()
+        assert fri == pkg.fri_prove(gpu, [o], [([3, 4], [(0, 0, 2)])], fs.copy_challenger(pkg, ch2), [3, 2], cap_height=4, proof_of_work_bits=4,
+                                    num_query_rounds=5)
+        betas, indices = fs.replay_transcript(ch2, fri, lay)
+        assert fs.python_fri_check(fri, lay, betas, indices) == []
+    finally:
+        o.close()
 
 
 def test_staged_flow_zero_knowledge(pkg, gpu, orc):

@@ -7,7 +7,9 @@ import ctypes
 import numpy as np
 import pytest
 
+import fri_schedules as fs
 import leaf_cases as lc
+from oracle_binding import OracleCircuit
 
 pytestmark = pytest.mark.gpu
 
@@ -109,6 +111,7 @@ def tamper_corpus(pkg, v, pack, proof, seed=11):
     """One tampered copy of `proof` per region (the list of the issue: opened rows, siblings, path lengths, FRI evaluations and
     paths, final polynomial, proof of work, a cap, an opening, a public input, a non-canonical word, random byte flips)."""
     lay = Layout(pkg, pack)
+    pkg.recursion._lib()                       # declares qpgpu_verifier_query_indices' argument types (pointers are 64-bit)
     idx = np.zeros(lay.nq, dtype=np.uint64)
     e = ctypes.create_string_buffer(CAP)
     assert v.lib.qpgpu_verifier_query_indices(v.h, proof, len(proof), idx.ctypes.data, lay.nq, e) == 0, e.value
@@ -125,7 +128,7 @@ def tamper_corpus(pkg, v, pack, proof, seed=11):
             variant(lambda b, q=q, k=k: set_word(b, lay.row(q, k), (word(b, lay.row(q, k)) + 1) % P))
         variant(lambda b, k=k: b.__setitem__(lay.plen_pos(1, k) + 1 + 8, b[lay.plen_pos(1, k) + 1 + 8] ^ 4))      # a sibling word
     for k in range(len(lay.opens)):
-        for val in (61, max(0, lay.opens[k][2] - 1)):
+        for val in (61, lay.opens[k][2] - 1 if lay.opens[k][2] else 1):     # a tree that is its own cap has no siblings: claim one
             variant(lambda b, k=k, val=val: b.__setitem__(lay.plen_pos(0, k), val))
     shift = 0
     for r, a in enumerate(lay.arity_bits):
@@ -133,9 +136,11 @@ def tamper_corpus(pkg, v, pack, proof, seed=11):
         within = (int(idx[0]) >> shift) & ((1 << a) - 1)
         for slot in (within, (within + 1) % (1 << a)):
             variant(lambda b, k=k, slot=slot: set_word(b, lay.row(0, k) + 16 * slot, (word(b, lay.row(0, k) + 16 * slot) + 5) % P))
-        variant(lambda b, k=k: b.__setitem__(lay.plen_pos(2, k) + 1 + 16, b[lay.plen_pos(2, k) + 1 + 16] ^ 1))     # FRI path
+        # FRI path (where the round has none, the byte belongs to what follows the empty path: the next query round)
+        variant(lambda b, k=k: b.__setitem__(lay.plen_pos(2, k) + 1 + 16, b[lay.plen_pos(2, k) + 1 + 16] ^ 1))
         shift += a
-    variant(lambda b: set_word(b, lay.final_pos + 16, (word(b, lay.final_pos + 16) + 1) % P))          # final polynomial
+    fin = lay.final_pos + (16 if lay.final_n > 1 else 0)                                                # final polynomial
+    variant(lambda b: set_word(b, fin, (word(b, fin) + 1) % P))
     variant(lambda b: set_word(b, lay.pow_pos, (word(b, lay.pow_pos) + 1) % P))                         # proof-of-work witness
     variant(lambda b: b.__setitem__(8, b[8] ^ 1))                                                       # the wires cap
     variant(lambda b: b.__setitem__(lay.openings_pos + 24, b[lay.openings_pos + 24] ^ 1))               # an opening
@@ -188,6 +193,83 @@ def batches(pkg, gpu):
     pb = priv.commit(leaves, seed=bytes(range(32))).prove()
     yield leaf, priv, leaves, pb
     priv.close()
+
+
+SCHEDULE_LABELS = ["ones", "falling", "rising", "none_long_final"]
+# different witnesses of one circuit come from its public-input cells, a trailer only packs with Poseidon rows carry (135 wires)
+WITH_PI_CELLS = dict(poseidon=True, base_sum=True)
+
+
+def schedule_fixture(pkg, gpu, orc, count=4):
+    """label -> (pack, Verifier, proofs, OracleCircuit): `count` proofs of different witnesses of a Poseidon / BaseSum circuit under rows
+    of fri_schedules.SCHEDULES."""
+    from test_batch_gpu import _witnesses
+    out = {}
+    for i, label in enumerate(SCHEDULE_LABELS):
+        pack, wires, _ = fs.synth_case(pkg, fs.BY_LABEL[label], seed=760 + i, **WITH_PI_CELLS)
+        pis, ws = _witnesses(pkg, gpu, pack, wires, count)
+        circ = pkg.Circuit(gpu, pack)
+        v = pkg.Verifier(pack, circuit=circ)
+        proofs = [circ.prove(w, p) for w, p in zip(ws, pis)]
+        circ.close()
+        out[label] = (pack, v, proofs, OracleCircuit(orc, pack))
+    return out
+
+
+def close_schedule_fixture(fx):
+    for _, v, _, oc in fx.values():
+        v.close(); oc.close()
+
+
+@pytest.fixture(scope="module")
+def schedules(pkg, gpu, orc):
+    fx = schedule_fixture(pkg, gpu, orc)
+    yield fx
+    close_schedule_fixture(fx)
+
+
+def assert_oracle_agrees(oc, proofs, results):
+    """Three-way agreement: oracle/verify.c accepts exactly what the host verifier (and so the device) accepts."""
+    for i, (p, r) in enumerate(zip(proofs, results)):
+        assert (oc.verify(p) == 0) == (r == 0), (i, r)
+
+
+@pytest.mark.parametrize("label", SCHEDULE_LABELS)
+def test_accepts_proofs_under_other_fri_schedules(schedules, gpu, label):
+    pack, v, proofs, oc = schedules[label]
+    assert len(set(proofs)) == len(proofs) == 4
+    rc, res, reasons, _ = assert_same_as_host(v, gpu, proofs)
+    assert rc == 0 and res == [0] * 4 and reasons == [""] * 4
+    assert_oracle_agrees(oc, proofs, res)
+
+
+@pytest.mark.parametrize("label", SCHEDULE_LABELS)
+def test_tamper_corpus_under_other_fri_schedules(schedules, pkg, gpu, label):
+    """The tamper corpus per schedule: host and device give the same verdict and reason for every variant, and the oracle's
+    verifier the same verdict. Under `ones` (arity 2, the last round's tree is its own cap) both kinds of FRI-round failure are
+    reached, and a sibling count other than 0 at that round is refused in the same words on both sides."""
+    pack, v, proofs, oc = schedules[label]
+    lay = Layout(pkg, pack)
+    corpus = tamper_corpus(pkg, v, pack, proofs[1], seed=13)
+    got = assert_same_as_host(v, gpu, corpus)
+    assert got[0] == EVERIFY and got[1].count(0) < len(corpus) // 4, got[1]
+    assert_oracle_agrees(oc, corpus, got[1])
+    kinds = {r.split(": ", 1)[-1] for r in got[2] if r}
+    for needle in ("Merkle path length of oracle", "does not lead to its cap"):
+        assert any(needle in k for k in kinds), (needle, sorted(kinds))
+    if label == "ones":
+        assert lay.opens[-1][2] == 0 and proofs[1][lay.plen_pos(0, len(lay.opens) - 1)] == 0
+        for needle in ("does not continue the previous evaluation", "Merkle path of FRI round", "Merkle path length of FRI round 6 out of range"):
+            assert any(needle in k for k in kinds), (needle, sorted(kinds))
+        for q in (0, lay.nq - 1):
+            for claimed in (1, 2):
+                b = bytearray(proofs[1]); b[lay.plen_pos(q, len(lay.opens) - 1)] = claimed
+                rc, res, reasons, _ = assert_same_as_host(v, gpu, [proofs[0], bytes(b)])
+                assert res == [0, EVERIFY] and reasons[1] == "query %d: Merkle path of FRI round 6 does not lead to its cap" % q, reasons
+                assert oc.verify(bytes(b)) != 0
+    if label == "none_long_final":
+        assert lay.arity_bits == [] and lay.final_n == 128
+        assert any("final polynomial" in k for k in kinds) or any("proof-of-work" in k for k in kinds), sorted(kinds)
 
 
 def test_accepts_what_the_host_accepts_bench_shape(bench, gpu):

@@ -18,7 +18,8 @@ import numpy as np
 import pytest
 
 import leaf_cases as lc
-from test_verifier_device_gpu import CAP, EINVAL, EVERIFY, Layout, host_call, set_word, tamper_corpus, word
+from test_verifier_device_gpu import (CAP, EINVAL, EVERIFY, SCHEDULE_LABELS, Layout, assert_oracle_agrees, close_schedule_fixture, host_call,
+                                      schedule_fixture, set_word, tamper_corpus, word)
 
 pytestmark = pytest.mark.gpu
 
@@ -369,3 +370,36 @@ def test_private_batch_prover_with_the_full_device_route(batches, pkg, gpu):
         assert "private-batch proof 0 failed verification against the pinned private-batch verifier" in str(e.value)
     finally:
         pub.close()
+
+
+# ---- FRI reduction schedules other than constant arity 16 (tests/fri_schedules.py) ----
+
+@pytest.fixture(scope="module")
+def schedules(pkg, gpu, orc):
+    fx = schedule_fixture(pkg, gpu, orc)
+    yield fx
+    close_schedule_fixture(fx)
+
+
+@pytest.mark.parametrize("label", SCHEDULE_LABELS)
+def test_head_on_device_under_other_fri_schedules(schedules, pkg, gpu, label):
+    """The device head under each schedule (its round count and its final-polynomial length are the transcript kernel's loop
+    bounds: 7 rounds and 2 coefficients, 3 and 1, 3 and 8, 0 and 128): the proofs are accepted, and a changed final polynomial,
+    FRI cap (the first opened row where there is no round) and proof-of-work witness get the host's verdict and reason; the
+    oracle's verifier gives the same verdicts. Then the whole tamper corpus through the head."""
+    pack, v, proofs, oc = schedules[label]
+    lay = Layout(pkg, pack)
+    assert v.verify_many(proofs, gpu=gpu, device_head=True) == [True] * 4 and v.reasons == [""] * 4
+    tampers = []
+    for pos in (lay.final_pos + 16 * (lay.final_n - 1) + 8, lay.fri_caps_pos + 8, lay.pow_pos):
+        b = bytearray(proofs[2]); set_word(b, pos, (word(b, pos) + 1) % pkg.P)
+        tampers.append(bytes(b))
+    batch = [proofs[0]] + tampers + [proofs[3]]
+    rc, res, reasons, _ = assert_same_as_host(v, gpu, batch)
+    assert rc == EVERIFY and res == [0, EVERIFY, EVERIFY, EVERIFY, 0], (res, reasons)
+    assert v.verify_many(batch, gpu=gpu, device_head=True) == [True, False, False, False, True] and v.reasons == reasons
+    assert_oracle_agrees(oc, batch, res)
+    corpus = tamper_corpus(pkg, v, pack, proofs[3], seed=14)
+    got = assert_same_as_host(v, gpu, corpus)
+    assert got[0] == EVERIFY
+    assert_oracle_agrees(oc, corpus, got[1])

@@ -207,3 +207,59 @@ def test_pack_config_is_canonical(pkg):
     assert lib.qpgpu_pack_config_is_canonical(priv.ctypes.data, priv.size, 1, err) == 0, err.value
     priv[13] = 20
     assert lib.qpgpu_pack_config_is_canonical(priv.ctypes.data, priv.size, 1, err) != 0 and b"num_query_rounds loaded=20, expected=28" in err.value
+
+
+# ---- FRI reduction schedules at the pack loader ----
+
+def _pack_refusal(pkg, lib, pack):
+    """(qpgpu_pack_validate's message, pkg.Verifier's message) for a pack both must refuse."""
+    p = np.ascontiguousarray(pack, dtype=np.uint64)
+    err = ctypes.create_string_buffer(200)
+    assert lib.qpgpu_pack_validate(p.ctypes.data, p.size, err) != 0
+    with pytest.raises(pkg.QpGpuError) as e:
+        pkg.Verifier(p)
+    assert e.value.code == -1
+    return err.value.decode(), str(e.value)
+
+
+def test_schedule_below_the_cap_is_refused_at_load(lib, pkg):
+    """degree_bits 8, rate 3, cap 4, [4, 4]: the sum fits the degree, but the second round's tree has 2^3 leaves under a cap of
+    2^4, and the proof layout would size its Merkle path as 3 - 4. The loader refuses with a message, for the validator and for
+    the verifier; the same list with the cap it fits loads."""
+    import fri_schedules as fs
+    pack, _, _ = pkg.synth_circuit(8, num_wires=24, num_routed=16, num_public_inputs=3, seed=5)
+    bad = fs.with_schedule(pack, [4, 4], cap_height=4, rate_bits=3)
+    msg, vmsg = _pack_refusal(pkg, lib, bad)
+    assert "below the cap height" in msg and ("cap height" in vmsg or "cap_height" in vmsg), (msg, vmsg)
+    # the loader itself (CircuitPack::validate), which the prover and the proof-target entries go through without the validator's
+    # extra pass: it used to take this pack, and the target count came out as 481 036 344 524 (a path of 3 - 4 siblings)
+    vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    lib.qpgpu_proof_target_shape.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz), ctypes.c_char_p]
+    lib.qpgpu_proof_target_count.argtypes = [vp, sz]; lib.qpgpu_proof_target_count.restype = sz
+    n = sz(); e = ctypes.create_string_buffer(400)
+    assert lib.qpgpu_proof_target_shape(bad.ctypes.data, bad.size, None, 0, ctypes.byref(n), e) == -1 and b"below the cap height" in e.value, e.value
+    assert lib.qpgpu_proof_target_count(bad.ctypes.data, bad.size) == 0
+    good = fs.with_schedule(pack, [4, 3], cap_height=4, rate_bits=3)
+    assert lib.qpgpu_proof_target_shape(good.ctypes.data, good.size, None, 0, ctypes.byref(n), e) == 0 and 0 < lib.qpgpu_proof_target_count(good.ctypes.data, good.size) < 1 << 20
+    err = ctypes.create_string_buffer(200)
+    for arity, cap in (([4, 4], 3), ([4, 3], 4), ([1] * 7, 4), ([1] * 8, 3)):                  # trees exactly at the cap load
+        ok = fs.with_schedule(pack, arity, cap_height=cap, rate_bits=3)
+        assert lib.qpgpu_pack_validate(ok.ctypes.data, ok.size, err) == 0, (arity, cap, err.value)
+        v = pkg.Verifier(ok)
+        assert v.proof_size() > 0
+        v.close()
+    for arity, cap in (([1] * 8, 4), ([4, 3, 1], 4), ([2, 4, 2], 4)):                          # one level below it do not
+        b = fs.with_schedule(pack, arity, cap_height=cap, rate_bits=3)
+        assert lib.qpgpu_pack_validate(b.ctypes.data, b.size, err) != 0 and b"cap height" in err.value, (arity, cap)
+
+
+def test_seventeen_rounds_are_refused_at_load(lib, pkg):
+    """A pack holds at most 16 reduction rounds (the verifiers keep 16 betas): 17 rounds of one bit at degree_bits 17, the smallest
+    degree that admits them, are refused by the validator and by the verifier with an error; 16 load."""
+    import fri_schedules as fs
+    pack, _, _ = pkg.synth_circuit(17, num_wires=8, num_routed=8, num_public_inputs=0, seed=6)
+    for msg in _pack_refusal(pkg, lib, fs.with_schedule(pack, [1] * 17)):
+        assert "out of range" in msg, msg
+    ok = fs.with_schedule(pack, [1] * 16)
+    err = ctypes.create_string_buffer(200)
+    assert lib.qpgpu_pack_validate(ok.ctypes.data, ok.size, err) == 0, err.value

@@ -207,3 +207,99 @@ def test_wire_budget_of_the_wrapper(pkg):
     for routed in (48, 60, 80):
         assert pkg.recursion.WrapperCircuit(fake.pack, ver, 1, num_routed_wires=routed, verify=True).info["degree_bits"] == 12
     ver.close()
+
+
+# ---- inner circuits under FRI reduction schedules other than constant arity 16 (tests/fri_schedules.py) ----
+
+# the fake leaf is a 2^5-row circuit: final_poly_bits below 5 so that it reduces at all
+SCHEDULE_KNOBS = {"twos": dict(reduction_arity_bits=2, reduction_final_poly_bits=1), "threes": dict(reduction_arity_bits=3, reduction_final_poly_bits=2)}
+GATE_RANDOM_ACCESS, GATE_COSET_INTERPOLATION = 10, 13
+FAKE_PIS = np.array([1, 100, 0, 10, 5, 6, 7, 8] + [0] * 12 + [42], dtype=np.uint64)
+
+
+def gate_table(pkg, pack):
+    """[(type, param0, param1)] of a pack's gate table."""
+    h = pkg.pack_header(pack)
+    at = 18 + h["num_arity_rounds"]
+    return [tuple(int(x) for x in pack[at + 8 * g:at + 8 * g + 3]) for g in range(h["num_gates"])]
+
+
+def schedule_inner(pkg, label):
+    """The fake leaf (21 free public inputs, no other assignment) under the config whose ConstantArityBits list is the row's."""
+    import fri_schedules as fs
+    L = pkg.leaf
+    fake = L.LeafCircuit(fragment=L.FRAGMENT_FAKE_LEAF, config=pkg.circuit_config("leaf", **SCHEDULE_KNOBS[label]))
+    h = pkg.pack_header(fake.pack)
+    row = fs.BY_LABEL[label]
+    arity = [int(x) for x in fake.pack[18:18 + h["num_arity_rounds"]]]
+    assert (h["rate_bits"], h["cap_height"]) == (row["rate_bits"], row["cap_height"])
+    knobs = {"reduction_final_poly_bits": 5, **SCHEDULE_KNOBS[label]}
+    assert arity == fs.constant_arity(h["degree_bits"], 3, 4, knobs["reduction_arity_bits"], knobs["reduction_final_poly_bits"])
+    assert arity and set(arity) == set(row["arity_bits"])
+    return fake, h, arity
+
+
+def forge_fri_evaluation(pkg, pack, proof, indices, query=1, rnd=0):
+    """`proof` with one FRI evaluation of `rnd` changed at a position other than the queried one: the continuation check and the
+    transcript do not see it, the Merkle path of that coset and the interpolation do."""
+    import fri_schedules as fs
+    _, fri, lay = fs.fri_of_proof(pkg, pack, proof, np.zeros(4, dtype=np.uint64))
+    base = proof.index(fri)
+    shift = sum(lay.arity_bits[:rnd])
+    ab = lay.arity_bits[rnd]
+    other = (((int(indices[query]) >> shift) & ((1 << ab) - 1)) + 1) % (1 << ab)
+    b = bytearray(proof)
+    b[base + lay.queries_pos + query * lay.q_bytes + lay.rounds[rnd][0] + 16 * other] ^= 1
+    return bytes(b)
+
+
+@pytest.mark.parametrize("label", ["twos", "threes"])
+def test_wrapper_over_other_fri_schedules(pkg, orc, label):
+    """The complete in-circuit verifier over an inner circuit that folds by 4 or by 8: the wrapper holds a CosetInterpolationGate
+    with subgroup_bits 2 / 3 and RandomAccess rows of 4 / 8 entries, the oracle generates its witness from an honest inner proof,
+    proves it and verifies; an inner proof with one FRI evaluation changed beside the queried position has no witness."""
+    fake, h, arity = schedule_inner(pkg, label)
+    ab = arity[0]
+    rc, wires, _ = orc.generate_witness(fake.pack, np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint64), FAKE_PIS)
+    assert rc == orc.WIT_OK
+    oc = ob.OracleCircuit(orc, fake.pack)
+    inner = oc.prove(wires, FAKE_PIS)
+    assert oc.verify(inner) == 0
+    ver = pkg.Verifier(fake.pack)
+    assert ver.verify(inner), ver.reason
+    w = pkg.recursion.WrapperCircuit(fake.pack, ver, 1, verify=True)
+    gates = gate_table(pkg, w.pack)
+    assert [g[1] for g in gates if g[0] == GATE_COSET_INTERPOLATION] == [ab]
+    assert sorted(g[1] for g in gates if g[0] == GATE_RANDOM_ACCESS) == sorted({ab, h["cap_height"]})
+    assert w.info["rows_random_access"] > 0
+    cells, vals, pis = w.commit([inner])
+    assert pis.tolist() == FAKE_PIS.tolist()
+    rc, ww, _ = orc.generate_witness(w.pack, cells, vals, pis)
+    assert rc == orc.WIT_OK
+    ocw = ob.OracleCircuit(orc, w.pack)
+    outer = ocw.prove(ww, pis)
+    assert ocw.verify(outer) == 0
+    ocw.close()
+    for rnd in range(len(arity)):
+        forged = forge_fri_evaluation(pkg, fake.pack, inner, w.query_indices(inner), query=1 + rnd, rnd=rnd)
+        assert not ver.verify(forged) and "FRI round %d" % rnd in ver.reason and oc.verify(forged) != 0
+        c = w.commit([forged], public_inputs=pis)
+        assert orc.generate_witness(w.pack, *c)[0] == orc.WIT_CONFLICT, rnd
+    oc.close(); ver.close()
+
+
+def test_wrapper_refuses_an_arity_2_round_by_name(pkg):
+    """A stated limit: the complete in-circuit verifier interpolates cosets of 2^2..2^5 points (CosetInterpolationGate), so an
+    inner schedule with a 1-bit round is refused with QPGPU_EINVAL and a message naming the range, not built and not aborted on;
+    the Merkle half and the transcript alone (no interpolation) still build over it."""
+    L = pkg.leaf
+    fake = L.LeafCircuit(fragment=L.FRAGMENT_FAKE_LEAF, config=pkg.circuit_config("leaf", reduction_arity_bits=1, reduction_final_poly_bits=0))
+    h = pkg.pack_header(fake.pack)
+    assert [int(x) for x in fake.pack[18:18 + h["num_arity_rounds"]]] == [1] * 4
+    ver = pkg.Verifier(fake.pack)
+    with pytest.raises(pkg.QpGpuError) as e:
+        pkg.recursion.WrapperCircuit(fake.pack, ver, 1, verify=True)
+    assert e.value.code == -1 and "interpolate_coset: 2^subgroup_bits values, 2..5 bits" in str(e.value)
+    w = pkg.recursion.WrapperCircuit(fake.pack, ver, 1)
+    assert GATE_COSET_INTERPOLATION not in {g[0] for g in gate_table(pkg, w.pack)}
+    ver.close()

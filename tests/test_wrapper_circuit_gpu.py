@@ -256,3 +256,49 @@ def test_recursion_under_the_poseidon2_hasher_on_the_device(pkg, orc):
         d.free(scrub=True); wc.close(); ver.close(); lp.close(); g2.close()
     finally:
         pkg.set_hasher_poseidon(); orc.select_poseidon()
+
+
+@pytest.mark.parametrize("label", ["twos", "threes"])
+def test_full_verification_over_other_fri_schedules_on_the_device(pkg, gpu, orc, label):
+    """The complete in-circuit verifier over an inner circuit that folds by 4 / by 8 (tests/test_wrapper_circuit.py builds the same
+    on the CPU): inner proof by the device prover, the wrapper's witness by stage s1 equal to the oracle's, the outer proof equal
+    to the oracle's bytes and accepted by both verifiers; an inner proof with one FRI evaluation changed beside the queried
+    position is QPGPU_EUNSAT at witness generation."""
+    from test_wrapper_circuit import FAKE_PIS, forge_fri_evaluation, schedule_inner
+    fake, h, arity = schedule_inner(pkg, label)
+    circ = pkg.Circuit(gpu, fake.pack)
+    none = np.zeros(0, dtype=np.uint64)
+    rc, iw, _ = orc.generate_witness(fake.pack, none, none, FAKE_PIS)          # the fake leaf has no assignment but its public inputs
+    assert rc == orc.WIT_OK
+    inner = circ.prove(iw, FAKE_PIS)
+    oc = ob.OracleCircuit(orc, fake.pack)
+    assert inner == oc.prove(iw, FAKE_PIS)
+    ver = pkg.Verifier(fake.pack, circuit=circ)
+    assert ver.verify(inner), ver.reason
+    w = pkg.recursion.WrapperCircuit(fake.pack, ver, 1, verify=True)
+    wh = pkg.pack_header(w.pack)
+    cells, vals, pis = w.commit([inner])
+    wc = pkg.Circuit(gpu, w.pack)
+    dw = gpu.alloc(8 * 135 << wh["degree_bits"])
+    try:
+        wc.generate_witness_partial_dev(cells, vals, pis, dw)
+        rc, want, _ = orc.generate_witness(w.pack, cells, vals, pis)
+        assert rc == orc.WIT_OK and np.array_equal(dw.download().reshape(135, 1 << wh["degree_bits"]), want)
+        wc.set_witness_check(True)
+        outer = wc.prove_dev(dw, pis)
+        ocw = ob.OracleCircuit(orc, w.pack)
+        assert outer == ocw.prove(want, pis) and ocw.verify(outer) == 0
+        ocw.close()
+        wver = pkg.Verifier(w.pack, circuit=wc)
+        assert wver.verify(outer), wver.reason
+        wver.close()
+        for rnd in range(len(arity)):
+            forged = forge_fri_evaluation(pkg, fake.pack, inner, w.query_indices(inner), query=1 + rnd, rnd=rnd)
+            assert not ver.verify(forged) and "FRI round %d" % rnd in ver.reason
+            c = w.commit([forged], public_inputs=pis)
+            with pytest.raises(pkg.QpGpuError) as e:
+                wc.generate_witness_partial_dev(c[0], c[1], c[2], dw)
+            assert e.value.code == -4, rnd
+    finally:
+        oc.close(); ver.close(); wc.close(); circ.close()
+        dw.free(scrub=True)
