@@ -164,6 +164,45 @@ int qpgpu_zk_proof_verify(const uint8_t leaf_hash[32], const uint8_t *siblings, 
 int qpgpu_zk_proof_from_unsorted(const uint8_t leaf_hash[32], const uint8_t *unsorted_siblings, size_t depth, uint8_t *sorted_out,
                                  uint8_t *positions_out, uint8_t root_out[32], char *err);
 
+/* ---- the same tree, whole, on the device (csrc/zk_tree.cpp, zk_tree_kernels.hip) ----
+ * The functions above restate the tree's rules one node at a time; these build every level of a block's tree in HBM and open the paths
+ * of many leaves in one call: zk_tree_root, zk_merkle_siblings and zk_merkle_positions of qpgpu_leaf_inputs. They are the
+ * specification: every node, sibling and position equals what the host functions give, byte for byte.
+ *   level 0 is the `count` leaf hashes in the order given; node g of level l + 1 is qpgpu_zk_hash_node of children 4g .. 4g + 3 of
+ *   level l, a child beyond the level's end being the empty hash, 32 zero bytes (zk_merkle.rs:384); level l holds ceil(count / 4^l)
+ *   nodes (wholly empty groups do not exist); `depth` levels are hashed: 1 <= depth <= 16 and 4^depth >= count, depth = 0 asks for the
+ *   smallest such depth (1 for a single leaf), a larger one keeps hashing [node, 0, 0, 0].
+ * The leaf and node hashes are the application hash (qp-poseidon-core's set), whatever the context's proof-system hasher is. Calls
+ * are synchronous on the context's stream and follow the threading rule of every context call (one thread at a time per context);
+ * a tree is freed before its context. Errors: a qpgpu.h code with the text in qpgpu_last_error of the context; qpgpu_zk_tree_build
+ * also writes it to err (QPGPU_LEAF_ERR_CAP bytes, may be NULL). */
+struct qpgpu_ctx;
+typedef struct qpgpu_zk_tree qpgpu_zk_tree;
+typedef struct { uint8_t to_account[32]; uint64_t transfer_count; uint32_t asset_id, input_amount; } qpgpu_zk_leaf;
+#define QPGPU_ZK_TREE_MAX_LEAVES ((size_t)1 << 24)   /* about 0.7 GB of nodes */
+
+/* qpgpu_zk_leaf_hash of `count` transfers (1 .. QPGPU_ZK_TREE_MAX_LEAVES) on the device; out: host, count x 32 bytes */
+int qpgpu_zk_leaf_hash_batch(struct qpgpu_ctx *ctx, const qpgpu_zk_leaf *leaves, size_t count, uint8_t *out);
+
+#define QPGPU_ZK_TREE_FROM_TRANSFERS 1u   /* `leaves` is qpgpu_zk_leaf[count]: the leaf hashes are computed on the device too */
+/* leaves: host, count x 32 bytes of leaf hashes (or transfers, see the flag). QPGPU_EINVAL: count = 0 or above
+ * QPGPU_ZK_TREE_MAX_LEAVES, a depth above 16 or with 4^depth < count, an unknown flag, and a leaf hash with a non-canonical limb (any
+ * 8-byte little-endian limb >= p, as the host functions refuse a child): the message names the lowest such leaf index. *out stays NULL
+ * on every error. */
+int qpgpu_zk_tree_build(struct qpgpu_ctx *ctx, const void *leaves, size_t count, unsigned depth, unsigned flags,
+                        qpgpu_zk_tree **out, char *err);
+void qpgpu_zk_tree_free(qpgpu_zk_tree *t);
+unsigned qpgpu_zk_tree_depth(const qpgpu_zk_tree *t);
+size_t qpgpu_zk_tree_leaf_count(const qpgpu_zk_tree *t);
+int qpgpu_zk_tree_root(const qpgpu_zk_tree *t, uint8_t out[32]);
+/* nodes of one level, for inspection and tests: first .. first + n of level `level` (0 = leaves, depth = root); out: n x 32 bytes.
+ * QPGPU_EINVAL for a level above the depth or a range past the level's end. */
+int qpgpu_zk_tree_read_level(const qpgpu_zk_tree *t, unsigned level, size_t first, size_t n, uint8_t *out);
+/* the paths of n leaves in one call, as qpgpu_zk_proof_from_unsorted returns them: siblings_out n x depth x 3 x 32 bytes (level major,
+ * sorted, the running hash removed at its first matching position), positions_out n x depth bytes. Indices may repeat; one that is
+ * >= the leaf count is QPGPU_EINVAL. */
+int qpgpu_zk_tree_open(const qpgpu_zk_tree *t, const uint64_t *indices, size_t n, uint8_t *siblings_out, uint8_t *positions_out);
+
 /* ---- the leaf circuit's constraints, natively ----
  * What WormholeCircuit constrains about a CircuitInputs (wormhole/circuit/src/circuit.rs:233-323 and the fragments it wires:
  * unspendable_account.rs:215-237, nullifier.rs:285-325, block_header/mod.rs:93-108, zk_merkle_proof.rs:480-626), evaluated on

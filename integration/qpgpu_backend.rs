@@ -132,11 +132,29 @@ extern "C" {
     pub fn qpgpu_leaf_circuit_hash_hint_cells(min_degree_bits: u32, inner_hasher: i32, p2_layout: *const u64, cells_out: *mut u64, cap: usize,
                                               count: *mut usize, err: *mut c_char) -> i32;
     pub fn qpgpu_leaf_hash_hints(inputs: *const c_void, values_out: *mut u64, cap: usize, count: *mut usize, err: *mut c_char) -> i32;
+    // include/qpgpu_leaf.h — the chain's 4-ary ZK Merkle tree of one block, built and kept on the device:
+    // leaves = count x 32 bytes of leaf hashes, or count QpgpuZkLeaf records with flags = QPGPU_ZK_TREE_FROM_TRANSFERS; depth 0 = the
+    // smallest valid depth. qpgpu_zk_tree_open fills zk_merkle_siblings / zk_merkle_positions of n leaves in one call
+    // (siblings_out: n x depth x 3 x 32 bytes, positions_out: n x depth bytes). err: 160 bytes. A tree is freed before its context.
+    pub fn qpgpu_zk_leaf_hash_batch(ctx: *mut QpgpuCtx, leaves: *const QpgpuZkLeaf, count: usize, out: *mut u8) -> i32;
+    pub fn qpgpu_zk_tree_build(ctx: *mut QpgpuCtx, leaves: *const c_void, count: usize, depth: u32, flags: u32, out: *mut *mut QpgpuZkTree,
+                               err: *mut c_char) -> i32;
+    pub fn qpgpu_zk_tree_free(t: *mut QpgpuZkTree);
+    pub fn qpgpu_zk_tree_depth(t: *const QpgpuZkTree) -> u32;
+    pub fn qpgpu_zk_tree_leaf_count(t: *const QpgpuZkTree) -> usize;
+    pub fn qpgpu_zk_tree_root(t: *const QpgpuZkTree, out: *mut u8) -> i32;
+    pub fn qpgpu_zk_tree_read_level(t: *const QpgpuZkTree, level: u32, first: usize, n: usize, out: *mut u8) -> i32;
+    pub fn qpgpu_zk_tree_open(t: *const QpgpuZkTree, indices: *const u64, n: usize, siblings_out: *mut u8, positions_out: *mut u8) -> i32;
     pub fn qpgpu_wrapper_circuit_build(inner_pack: *const u64, inner_words: usize, inner_cs_cap: *const u64, cap_words: usize, num_proofs: u32,
                                        num_routed_wires: u32, min_degree_bits: u32, inner_hasher: i32, flags: u32, pack_out: *mut u64, pack_cap_words: usize,
                                        pack_words: *mut usize, target_map_out: *mut u64, map_cap: usize, map_count: *mut usize, info_out: *mut u64,
                                        err: *mut c_char) -> i32;
 }
+#[repr(C)] pub struct QpgpuZkTree { _p: [u8; 0] }
+/// qpgpu_zk_leaf (include/qpgpu_leaf.h): what a leaf of the ZK tree hashes; 48 bytes
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct QpgpuZkLeaf { pub to_account: [u8; 32], pub transfer_count: u64, pub asset_id: u32, pub input_amount: u32 }
+pub const QPGPU_ZK_TREE_FROM_TRANSFERS: u32 = 1;
 /// qpgpu_circuit_config (include/qpgpu_wire.h): plonky2's CircuitConfig + FriConfig (ConstantArityBits reduction) as plain data
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct QpgpuCircuitConfig {

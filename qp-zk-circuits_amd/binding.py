@@ -68,6 +68,15 @@ def load_library():
         "qpgpu_poseidon_permute_dev": (c.c_int, [vp, u64p, c.c_size_t]),
         "qpgpu_poseidon2_hash_pad10_dev": (c.c_int, [vp, u64p, c.c_size_t, u64p, c.c_size_t, c.c_size_t, u64p]),
         "qpgpu_poseidon2_qp_params": (c.c_size_t, [u64p, c.c_size_t]),
+        # the chain's 4-ary ZK Merkle tree on the device (include/qpgpu_leaf.h; wrapped by leaf.ZkTree)
+        "qpgpu_zk_leaf_hash_batch": (c.c_int, [vp, vp, c.c_size_t, vp]),
+        "qpgpu_zk_tree_build": (c.c_int, [vp, vp, c.c_size_t, c.c_uint, c.c_uint, c.POINTER(vp), c.c_char_p]),
+        "qpgpu_zk_tree_free": (None, [vp]),
+        "qpgpu_zk_tree_depth": (c.c_uint, [vp]),
+        "qpgpu_zk_tree_leaf_count": (c.c_size_t, [vp]),
+        "qpgpu_zk_tree_root": (c.c_int, [vp, vp]),
+        "qpgpu_zk_tree_read_level": (c.c_int, [vp, c.c_uint, c.c_size_t, c.c_size_t, vp]),
+        "qpgpu_zk_tree_open": (c.c_int, [vp, vp, c.c_size_t, vp, vp]),
         "qpgpu_poseidon2_hash_pad10": (c.c_int, [u64p, c.c_size_t, u64p, c.c_size_t, u64p]),
         "qpgpu_crash_trace_armed": (c.c_int, []),
         "qpgpu_circuit_num_public_inputs": (c.c_size_t, [vp]),

@@ -1,0 +1,174 @@
+// zk_tree.cpp — C ABI of the chain's 4-ary ZK Merkle tree on the device (include/qpgpu_leaf.h): a handle that keeps every level of a
+// block's tree in HBM, its root, its levels and the Merkle paths of many leaves per call. The rules are common/src/zk_merkle.rs as
+// leaf_witness.cpp restates them on the host; the geometry and the argument checks are zk_tree.hpp's, the kernels zk_tree_kernels.hip's.
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include "../../include/qpgpu_leaf.h"
+#include "ctx.hpp"
+#include "zk_tree.hpp"
+
+static_assert(sizeof(qpgpu_zk_leaf) == zk_tree::LEAF_RECORD_BYTES, "qpgpu_zk_leaf is read by the kernel as six 64-bit words");
+static_assert(QPGPU_ZK_TREE_MAX_LEAVES == zk_tree::MAX_LEAVES && QPGPU_LEAF_MAX_DEPTH == zk_tree::MAX_DEPTH &&
+              QPGPU_ZK_TREE_FROM_TRANSFERS == zk_tree::FLAG_FROM_TRANSFERS, "qpgpu_leaf.h and zk_tree.hpp disagree");
+
+struct qpgpu_zk_tree {
+    qpgpu_ctx *ctx = nullptr;
+    zk_tree::Plan plan;
+    uint8_t *d_nodes = nullptr;      // plan.total() nodes of 32 bytes
+};
+
+namespace {
+
+// a device allocation that lives for one call
+struct Scratch {
+    void *p = nullptr;
+    ~Scratch() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+    template <class T> T *as() const { return (T *)p; }
+};
+
+int refuse(qpgpu_ctx *ctx, char *err, int code, const char *what, const char *why) {
+    char msg[QPGPU_LEAF_ERR_CAP];
+    std::snprintf(msg, sizeof msg, "%s: %s", what, why);
+    if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "%s", msg);
+    return ctx->fail(code, msg);
+}
+int hip_refuse(qpgpu_ctx *ctx, char *err, hipError_t e, const char *what) {
+    const int rc = e == hipErrorOutOfMemory ? ctx->fail(QPGPU_ENOMEM, std::string(what) + ": out of device memory") : ctx->hip_fail(e, what);
+    if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "%s", ctx->err.c_str());
+    return rc;
+}
+#define ZK_HIP(ctx, err, call, what) do { hipError_t _e = (call); if (_e != hipSuccess) return hip_refuse((ctx), (err), _e, (what)); } while (0)
+
+// device -> host, synchronous on the context's stream
+int read_nodes(qpgpu_ctx *ctx, void *dst, const void *d_src, size_t bytes, const char *what) {
+    if (bytes == 0) return QPGPU_OK;
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream), what);
+    ZK_HIP(ctx, nullptr, hipStreamSynchronize(ctx->stream), what);
+    return QPGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qpgpu_zk_leaf_hash_batch(qpgpu_ctx *ctx, const qpgpu_zk_leaf *leaves, size_t count, uint8_t *out) {
+    if (!ctx) return QPGPU_EINVAL;
+    QP_DEV(ctx);
+    static const char *const what = "zk_leaf_hash_batch";
+    if (!leaves || !out) return refuse(ctx, nullptr, QPGPU_EINVAL, what, "null argument");
+    if (count == 0 || count > zk_tree::MAX_LEAVES) return refuse(ctx, nullptr, QPGPU_EINVAL, what, "count must be 1 .. 2^24");
+    int rc = ctx->ensure_p2_app();
+    if (rc) return rc;
+    Scratch rec, dig;
+    ZK_HIP(ctx, nullptr, rec.alloc(count * zk_tree::LEAF_RECORD_BYTES), what);
+    ZK_HIP(ctx, nullptr, dig.alloc(count * zk_tree::NODE_BYTES), what);
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(rec.p, leaves, count * zk_tree::LEAF_RECORD_BYTES, hipMemcpyHostToDevice, ctx->stream), what);
+    ZK_HIP(ctx, nullptr, zk_tree_leaf_hashes(rec.as<uint8_t>(), count, dig.as<uint8_t>(), ctx->d_p2_app, ctx->stream), what);
+    return read_nodes(ctx, out, dig.p, count * zk_tree::NODE_BYTES, what);      // the sync also ends the kernel's use of both buffers
+}
+
+int qpgpu_zk_tree_build(qpgpu_ctx *ctx, const void *leaves, size_t count, unsigned depth, unsigned flags, qpgpu_zk_tree **out, char *err) {
+    if (err) err[0] = 0;
+    if (out) *out = nullptr;
+    if (!ctx) { if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "zk_tree_build: null context"); return QPGPU_EINVAL; }
+    QP_DEV(ctx);
+    static const char *const what = "zk_tree_build";
+    if (!leaves || !out) return refuse(ctx, err, QPGPU_EINVAL, what, "null argument");
+    zk_tree::Plan plan;
+    if (const char *why = zk_tree::make_plan(count, depth, flags, plan)) return refuse(ctx, err, QPGPU_EINVAL, what, why);
+    int rc = ctx->ensure_p2_app();
+    if (rc) { if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "%s", ctx->err.c_str()); return rc; }
+
+    // the nodes, and behind them the word that names a refused leaf
+    const size_t node_bytes = (size_t)plan.total() * zk_tree::NODE_BYTES;
+    Scratch nodes, records;
+    ZK_HIP(ctx, err, nodes.alloc(node_bytes + sizeof(uint32_t)), what);
+    uint8_t *d_nodes = nodes.as<uint8_t>();
+    uint32_t *d_bad = (uint32_t *)(d_nodes + node_bytes);
+    ZK_HIP(ctx, err, hipMemsetAsync(d_bad, 0xFF, sizeof(uint32_t), ctx->stream), what);
+    if (flags & zk_tree::FLAG_FROM_TRANSFERS) {
+        ZK_HIP(ctx, err, records.alloc(count * zk_tree::LEAF_RECORD_BYTES), what);
+        ZK_HIP(ctx, err, hipMemcpyAsync(records.p, leaves, count * zk_tree::LEAF_RECORD_BYTES, hipMemcpyHostToDevice, ctx->stream), what);
+        ZK_HIP(ctx, err, zk_tree_leaf_hashes(records.as<uint8_t>(), count, d_nodes, ctx->d_p2_app, ctx->stream), what);
+    } else {
+        ZK_HIP(ctx, err, hipMemcpyAsync(d_nodes, leaves, count * zk_tree::NODE_BYTES, hipMemcpyHostToDevice, ctx->stream), what);
+    }
+    ctx->prof_begin("zk_tree_levels");
+    const hipError_t e_levels = zk_tree_reduce(d_nodes, plan, d_bad, ctx->d_p2_app, ctx->stream);
+    ctx->prof_end();
+    ZK_HIP(ctx, err, e_levels, what);
+    uint32_t bad = 0;
+    ZK_HIP(ctx, err, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream), what);
+    ZK_HIP(ctx, err, hipStreamSynchronize(ctx->stream), what);
+    if (bad != 0xFFFFFFFFu) {
+        char why[96];
+        std::snprintf(why, sizeof why, "leaf %u: hash bytes are noncanonical (a limb >= p)", bad);
+        return refuse(ctx, err, QPGPU_EINVAL, what, why);
+    }
+    qpgpu_zk_tree *t = new (std::nothrow) qpgpu_zk_tree;
+    if (!t) return refuse(ctx, err, QPGPU_ENOMEM, what, "out of host memory");
+    t->ctx = ctx; t->plan = plan; t->d_nodes = d_nodes;
+    nodes.p = nullptr;               // owned by the handle from here
+    *out = t;
+    return QPGPU_OK;
+}
+
+void qpgpu_zk_tree_free(qpgpu_zk_tree *t) {
+    if (!t) return;
+    if (t->d_nodes && hipSetDevice(t->ctx->device) == hipSuccess) (void)hipFree(t->d_nodes);
+    delete t;
+}
+
+unsigned qpgpu_zk_tree_depth(const qpgpu_zk_tree *t) { return t ? t->plan.depth : 0; }
+size_t qpgpu_zk_tree_leaf_count(const qpgpu_zk_tree *t) { return t ? (size_t)t->plan.count : 0; }
+
+int qpgpu_zk_tree_read_level(const qpgpu_zk_tree *t, unsigned level, size_t first, size_t n, uint8_t *out) {
+    if (!t) return QPGPU_EINVAL;
+    qpgpu_ctx *ctx = t->ctx;
+    QP_DEV(ctx);
+    static const char *const what = "zk_tree_read_level";
+    if (const char *why = zk_tree::check_range(t->plan, level, first, n)) return refuse(ctx, nullptr, QPGPU_EINVAL, what, why);
+    if (!out && n) return refuse(ctx, nullptr, QPGPU_EINVAL, what, "null argument");
+    return read_nodes(ctx, out, t->d_nodes + (t->plan.off[level] + first) * zk_tree::NODE_BYTES, n * zk_tree::NODE_BYTES, what);
+}
+
+int qpgpu_zk_tree_root(const qpgpu_zk_tree *t, uint8_t out[32]) {
+    if (!t) return QPGPU_EINVAL;
+    if (!out) return refuse(t->ctx, nullptr, QPGPU_EINVAL, "zk_tree_root", "null argument");
+    return qpgpu_zk_tree_read_level(t, t->plan.depth, 0, 1, out);
+}
+
+int qpgpu_zk_tree_open(const qpgpu_zk_tree *t, const uint64_t *indices, size_t n, uint8_t *siblings_out, uint8_t *positions_out) {
+    if (!t) return QPGPU_EINVAL;
+    qpgpu_ctx *ctx = t->ctx;
+    QP_DEV(ctx);
+    static const char *const what = "zk_tree_open";
+    if (n == 0) return QPGPU_OK;
+    if (!indices || !siblings_out || !positions_out) return refuse(ctx, nullptr, QPGPU_EINVAL, what, "null argument");
+    uint64_t bad = 0;
+    if (const char *why = zk_tree::check_open(t->plan, indices, n, &bad)) {
+        char msg[96];
+        if (std::strcmp(why, "leaf index out of range") == 0) std::snprintf(msg, sizeof msg, "entry %llu: %s", (unsigned long long)bad, why);
+        else std::snprintf(msg, sizeof msg, "%s", why);
+        return refuse(ctx, nullptr, QPGPU_EINVAL, what, msg);
+    }
+    const size_t rows = n * t->plan.depth;
+    Scratch idx, sib, pos;
+    ZK_HIP(ctx, nullptr, idx.alloc(n * sizeof(uint64_t)), what);
+    ZK_HIP(ctx, nullptr, sib.alloc(rows * zk_tree::PATH_LEVEL_BYTES), what);
+    ZK_HIP(ctx, nullptr, pos.alloc(rows), what);
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(idx.p, indices, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream), what);
+    ctx->prof_begin("zk_tree_open");
+    const hipError_t e_open = zk_tree_open_paths(t->d_nodes, t->plan, idx.as<uint64_t>(), n, sib.as<uint8_t>(), pos.as<uint8_t>(), ctx->stream);
+    ctx->prof_end();
+    ZK_HIP(ctx, nullptr, e_open, what);
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(siblings_out, sib.p, rows * zk_tree::PATH_LEVEL_BYTES, hipMemcpyDeviceToHost, ctx->stream), what);
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(positions_out, pos.p, rows, hipMemcpyDeviceToHost, ctx->stream), what);
+    ZK_HIP(ctx, nullptr, hipStreamSynchronize(ctx->stream), what);
+    return QPGPU_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,82 @@
+// zk_tree.hpp — the chain's 4-ary ZK Merkle tree on the device: level geometry and argument checks (host only, no HIP: also compiled
+// stand-alone under the sanitizers by tools/host_checks/zk_tree_plan_check.cpp) and the launch interface of zk_tree_kernels.hip.
+//
+// Storage: one array of 32-byte nodes, level 0 (the leaves) first, every level behind the one below it. Level l holds
+// ceil(count / 4^l) nodes; a child beyond a level's end is the empty hash (32 zero bytes) and is not stored.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace zk_tree {
+
+constexpr unsigned MAX_DEPTH = 16;                       // common/src/zk_merkle.rs:65
+constexpr uint64_t MAX_LEAVES = 1ull << 24;
+constexpr unsigned FLAG_FROM_TRANSFERS = 1u, KNOWN_FLAGS = FLAG_FROM_TRANSFERS;
+constexpr size_t NODE_BYTES = 32, LEAF_RECORD_BYTES = 48, PATH_LEVEL_BYTES = 96;
+
+// passed to the kernels by value
+struct Plan {
+    uint64_t count = 0;
+    uint32_t depth = 0;
+    uint64_t size[MAX_DEPTH + 1] = {0};                  // nodes of level l, l = 0 .. depth
+    uint64_t off[MAX_DEPTH + 2] = {0};                   // first node of level l; off[depth + 1] = nodes in all
+    uint64_t total() const { return off[depth + 1]; }
+};
+
+// ceil(count / 4^level); level <= 16, so 4^level fits 33 bits and the sum cannot wrap for count <= 2^24
+inline uint64_t level_size(uint64_t count, unsigned level) { return (count + ((1ull << (2 * level)) - 1)) >> (2 * level); }
+
+// the smallest depth with 4^depth >= count, at least 1 (a path always has a level); 0 when there is none up to MAX_DEPTH
+inline unsigned min_depth(uint64_t count) {
+    for (unsigned d = 1; d <= MAX_DEPTH; d++)
+        if ((1ull << (2 * d)) >= count) return d;
+    return 0;
+}
+
+// nullptr and a filled plan, or the reason the arguments are refused. depth = 0: the smallest valid depth.
+inline const char *make_plan(uint64_t count, unsigned depth, unsigned flags, Plan &p) {
+    if (count == 0) return "count is 0";
+    if (count > MAX_LEAVES) return "count exceeds 2^24 leaves";
+    if (flags & ~KNOWN_FLAGS) return "unknown flag";
+    if (depth > MAX_DEPTH) return "depth exceeds 16";
+    const unsigned dmin = min_depth(count);
+    if (depth == 0) depth = dmin;
+    if (depth < dmin) return "depth too small: 4^depth is below count";
+    p = Plan();
+    p.count = count; p.depth = depth;
+    uint64_t at = 0;
+    for (unsigned l = 0; l <= depth; l++) { p.size[l] = level_size(count, l); p.off[l] = at; at += p.size[l]; }
+    p.off[depth + 1] = at;
+    return nullptr;
+}
+
+// nodes first .. first + n of `level`
+inline const char *check_range(const Plan &p, unsigned level, uint64_t first, uint64_t n) {
+    if (level > p.depth) return "level above the tree's depth";
+    if (first > p.size[level] || n > p.size[level] - first) return "range past the level's end";
+    return nullptr;
+}
+
+// n paths: the output sizes must not wrap size_t (n x depth x 96 bytes), and every index names a leaf. *bad: the first refused entry.
+inline const char *check_open(const Plan &p, const uint64_t *indices, uint64_t n, uint64_t *bad) {
+    if (n > (uint64_t)SIZE_MAX / (PATH_LEVEL_BYTES * MAX_DEPTH)) return "too many paths for one call";
+    for (uint64_t i = 0; i < n; i++)
+        if (indices[i] >= p.count) { if (bad) *bad = i; return "leaf index out of range"; }
+    return nullptr;
+}
+
+}  // namespace zk_tree
+
+#ifndef ZK_TREE_PLAN_ONLY   // the stand-alone host check takes the geometry alone
+#include <hip/hip_runtime_api.h>
+namespace poseidon2 { struct Params; }
+// every launcher: p2 = the device copy of qp-poseidon-core's parameter set (qpgpu_ctx::d_p2_app)
+// count records of 48 bytes (qpgpu_zk_leaf) -> count leaf hashes
+hipError_t zk_tree_leaf_hashes(const uint8_t *d_records, uint64_t count, uint8_t *d_out, const poseidon2::Params *p2, hipStream_t st);
+// levels 1 .. depth of a tree whose level 0 is in place; *d_bad_leaf (preset to 0xFFFFFFFF) receives the lowest index of a leaf with a
+// non-canonical limb
+hipError_t zk_tree_reduce(uint8_t *d_nodes, const zk_tree::Plan &plan, uint32_t *d_bad_leaf, const poseidon2::Params *p2, hipStream_t st);
+// n paths: d_siblings n x depth x 96 bytes, d_positions n x depth bytes
+hipError_t zk_tree_open_paths(const uint8_t *d_nodes, const zk_tree::Plan &plan, const uint64_t *d_indices, uint64_t n, uint8_t *d_siblings,
+                              uint8_t *d_positions, hipStream_t st);
+#endif  // ZK_TREE_PLAN_ONLY

@@ -51,6 +51,17 @@ class LeafInputs(ctypes.Structure):
         ctypes.memmove(ctypes.byref(other), ctypes.byref(self), ctypes.sizeof(LeafInputs))
         return other
 
+    def set_zk_path(self, tree, index):
+        """The Merkle path of leaf `index` of a ZkTree: zk_tree_root, zk_merkle_depth, the sorted siblings and the positions (levels past
+        the depth zeroed)."""
+        siblings, positions = tree.open([index])
+        ctypes.memset(self.zk_merkle_siblings, 0, MAX_DEPTH * 96)
+        ctypes.memset(self.zk_merkle_positions, 0, MAX_DEPTH)
+        ctypes.memmove(self.zk_merkle_siblings, siblings.ctypes.data, tree.depth * 96)
+        ctypes.memmove(self.zk_merkle_positions, positions.ctypes.data, tree.depth)
+        self.zk_merkle_depth = tree.depth
+        return self.set32("zk_tree_root", tree.root)
+
 
 def _lib():
     L = load_library()
@@ -123,6 +134,102 @@ def zk_proof_from_unsorted(leaf_hash, unsorted_siblings):
     if _lib().qpgpu_zk_proof_from_unsorted(bytes(leaf_hash), flat, depth, so, po, root, err) != 0:
         raise ValueError(err.value.decode())
     return so.raw[:96 * depth], list(po.raw[:depth]), root.raw
+
+
+# qpgpu_zk_leaf: what a leaf of the chain's ZK tree hashes
+ZK_LEAF_DTYPE = np.dtype([("to_account", np.uint8, 32), ("transfer_count", "<u8"), ("asset_id", "<u4"), ("input_amount", "<u4")])
+ZK_TREE_FROM_TRANSFERS = 1
+
+
+def _zk_transfers(transfers):
+    """[(to_account, transfer_count, asset_id, input_amount), ...] or an array of ZK_LEAF_DTYPE -> contiguous qpgpu_zk_leaf records"""
+    if isinstance(transfers, np.ndarray) and transfers.dtype == ZK_LEAF_DTYPE:
+        return np.ascontiguousarray(transfers).reshape(-1)
+    rec = np.zeros(len(transfers), dtype=ZK_LEAF_DTYPE)
+    for i, (acct, tc, asset, amount) in enumerate(transfers):
+        acct = bytes(acct)
+        assert len(acct) == 32, "to_account is 32 bytes"
+        rec[i] = (np.frombuffer(acct, dtype=np.uint8), tc, asset, amount)
+    return rec
+
+
+def _zk_hashes(leaves):
+    """bytes (count x 32), an array of that many bytes, or a list of 32-byte strings -> uint8 [count, 32]"""
+    if isinstance(leaves, (list, tuple)):
+        leaves = b"".join(bytes(h) for h in leaves)
+    a = np.frombuffer(leaves, dtype=np.uint8) if isinstance(leaves, (bytes, bytearray, memoryview)) else np.ascontiguousarray(leaves, dtype=np.uint8)
+    if a.size % 32:
+        raise ValueError("leaf hashes are 32 bytes each")
+    return np.ascontiguousarray(a).reshape(-1, 32)
+
+
+def zk_leaf_hash_batch(gpu, transfers):
+    """qpgpu_zk_leaf_hash of every transfer, on the device: uint8 [count, 32]."""
+    rec = _zk_transfers(transfers)
+    out = np.empty((rec.size, 32), dtype=np.uint8)
+    gpu._check(gpu.lib.qpgpu_zk_leaf_hash_batch(gpu.ctx, rec.ctypes.data, rec.size, out.ctypes.data))
+    return out
+
+
+class ZkTree:
+    """The chain's 4-ary ZK Merkle tree of one block, resident on the device (qpgpu_zk_tree_*): built from leaf hashes (`leaves`) or from
+    the transfers themselves (`transfers`, hashed on the device too). depth = 0 is the smallest depth that holds the leaves. Raises
+    QpGpuError(QPGPU_EINVAL) for arguments the library refuses, a leaf hash with a non-canonical limb among them."""
+
+    def __init__(self, gpu, leaves=None, transfers=None, depth=0, flags=None):
+        if (leaves is None) == (transfers is None):
+            raise ValueError("ZkTree: give the leaf hashes or the transfers")
+        data = _zk_hashes(leaves) if transfers is None else _zk_transfers(transfers)
+        count = data.shape[0]
+        if flags is None:
+            flags = 0 if transfers is None else ZK_TREE_FROM_TRANSFERS
+        self.gpu, self.h = gpu, None
+        h = ctypes.c_void_p(); err = ctypes.create_string_buffer(160)
+        rc = gpu.lib.qpgpu_zk_tree_build(gpu.ctx, data.ctypes.data if count else None, count, depth, flags, ctypes.byref(h), err)
+        if rc != 0:
+            assert not h.value, "a refused build leaves no handle"
+            raise QpGpuError(rc, err.value.decode())
+        self.h = h
+        self.depth = int(gpu.lib.qpgpu_zk_tree_depth(h))
+        self.leaf_count = int(gpu.lib.qpgpu_zk_tree_leaf_count(h))
+        self._root = None
+
+    @property
+    def root(self):
+        if self._root is None:
+            out = ctypes.create_string_buffer(32)
+            self.gpu._check(self.gpu.lib.qpgpu_zk_tree_root(self.h, out))
+            self._root = out.raw
+        return self._root
+
+    def level_size(self, level):
+        return (self.leaf_count + 4 ** level - 1) // 4 ** level
+
+    def level(self, level, first=0, n=None):
+        """Nodes first .. first + n (default: to the end) of a level, 0 = the leaves, depth = the root: uint8 [n, 32]."""
+        if n is None:
+            n = max(self.level_size(level) - first, 0) if level <= self.depth else 0
+        out = np.empty((n, 32), dtype=np.uint8)
+        self.gpu._check(self.gpu.lib.qpgpu_zk_tree_read_level(self.h, level, first, n, out.ctypes.data))
+        return out
+
+    def open(self, indices):
+        """The paths of many leaves in one call: (siblings uint8 [n, depth, 3, 32] in sorted order, positions uint8 [n, depth])."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        sib = np.empty((idx.size, self.depth, 3, 32), dtype=np.uint8); pos = np.empty((idx.size, self.depth), dtype=np.uint8)
+        self.gpu._check(self.gpu.lib.qpgpu_zk_tree_open(self.h, idx.ctypes.data, idx.size, sib.ctypes.data, pos.ctypes.data))
+        return sib, pos
+
+    def close(self):
+        if self.h:
+            self.gpu.lib.qpgpu_zk_tree_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 def dummy_circuit_inputs():
