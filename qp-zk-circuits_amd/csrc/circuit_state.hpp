@@ -38,6 +38,8 @@ struct qpgpu_circuit {
     gl::u64 *d_qcp = nullptr, *d_rowprod = nullptr, *d_z = nullptr, *d_zs_vals = nullptr;
     gl::u64 *d_small = nullptr;          // per proof: betas, gammas, beta_k_is, alpha pows, pi hash
     size_t small_words = 0;              // words of that table per proof
+    gl::u64 *d_fold = nullptr;           // per proof: the folded hash gates' weight tables (quotient_fold.hpp); nullptr: the circuit runs them round by round
+    size_t fold_words = 0;               // words of them per proof
     gl::e2 *d_points = nullptr, *d_open = nullptr;
     FriParams fri;
     FriWork fri_work;                // s8..s11 workspace, one allocation

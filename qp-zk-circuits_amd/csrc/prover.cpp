@@ -217,6 +217,16 @@ int qpgpu_circuit_load_batch(qpgpu_ctx *ctx, const uint64_t *pack_words, size_t 
     const size_t nterms = nch + nch * p.num_chunks() + p.num_gate_constraints;
     c->small_words = (2 * nch + nch * R + nch * nterms + 4 + 3) & ~(size_t)3;
     CK(c->alloc(&c->d_small, (size_t)B * c->small_words));
+    {
+        // The hash gates' quotient kernels run in the folded form (quotient_fold.hpp). QPGPU_QUOTIENT_FOLD=0, read here and nowhere
+        // else, keeps the round-by-round form for this circuit: the A/B measurement and the parity test.
+        const uint32_t n_hash = pk_count_hash_gates(gd.data(), (uint32_t)gd.size());
+        const char *e = getenv("QPGPU_QUOTIENT_FOLD");
+        if (n_hash > 0 && n_hash <= qfold::MAX_GATES && !(e && *e == '0')) {
+            c->fold_words = (size_t)n_hash * nch * qfold::WORDS;
+            CK(c->alloc(&c->d_fold, (size_t)B * c->fold_words));
+        }
+    }
     const size_t n_open = p.num_cs_cols() + p.num_wires + p.num_zs_pp_cols() + p.num_quotient_cols();
     CK(c->alloc(&c->d_points, (size_t)B * 2));
     CK(c->alloc(&c->d_open, (size_t)B * (n_open + nch), true));
@@ -379,6 +389,12 @@ static int prove_batch_impl(qpgpu_circuit *c, uint32_t nb, const u64 *d_wires, c
         std::memcpy(ap + (size_t)nch * nterms, pih[b].data(), 32);
     }
     QP_TRY(c->stage.put_rows(ctx, d_apow, SW, small.data() + 2 * nch + (size_t)nch * R, SW, (size_t)nch * nterms + 4, nb));
+    // the folded hash gates' weights for this batch's alphas: one small launch, read by the gate kernels of the witness check and of s6
+    QuotientArgs qa{};
+    qa.alpha_pows = d_apow; qa.poseidon_rc = c->d_poseidon_rc; qa.p2_gate = ctx->d_p2_app; qa.p2_layout = p.p2_layout;
+    qa.nch = nch; qa.nchunks = nchunks; qa.nterms = (uint32_t)nterms; qa.num_gates = (uint32_t)p.gates.size(); qa.batch = nb; qa.ps_small = SW;
+    qa.fold = c->d_fold; qa.ps_fold = c->fold_words;
+    QP_HIP(ctx, pk_quotient_fold_sweep(qa, c->h_gates.data(), st));
     if (c->check_witness) {
         // the analogue of plonky2's debug assertions: filtered gate constraints must vanish on every trace row and the
         // permutation product must close; alpha-weighted sums are zero iff every constraint is (alpha is a transcript challenge)
@@ -390,6 +406,7 @@ static int prove_batch_impl(qpgpu_circuit *c, uint32_t nb, const u64 *d_wires, c
         ta.chunk = (uint32_t)p.quotient_degree_factor; ta.nchunks = nchunks; ta.sig0 = (uint32_t)sig0;
         ta.num_selectors = (uint32_t)p.num_selectors; ta.num_gates = (uint32_t)p.gates.size(); ta.nterms = (uint32_t)nterms;
         ta.batch = nb; ta.ps_wires = NW * n; ta.ps_zs = 0; ta.ps_small = SW; ta.ps_acc = (u64)nch * n; ta.ps_out = (u64)nch * n;
+        ta.fold = c->d_fold; ta.ps_fold = c->fold_words;
         QP_HIP(ctx, hipMemsetAsync(c->d_qacc, 0, (size_t)nb * nch * n * 8, st));
         std::vector<u64> init(2 * (size_t)nb);
         for (uint32_t b = 0; b < nb; b++) { init[2 * b] = ~0ull; init[2 * b + 1] = 0; }
@@ -405,7 +422,6 @@ static int prove_batch_impl(qpgpu_circuit *c, uint32_t nb, const u64 *d_wires, c
         }
     }
     ctx->prof_begin("prove_quotient");
-    QuotientArgs qa{};
     qa.wires = c->wires.lde; qa.cs = c->cs.lde; qa.zs_pp = c->zs.lde; qa.x_coset = c->d_x_coset; qa.l0_coset = c->d_l0_coset;
     qa.zh_inv = c->d_zh_inv; qa.alpha_pows = d_apow; qa.beta_k_is = d_bk; qa.betas = d_betas; qa.gammas = d_gammas; qa.pi_hash = d_pih;
     qa.gates = c->d_gates; qa.acc = c->d_qacc; qa.poseidon_rc = c->d_poseidon_rc; qa.poseidon_fast = c->d_poseidon_fast; qa.out = c->quot.coeffs;

@@ -123,6 +123,7 @@ __device__ __forceinline__ void quotient_select_proof(QuotientArgs &a) {
     a.wires += pr * a.ps_wires; a.zs_pp += pr * a.ps_zs;
     a.alpha_pows += pr * a.ps_small; a.beta_k_is += pr * a.ps_small; a.betas += pr * a.ps_small; a.gammas += pr * a.ps_small; a.pi_hash += pr * a.ps_small;
     a.acc += pr * a.ps_acc; a.out += pr * a.ps_out;
+    if (a.fold) a.fold += pr * a.ps_fold;
 }
 
 // (1) L_0(x)(Z(x) - 1) and the partial-product checks
@@ -218,15 +219,36 @@ __global__ void __launch_bounds__(256) quotient_gates_kernel(QuotientArgs a, u32
 #pragma unroll
             for (int c = 0; c < NCH; c++) gl::acc_mul(sum[c], cst, ap[(u64)c * a.nterms + q]);
         };
+        // The leaf circuit's gate types run in fixed-size chunks: a chunk's wire loads are issued together, ahead of its arithmetic
+        // (every load of a column is strided by S and independent of the others), and the chunk bodies unroll at compile time.
         if (g.type == 1) {            // ConstantGate: const_i - wire_i
-            for (u32 q = 0; q < g.param0; q++) emit(q, gl::sub(consts_base[(u64)q * S], a.wires[(u64)q * S + j]));
+            u32 q = 0;
+#pragma unroll 1
+            for (; q + 2 <= g.param0; q += 2) {
+                const u64 k0 = consts_base[(u64)q * S], k1 = consts_base[(u64)(q + 1) * S], w0 = a.wires[(u64)q * S + j], w1 = a.wires[(u64)(q + 1) * S + j];
+                emit(q, gl::sub(k0, w0)); emit(q + 1, gl::sub(k1, w1));
+            }
+            for (; q < g.param0; q++) emit(q, gl::sub(consts_base[(u64)q * S], a.wires[(u64)q * S + j]));
         } else if (g.type == 2) {     // PublicInputGate: wire_i - pi_hash_i
-            for (u32 q = 0; q < 4; q++) emit(q, gl::sub(a.wires[(u64)q * S + j], a.pi_hash[q]));
-        } else if (g.type == 3) {     // ArithmeticGate: out - (c0 m0 m1 + c1 addend)
+            u64 v[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) v[q] = a.wires[(u64)q * S + j];
+#pragma unroll
+            for (int q = 0; q < 4; q++) emit(q, gl::sub(v[q], a.pi_hash[q]));
+        } else if (g.type == 3) {     // ArithmeticGate: out - (c0 m0 m1 + c1 addend), four operations per chunk
             const u64 c0 = consts_base[0], c1 = consts_base[S];
-            for (u32 q = 0; q < g.param0; q++) {
-                const u64 m0 = a.wires[(u64)(4 * q) * S + j], m1 = a.wires[(u64)(4 * q + 1) * S + j];
-                const u64 ad = a.wires[(u64)(4 * q + 2) * S + j], out = a.wires[(u64)(4 * q + 3) * S + j];
+            const u64 *w = a.wires + j;
+            u32 q = 0;
+#pragma unroll 1
+            for (; q + 4 <= g.param0; q += 4) {
+                u64 v[16];
+#pragma unroll
+                for (int i = 0; i < 16; i++) v[i] = w[(u64)(4 * q + i) * S];
+#pragma unroll
+                for (int i = 0; i < 4; i++) emit(q + i, gl::sub(v[4 * i + 3], gl::add(gl::mul(gl::mul(v[4 * i], v[4 * i + 1]), c0), gl::mul(v[4 * i + 2], c1))));
+            }
+            for (; q < g.param0; q++) {
+                const u64 m0 = w[(u64)(4 * q) * S], m1 = w[(u64)(4 * q + 1) * S], ad = w[(u64)(4 * q + 2) * S], out = w[(u64)(4 * q + 3) * S];
                 emit(q, gl::sub(out, gl::add(gl::mul(gl::mul(m0, m1), c0), gl::mul(ad, c1))));
             }
         } else if (g.type == 6) {     // ArithmeticExtensionGate<2>: out - (c0 m0 m1 + c1 addend) over F[x]/(x^2-7)
@@ -331,14 +353,29 @@ __global__ void __launch_bounds__(256) quotient_gates_kernel(QuotientArgs a, u32
             }
             const e2 val = ld(s_ev);
             emit(q_out++, gl::sub(val.a, ev.a)); emit(q_out++, gl::sub(val.b, ev.b));
-        } else if (g.type == 5) {     // BaseSumGate<2>: sum - sum_i 2^i limb_i, and limb_i (limb_i - 1)
+        } else if (g.type == 5) {     // BaseSumGate<2>: sum - sum_i 2^i limb_i, and limb_i (limb_i - 1); every limb is loaded once,
+            // from the top limb down (Horner), eight per chunk
+            const u64 *w = a.wires + S + j;      // limb 0
             u64 s2 = 0;
-            for (u32 q = g.param0; q-- > 0;) s2 = gl::add(gl::add(s2, s2), a.wires[(u64)(1 + q) * S + j]);
-            emit(0, gl::sub(s2, a.wires[j]));
-            for (u32 q = 0; q < g.param0; q++) {
-                const u64 limb = a.wires[(u64)(1 + q) * S + j];
+            u32 q = g.param0;
+            for (; q & 7; ) {
+                const u64 limb = w[(u64)--q * S];
+                s2 = gl::add(gl::add(s2, s2), limb);
                 emit(1 + q, gl::mul(limb, gl::sub(limb, 1)));
             }
+#pragma unroll 1
+            while (q) {
+                q -= 8;
+                u64 v[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) v[i] = w[(u64)(q + i) * S];
+#pragma unroll
+                for (int i = 7; i >= 0; i--) {
+                    s2 = gl::add(gl::add(s2, s2), v[i]);
+                    emit(1 + q + i, gl::mul(v[i], gl::sub(v[i], 1)));
+                }
+            }
+            emit(0, gl::sub(s2, a.wires[j]));
         }
 #pragma unroll
         for (int c = 0; c < NCH; c++) acc[c] = gl::add(acc[c], gl::mul(f, gl::acc_reduce(sum[c])));
@@ -356,9 +393,9 @@ __global__ void __launch_bounds__(256) quotient_gates_kernel(QuotientArgs a, u32
 
 // (3) PoseidonGate (plonky2::gates::poseidon) at one point: wires 0..11 input, 12..23 output, 24 swap, 25..28 delta,
 // 29..64 / 65..86 / 87..134 S-box inputs of the full / partial / full rounds; 123 constraints, each weighted by
-// alpha_c^(t0+q) on the fly.
+// alpha_c^(t0+q) on the fly. This is the round-by-round form (QuotientArgs::fold == nullptr); the folded form follows below.
 template <int NCH>
-__global__ void __launch_bounds__(256) quotient_poseidon_kernel(QuotientArgs a, u32 gi, u32 t0, int finalize) {
+__global__ void __launch_bounds__(256) quotient_poseidon_rounds_kernel(QuotientArgs a, u32 gi, u32 t0, int finalize) {
     const u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x;
     if (j >= a.q_n) return;
     quotient_select_proof(a);
@@ -442,7 +479,7 @@ __global__ void __launch_bounds__(256) quotient_poseidon_kernel(QuotientArgs a, 
 // wires, and the 12 outputs: 123 constraints of degree 7 with the default layout. The external layers use the multiplication-free
 // form of qp-poseidon-core's block circ(2, 3, 1, 1) (poseidon2::ext_layer_qp).
 template <int NCH>
-__global__ void __launch_bounds__(256) quotient_poseidon2_kernel(QuotientArgs a, u32 gi, u32 t0, int finalize) {
+__global__ void __launch_bounds__(256) quotient_poseidon2_rounds_kernel(QuotientArgs a, u32 gi, u32 t0, int finalize) {
     const u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x;
     if (j >= a.q_n) return;
     quotient_select_proof(a);
@@ -518,6 +555,146 @@ __global__ void __launch_bounds__(256) quotient_poseidon2_kernel(QuotientArgs a,
 #pragma unroll
         for (int c = 0; c < NCH; c++) a.acc[(u64)c * S + j] = gl::add(a.acc[(u64)c * S + j], gl::mul(f, sum[c]));
     }
+}
+
+// ---- (3'), (4') the hash gates with their linear layers folded into the alpha weights (quotient_fold.hpp) ----
+// x^7 of N independent values as rare-fold product groups (gl::mul_group: 19 instead of 22 vector instructions per product, one
+// scalar branch per group and stage). These launches are large (q_n x batch threads), the regime that form is for.
+template <int N>
+__device__ __forceinline__ void sbox7_group(u64 (&x)[N]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    u64 x2[N], x3[N], x4[N];
+    gl::mul_group(x2, x, x);
+    gl::mul_group(x4, x2, x2);
+    gl::mul_group(x3, x, x2);
+    gl::mul_group(x, x3, x4);
+#else
+    for (int i = 0; i < N; i++) x[i] = poseidon::sbox7(x[i]);   // host pass of the unit: parsed, never called
+#endif
+}
+// Wires per product group (it divides 12; 106 and 118 wires leave the same tail). The group's temporaries set the kernels' register
+// count: 12 per group (a full round's worth) needs 134 VGPRs, 6 needs 98, 4 needs 86-88 and runs five waves per SIMD. Measured per
+// lockstep batch of 32 at 2^13 rows, PoseidonGate / Poseidon2 gate: 514 / 522 us, 476 / 481 us, 443 / 440 us
+// (profiles/quotient_fold_notes.txt).
+#ifndef FOLD_GROUP
+#define FOLD_GROUP 4
+#endif
+constexpr int FOLD_TAIL = 106 % FOLD_GROUP, FOLD_HEAD = FOLD_GROUP;   // FOLD_GROUP divides 12
+static_assert(12 % FOLD_GROUP == 0, "the head's twelve S-boxes go in whole groups");
+static_assert(118 % FOLD_GROUP == FOLD_TAIL && FOLD_TAIL > 0, "the tail group serves both wire counts");
+// N target wires from number j0 on: each adds wire * (-alpha^q) and wire^7 * omega. Their S-box inputs are all wires, hence
+// independent of one another also across partial rounds: one product group per stage for the N of them.
+template <int NCH, int N>
+__device__ __forceinline__ void fold_targets(const QuotientArgs &a, const qfold::Schedule &s, const u64 *F, u64 j, u32 j0, gl::Acc192 (&wsum)[NCH]) {
+    u64 v[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) v[i] = a.wires[(u64)qfold::target_wire(s, j0 + i) * a.lde_n + j];
+#pragma unroll
+    for (int i = 0; i < N; i++)
+#pragma unroll
+        for (int c = 0; c < NCH; c++) gl::acc_mul(wsum[c], v[i], F[c * qfold::WORDS + qfold::T_NALPHA + j0 + i]);
+    sbox7_group(v);
+#pragma unroll
+    for (int i = 0; i < N; i++)
+#pragma unroll
+        for (int c = 0; c < NCH; c++) gl::acc_mul(wsum[c], v[i], F[c * qfold::WORDS + qfold::T_OMEGA + j0 + i]);
+}
+// One point of one hash gate. Unchanged against the round-by-round kernels: the swap / delta constraints, gate_filter, the
+// finalize path and the proof selection. Acc192::top counts the carries out of 128 bits of at most 5 + 12 + 2 * 118 + 12 = 265
+// products below 2^128: it stays below 2^9 of its 32 bits.
+template <int NCH>
+__device__ __forceinline__ void hash_gate_folded(QuotientArgs &a, const qfold::Schedule &s, u32 gi, u32 t0, u32 slot, int finalize) {
+    const u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (j >= a.q_n) return;
+    quotient_select_proof(a);
+    const u64 S = a.lde_n;
+    const u64 *ap = a.alpha_pows + t0;
+    const u64 *F = a.fold + (u64)slot * NCH * qfold::WORDS;
+    const qfold::Consts K = {a.poseidon_rc, a.p2_gate};
+    auto W = [&](u32 i) -> u64 { return a.wires[(u64)i * S + j]; };
+    gl::Acc192 wsum[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) wsum[c] = gl::acc_zero();
+    u64 st[12];
+    if (s.w_swap != qfold::NO_SWAP) {
+        const u64 swap = W(s.w_swap), sb = gl::mul(swap, gl::sub(swap, 1));
+#pragma unroll
+        for (int c = 0; c < NCH; c++) gl::acc_mul(wsum[c], sb, ap[(u64)c * a.nterms]);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const u64 lhs = W(s.w_input + i), rhs = W(s.w_input + 4 + i), delta = W(s.w_delta + i);
+            const u64 d = gl::sub(gl::mul(swap, gl::sub(rhs, lhs)), delta);
+#pragma unroll
+            for (int c = 0; c < NCH; c++) gl::acc_mul(wsum[c], d, ap[(u64)c * a.nterms + 1 + i]);
+            st[i] = gl::add(lhs, delta); st[i + 4] = gl::sub(rhs, delta);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++) st[i] = W(s.w_input + i);
+    }
+#pragma unroll
+    for (int i = 8; i < 12; i++) st[i] = W(s.w_input + i);
+    qfold::head_inputs(s, K, st);
+    if (s.head == qfold::HEAD_SBOX) {      // in groups of FOLD_GROUP like the target wires: the group size sets the kernel's register count
+#pragma unroll
+        for (int g0 = 0; g0 < 12; g0 += FOLD_HEAD) {
+            u64 h[FOLD_HEAD];
+#pragma unroll
+            for (int i = 0; i < FOLD_HEAD; i++) h[i] = st[g0 + i];
+            sbox7_group(h);
+#pragma unroll
+            for (int i = 0; i < FOLD_HEAD; i++) st[g0 + i] = h[i];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 12; i++)
+#pragma unroll
+        for (int c = 0; c < NCH; c++) gl::acc_mul(wsum[c], st[i], F[c * qfold::WORDS + qfold::T_HEAD + i]);
+    u32 j0 = 0;
+#pragma unroll 1
+    for (; j0 + FOLD_GROUP <= s.nw; j0 += FOLD_GROUP) fold_targets<NCH, FOLD_GROUP>(a, s, F, j, j0, wsum);
+    if (s.nw - j0 == FOLD_TAIL) { fold_targets<NCH, FOLD_TAIL>(a, s, F, j, j0, wsum); j0 += FOLD_TAIL; }   // 106 and 118 both leave this many
+#pragma unroll 1
+    for (; j0 < s.nw; j0++) fold_targets<NCH, 1>(a, s, F, j, j0, wsum);
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        const u64 o = W(s.w_output + i);
+#pragma unroll
+        for (int c = 0; c < NCH; c++) gl::acc_mul(wsum[c], o, F[c * qfold::WORDS + qfold::T_NALPHA + s.nw + i]);
+    }
+    const u64 f = gate_filter(a, gi, a.cs[(u64)a.gates[gi].selector_index * S + j]);
+    u64 sum[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) sum[c] = gl::add(gl::acc_reduce(wsum[c]), F[c * qfold::WORDS + qfold::T_KAPPA]);
+    if (finalize) {
+        const u64 i = brev32((u32)j, a.log_lde);
+        const u64 zi = a.zh_inv[i & (a.rate - 1)];
+#pragma unroll
+        for (int c = 0; c < NCH; c++) a.out[(u64)c * a.q_n + (i >> a.q_shift)] = gl::canon(gl::mul(gl::add(a.acc[(u64)c * S + j], gl::mul(f, sum[c])), zi));
+    } else {
+#pragma unroll
+        for (int c = 0; c < NCH; c++) a.acc[(u64)c * S + j] = gl::add(a.acc[(u64)c * S + j], gl::mul(f, sum[c]));
+    }
+}
+template <int NCH>
+__global__ void __launch_bounds__(256) quotient_poseidon_kernel(QuotientArgs a, qfold::Schedule s, u32 gi, u32 t0, u32 slot, int finalize) {
+    s.kind = GATE_POSEIDON; s.head = qfold::HEAD_SBOX;    // known here: the other gate's branches fold away
+    hash_gate_folded<NCH>(a, s, gi, t0, slot, finalize);
+}
+template <int NCH>
+__global__ void __launch_bounds__(256) quotient_poseidon2_kernel(QuotientArgs a, qfold::Schedule s, u32 gi, u32 t0, u32 slot, int finalize) {
+    s.kind = GATE_POSEIDON2;
+    hash_gate_folded<NCH>(a, s, gi, t0, slot, finalize);
+}
+// the backward walk: block (hash gate, challenge, proof), one wave; 48 of its lanes share a step's 144 products
+__global__ void __launch_bounds__(64) quotient_fold_sweep_kernel(FoldSweepArgs fa) {
+    __shared__ qfold::Scratch scratch;
+    const u32 slot = blockIdx.x, c = blockIdx.y;
+    const u64 pr = blockIdx.z;
+    const u64 *ap = fa.alpha_pows + pr * fa.ps_small + (u64)c * fa.nterms + fa.t0;
+    u64 *table = fa.fold + pr * fa.ps_fold + ((u64)slot * fa.nch + c) * qfold::WORDS;
+    const qfold::Consts K = {fa.poseidon_rc, fa.p2_gate};
+    qfold::sweep(fa.sched[slot], K, ap, scratch, table, threadIdx.x, blockDim.x, [] { __syncthreads(); });
 }
 
 // Witness check on the trace rows (optional): acc holds the alpha-weighted gate-constraint sums per row (the gate kernels
@@ -822,14 +999,50 @@ static bool wide_random_access(const QuotientArgs &a, const GateDev *host_gates)
     for (u32 i = 0; i < a.num_gates; i++) if (host_gates[i].type == 10 && host_gates[i].param0 > 4) return true;
     return false;
 }
+static bool is_hash_gate(const GateDev &g) { return (g.type == GATE_POSEIDON || g.type == GATE_POSEIDON2) && g.num_constraints; }
+uint32_t pk_count_hash_gates(const GateDev *host_gates, uint32_t num_gates) {
+    uint32_t n = 0;
+    for (u32 i = 0; i < num_gates; i++) if (is_hash_gate(host_gates[i])) n++;
+    return n;
+}
+static qfold::Schedule hash_gate_schedule(const QuotientArgs &a, const GateDev &g) {
+    return g.type == GATE_POSEIDON ? qfold::poseidon_schedule() : qfold::poseidon2_schedule(a.p2_layout);
+}
+// hash gate number `slot` (gate gi of the list): the one call site of the folded and the round-by-round form
+template <int NCH>
+static void hash_gate_launch(const QuotientArgs &a, const GateDev *host_gates, u32 gi, u32 t0, u32 slot, int finalize, dim3 g, dim3 b, hipStream_t st) {
+    const bool p1 = host_gates[gi].type == GATE_POSEIDON;
+    if (a.fold) {
+        const qfold::Schedule s = hash_gate_schedule(a, host_gates[gi]);
+        if (p1) hipLaunchKernelGGL((quotient_poseidon_kernel<NCH>), g, b, 0, st, a, s, gi, t0, slot, finalize);
+        else hipLaunchKernelGGL((quotient_poseidon2_kernel<NCH>), g, b, 0, st, a, s, gi, t0, slot, finalize);
+    } else {
+        if (p1) hipLaunchKernelGGL((quotient_poseidon_rounds_kernel<NCH>), g, b, 0, st, a, gi, t0, finalize);
+        else hipLaunchKernelGGL((quotient_poseidon2_rounds_kernel<NCH>), g, b, 0, st, a, gi, t0, finalize);
+    }
+}
+hipError_t pk_quotient_fold_sweep(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st) {
+    if (!a.fold || a.batch == 0) return hipSuccess;
+    FoldSweepArgs fa{};
+    for (u32 i = 0; i < a.num_gates; i++)
+        if (is_hash_gate(host_gates[i])) {
+            if (fa.ngates == qfold::MAX_GATES) return hipErrorInvalidValue;
+            fa.sched[fa.ngates++] = hash_gate_schedule(a, host_gates[i]);
+        }
+    if (fa.ngates == 0) return hipSuccess;
+    fa.nch = a.nch; fa.nterms = a.nterms; fa.t0 = a.nch + a.nch * a.nchunks; fa.batch = a.batch;
+    fa.alpha_pows = a.alpha_pows; fa.poseidon_rc = a.poseidon_rc; fa.p2_gate = a.p2_gate;
+    fa.fold = const_cast<u64 *>(a.fold); fa.ps_small = a.ps_small; fa.ps_fold = a.ps_fold;
+    hipLaunchKernelGGL(quotient_fold_sweep_kernel, dim3(fa.ngates, fa.nch, fa.batch), dim3(64), 0, st, fa);
+    return hipGetLastError();
+}
 template <int NCH>
 static hipError_t quotient_launch(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st) {
     dim3 b(256), g((unsigned)((a.q_n + 255) / 256), 1, a.batch);
     const u32 t0 = a.nch + a.nch * a.nchunks;
     // Poseidon gates (heavy, one launch each) come last; the final launch also applies 1/Z_H and stores
-    auto is_hash_gate = [&](u32 i) { return (host_gates[i].type == 4 || host_gates[i].type == 14) && host_gates[i].num_constraints; };
-    int n_pos = 0;
-    for (u32 i = 0; i < a.num_gates; i++) if (is_hash_gate(i)) n_pos++;
+    auto is_hash_gate = [&](u32 i) { return ::is_hash_gate(host_gates[i]); };
+    const int n_pos = (int)pk_count_hash_gates(host_gates, a.num_gates);
     hipLaunchKernelGGL((quotient_perm_kernel<NCH>), g, b, 0, st, a);
     if (wide_random_access(a, host_gates)) hipLaunchKernelGGL((quotient_gates_kernel<NCH, true>), g, b, 0, st, a, t0, n_pos == 0 ? 1 : 0);
     else hipLaunchKernelGGL((quotient_gates_kernel<NCH, false>), g, b, 0, st, a, t0, n_pos == 0 ? 1 : 0);
@@ -837,8 +1050,7 @@ static hipError_t quotient_launch(const QuotientArgs &a, const GateDev *host_gat
     for (u32 i = 0; i < a.num_gates; i++)
         if (is_hash_gate(i)) {
             seen++;
-            if (host_gates[i].type == 4) hipLaunchKernelGGL((quotient_poseidon_kernel<NCH>), g, b, 0, st, a, i, t0, seen == n_pos ? 1 : 0);
-            else hipLaunchKernelGGL((quotient_poseidon2_kernel<NCH>), g, b, 0, st, a, i, t0, seen == n_pos ? 1 : 0);
+            hash_gate_launch<NCH>(a, host_gates, i, t0, seen - 1, seen == n_pos ? 1 : 0, g, b, st);
         }
     return hipGetLastError();
 }
@@ -849,10 +1061,9 @@ static hipError_t gates_only_launch(const QuotientArgs &a, const GateDev *host_g
     const u32 t0 = a.nch + a.nch * a.nchunks;
     if (wide_random_access(a, host_gates)) hipLaunchKernelGGL((quotient_gates_kernel<NCH, true>), g, b, 0, st, a, t0, 0);
     else hipLaunchKernelGGL((quotient_gates_kernel<NCH, false>), g, b, 0, st, a, t0, 0);
-    for (u32 i = 0; i < a.num_gates; i++) {
-        if (host_gates[i].type == 4 && host_gates[i].num_constraints) hipLaunchKernelGGL((quotient_poseidon_kernel<NCH>), g, b, 0, st, a, i, t0, 0);
-        if (host_gates[i].type == 14 && host_gates[i].num_constraints) hipLaunchKernelGGL((quotient_poseidon2_kernel<NCH>), g, b, 0, st, a, i, t0, 0);
-    }
+    u32 slot = 0;
+    for (u32 i = 0; i < a.num_gates; i++)
+        if (is_hash_gate(host_gates[i])) hash_gate_launch<NCH>(a, host_gates, i, t0, slot++, 0, g, b, st);
     return hipGetLastError();
 }
 hipError_t pk_gate_sums(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st) {

@@ -8,8 +8,7 @@
 #include <stdint.h>
 #include "circuit.hpp"
 #include "gl64.hpp"
-
-namespace poseidon2 { struct Params; }
+#include "quotient_fold.hpp"
 
 struct GateDev { uint32_t type, param0, param1, selector_index, group_start, group_end, num_constraints, param2; };
 
@@ -46,6 +45,21 @@ struct QuotientArgs {
     uint32_t log_lde, rate, nch, num_routed, chunk, nchunks, sig0, num_selectors, num_gates, nterms;
     uint32_t batch;
     uint64_t ps_wires, ps_zs, ps_small, ps_acc, ps_out;   // per-proof strides (alpha_pows, beta_k_is, betas, gammas, pi_hash share ps_small)
+    // folded hash gates (quotient_fold.hpp): [hash gate in gate-list order][nch][qfold::WORDS] per proof, written by pk_quotient_fold_sweep
+    // for this batch's alphas; nullptr = the hash-gate kernels walk the rounds with their linear layers (the form before the fold)
+    const uint64_t *fold;
+    uint64_t ps_fold;
+};
+
+// the backward walk that fills QuotientArgs::fold: one workgroup per (hash gate, challenge, proof)
+struct FoldSweepArgs {
+    qfold::Schedule sched[qfold::MAX_GATES];
+    uint32_t ngates, nch, nterms, t0, batch;
+    const uint64_t *alpha_pows;           // [nch][nterms] per proof, stride ps_small
+    const uint64_t *poseidon_rc;
+    const poseidon2::Params *p2_gate;
+    uint64_t *fold;
+    uint64_t ps_small, ps_fold;
 };
 
 struct ReduceArgs {
@@ -73,6 +87,10 @@ hipError_t pk_pp_rows(const PpArgs &a, hipStream_t st);
 hipError_t pk_pp_scan(const uint64_t *rowprod, uint64_t *z, uint64_t n, uint32_t nch_total, hipStream_t st);   // [batch * nch][n], contiguous
 hipError_t pk_pp_finish(const PpArgs &a, const uint64_t *z, uint64_t *zs_pp, uint64_t ps_z, uint64_t ps_zs, hipStream_t st);
 hipError_t pk_quotient(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st);
+// hash gates of the list that carry constraints; more than qfold::MAX_GATES: the circuit runs without the fold
+uint32_t pk_count_hash_gates(const GateDev *host_gates, uint32_t num_gates);
+// fills a.fold for the batch from its alpha powers (run before pk_quotient / pk_gate_sums whenever QuotientArgs::fold is set)
+hipError_t pk_quotient_fold_sweep(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st);
 hipError_t pk_gate_sums(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st);
 // result: [batch][2]
 hipError_t pk_witness_check(const uint64_t *acc, uint64_t n, uint32_t nch, const uint64_t *z, const uint64_t *rowprod, uint64_t *result, uint32_t batch, hipStream_t st);
