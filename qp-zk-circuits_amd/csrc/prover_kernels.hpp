@@ -1,4 +1,4 @@
-// prover_kernels.hpp — argument blocks and launchers of prover_kernels.hip.
+// prover_kernels.hpp — argument blocks and launchers of prover_kernels.hip (stages s5, s7..s11; s6: quotient_kernels.hpp).
 //
 // Lockstep batches: every launcher takes `batch` proofs of one circuit at once (grid.z or a folded leading dimension =
 // proof index). A per-proof buffer X of one proof's size |X| is laid out as [batch][|X|]; the `ps_*` fields are those
@@ -8,9 +8,7 @@
 #include <stdint.h>
 #include "circuit.hpp"
 #include "gl64.hpp"
-#include "quotient_fold.hpp"
-
-struct GateDev { uint32_t type, param0, param1, selector_index, group_start, group_end, num_constraints, param2; };
+#include "quotient_kernels.hpp"   // stage s6 has a unit of its own; its callers include this header
 
 struct PpArgs {
     const uint64_t *wires;      // [num_wires][n] values, natural order
@@ -24,42 +22,6 @@ struct PpArgs {
     uint32_t num_routed, chunk, nchunks, nch;
     uint32_t batch;
     uint64_t ps_wires, ps_small, ps_qcp, ps_rowprod;   // per-proof strides: wires; betas/gammas/beta_k_is; qcp; rowprod
-};
-
-struct QuotientArgs {
-    const uint64_t *wires, *cs, *zs_pp;   // LDE, column-major, leaf order, stride lde_n
-    const uint64_t *x_coset, *l0_coset;   // [lde_n] slot order
-    const uint64_t *zh_inv;               // [rate]
-    const uint64_t *alpha_pows;           // [nch][nterms]
-    const uint64_t *beta_k_is, *betas, *gammas, *pi_hash;
-    const GateDev *gates;
-    const uint64_t *poseidon_rc;          // 360 round constants (PoseidonGate)
-    const uint64_t *poseidon_fast;        // FAST_PARTIAL_* tables, poseidon::FP_WORDS entries
-    const poseidon2::Params *p2_gate;     // constants of the Poseidon2 gate (qp-poseidon-core's set), device block
-    P2GateLayout p2_layout;               // its wire layout (circuit.hpp)
-    uint64_t *acc;                        // [nch][lde_n] slot order: running alpha-weighted sums between the s6 kernels
-    uint64_t *out;                        // [nch][lde_n] natural order
-    uint64_t lde_n;                       // column stride of the LDE batches (slots)
-    uint64_t q_n;                         // points the quotient is evaluated on: the first q_n slots = the coset g<w_{n*qdf}>
-    uint32_t q_shift;                     // rate_bits - log2(quotient_degree_factor): natural LDE index >> q_shift = quotient index
-    uint32_t log_lde, rate, nch, num_routed, chunk, nchunks, sig0, num_selectors, num_gates, nterms;
-    uint32_t batch;
-    uint64_t ps_wires, ps_zs, ps_small, ps_acc, ps_out;   // per-proof strides (alpha_pows, beta_k_is, betas, gammas, pi_hash share ps_small)
-    // folded hash gates (quotient_fold.hpp): [hash gate in gate-list order][nch][qfold::WORDS] per proof, written by pk_quotient_fold_sweep
-    // for this batch's alphas; nullptr = the hash-gate kernels walk the rounds with their linear layers (the form before the fold)
-    const uint64_t *fold;
-    uint64_t ps_fold;
-};
-
-// the backward walk that fills QuotientArgs::fold: one workgroup per (hash gate, challenge, proof)
-struct FoldSweepArgs {
-    qfold::Schedule sched[qfold::MAX_GATES];
-    uint32_t ngates, nch, nterms, t0, batch;
-    const uint64_t *alpha_pows;           // [nch][nterms] per proof, stride ps_small
-    const uint64_t *poseidon_rc;
-    const poseidon2::Params *p2_gate;
-    uint64_t *fold;
-    uint64_t ps_small, ps_fold;
 };
 
 struct ReduceArgs {
@@ -86,14 +48,6 @@ struct PowArgs {
 hipError_t pk_pp_rows(const PpArgs &a, hipStream_t st);
 hipError_t pk_pp_scan(const uint64_t *rowprod, uint64_t *z, uint64_t n, uint32_t nch_total, hipStream_t st);   // [batch * nch][n], contiguous
 hipError_t pk_pp_finish(const PpArgs &a, const uint64_t *z, uint64_t *zs_pp, uint64_t ps_z, uint64_t ps_zs, hipStream_t st);
-hipError_t pk_quotient(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st);
-// hash gates of the list that carry constraints; more than qfold::MAX_GATES: the circuit runs without the fold
-uint32_t pk_count_hash_gates(const GateDev *host_gates, uint32_t num_gates);
-// fills a.fold for the batch from its alpha powers (run before pk_quotient / pk_gate_sums whenever QuotientArgs::fold is set)
-hipError_t pk_quotient_fold_sweep(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st);
-hipError_t pk_gate_sums(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st);
-// result: [batch][2]
-hipError_t pk_witness_check(const uint64_t *acc, uint64_t n, uint32_t nch, const uint64_t *z, const uint64_t *rowprod, uint64_t *result, uint32_t batch, hipStream_t st);
 hipError_t pk_scale_powers(uint64_t *data, uint64_t n, uint64_t ncols, const uint64_t *pw_lo, const uint64_t *pw_hi, uint32_t lo_bits, hipStream_t st);
 // out[b][point][poly]; coeffs of proof b at coeffs + b * ps_coeffs (0: shared), its points at points + b * ps_points
 hipError_t pk_poly_eval(const uint64_t *coeffs, uint64_t n, uint32_t npolys, const gl::e2 *points, uint32_t npoints, gl::e2 *out,

@@ -9,15 +9,23 @@
 // linear layers: lambda starts as the alpha powers of the output constraints; through a layer lambda <- L^T lambda and
 // kappa += lambda . rc; where a lane was replaced by a wire, omega of the S-box behind that wire is the incoming lambda and
 // the lane's lambda restarts at the alpha power of that wire's constraint. One walk per (proof, challenge, hash gate) and
-// lockstep batch; the per-point kernel then computes S-boxes and weighted sums only (prover_kernels.hip).
+// lockstep batch; the per-point kernel then computes S-boxes and weighted sums only (quotient_kernels.hip).
 //
-// ONE description of the round structure (Schedule, seg_*) serves the backward walk (sweep), the per-point kernels and the host
-// form of the folded sum (folded_sum, checked against verify_math.hpp by tools/host_checks/quotient_fold_check.cpp). L^T is
-// taken from the forward layers themselves (their images of the unit vectors), so a change there cannot drift from here.
+// ONE description of the round structure (Schedule, seg_*) serves the backward walk (sweep), the forward walk it is the adjoint
+// of (walk: the round-by-round form of the constraints, the fold's A/B partner under QPGPU_QUOTIENT_FOLD=0), the per-point kernels
+// (quotient_kernels.hip) and the host form of the folded sum (folded_sum); walk and folded_sum are checked against verify_math.hpp
+// by tools/host_checks/quotient_fold_check.cpp. L^T is taken from the forward layers themselves (their images of the unit
+// vectors), so a change there cannot drift from here.
 #pragma once
 #include "circuit.hpp"
 #include "gl64.hpp"
 #include "poseidon.hpp"
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define QFOLD_UNROLL _Pragma("unroll")
+#else
+#define QFOLD_UNROLL
+#endif
 
 namespace qfold {
 using gl::u32;
@@ -72,14 +80,15 @@ GL_HD u32 seg_lin(const Schedule &s, int k) {
     const int r = seg_round(s, k);
     return r >= 4 && r <= 25 ? LIN_P2_INT : LIN_P2_EXT;
 }
-// the constant added to lane i behind segment k's layer (canonical)
+// the constant added to lane i behind segment k's layer (canonical). The indices are formed unsigned: none is negative, and the
+// compiler need not prove it at every call site to spare the sign extension
 GL_HD u64 seg_rc(const Schedule &s, const Consts &c, int k, int i) {
     const int r = seg_round(s, k);
     if (r == 29) return 0;
-    if (s.kind == GATE_POSEIDON) return c.rc[(r + 1) * 12 + i];
-    if (r < 3) return c.p2->rc_ext[(r + 1) * 12 + i];
-    if (r < 25) return i == 0 ? c.p2->rc_int[r - 3] : 0;
-    return c.p2->rc_ext[(r - 21) * 12 + i];
+    if (s.kind == GATE_POSEIDON) return c.rc[(u32)((r + 1) * 12 + i)];
+    if (r < 3) return c.p2->rc_ext[(u32)((r + 1) * 12 + i)];
+    if (r < 25) return i == 0 ? c.p2->rc_int[(u32)(r - 3)] : 0;
+    return c.p2->rc_ext[(u32)((r - 21) * 12 + i)];
 }
 GL_HD void apply_lin(u32 lin, u64 (&x)[12], const Consts &c) {
     if (lin == LIN_MDS) poseidon::mds_layer(x);
@@ -94,15 +103,11 @@ GL_HD u32 target_wire(const Schedule &s, u32 j) {
 // the inputs of the head's S-boxes from the (swapped) gate inputs; HEAD_RAW: the inputs stay as they are (and get no S-box)
 GL_HD void head_inputs(const Schedule &s, const Consts &c, u64 (&st)[12]) {
     if (s.kind == GATE_POSEIDON) {
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
+        QFOLD_UNROLL
         for (int i = 0; i < 12; i++) st[i] = gl::add(st[i], c.rc[i]);
     } else if (s.head == HEAD_SBOX) {
         poseidon2::ext_layer_qp(st);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
+        QFOLD_UNROLL
         for (int i = 0; i < 12; i++) st[i] = gl::add(st[i], c.p2->rc_ext[i]);
     }
 }
@@ -165,20 +170,59 @@ GL_HD void sweep(const Schedule &s, const Consts &c, const u64 *ap, Scratch &w, 
     }
 }
 
+// The hash gates' prologue: the swap boolean (constraint 0), the four delta constraints (1..4) and the state that enters the
+// permutation, its first two groups of four swapped by the deltas; without a swap wire the inputs as they are. read(wire) gives a
+// wire's value at the point, emit(q, c) takes constraint q of the gate.
+template <class Read, class Emit>
+GL_HD void swapped_inputs(const Schedule &s, Read read, Emit emit, u64 (&st)[12]) {
+    if (s.w_swap != NO_SWAP) {
+        const u64 swap = read(s.w_swap);
+        emit(0u, gl::mul(swap, gl::sub(swap, 1)));
+        QFOLD_UNROLL
+        for (int i = 0; i < 4; i++) {
+            const u64 lhs = read(s.w_input + i), rhs = read(s.w_input + 4 + i), delta = read(s.w_delta + i);
+            emit(1u + i, gl::sub(gl::mul(swap, gl::sub(rhs, lhs)), delta));
+            st[i] = gl::add(lhs, delta); st[i + 4] = gl::sub(rhs, delta);
+        }
+    } else {
+        QFOLD_UNROLL
+        for (int i = 0; i < 8; i++) st[i] = read(s.w_input + i);
+    }
+    QFOLD_UNROLL
+    for (int i = 8; i < 12; i++) st[i] = read(s.w_input + i);
+}
+
+// The forward walk, of which sweep is the adjoint: every constraint of the gate at one point, round by round. Behind each layer
+// and its constants the target lanes meet their wires (`state - wire`, constraint q0 + j in the order of target_wire, the last
+// segment's the twelve outputs); the wire replaces the lane and goes through the S-box.
+template <class Read, class Emit>
+GL_HD void walk(const Schedule &s, const Consts &c, Read read, Emit emit) {
+    u64 st[12];
+    swapped_inputs(s, read, emit, st);
+    head_inputs(s, c, st);
+    if (s.head == HEAD_SBOX) poseidon::sbox7_layer(st);
+    u32 j = 0;
+    for (int k = 0; k < (int)s.nseg; k++) {
+        apply_lin(seg_lin(s, k), st, c);
+        const bool last = k == (int)s.nseg - 1;
+        const u32 nt = seg_targets(s, k);
+        QFOLD_UNROLL
+        for (int i = 0; i < 12; i++) {      // the lane index stays a compile-time constant: the state lives in registers
+            st[i] = gl::add(st[i], seg_rc(s, c, k, i));
+            if ((u32)i >= nt) continue;
+            const u64 w = read(last ? s.w_output + i : target_wire(s, j + i));
+            emit(s.q0 + j + i, gl::sub(st[i], w));
+            if (!last) st[i] = poseidon::sbox7_lane(w);
+        }
+        j += nt;
+    }
+}
+
 // The folded sum at one point in plain arithmetic: what the per-point kernels compute (there with grouped S-box products and
 // 192-bit accumulators). row = the wire values at the point, ap and table as in sweep.
 GL_HD u64 folded_sum(const Schedule &s, const Consts &c, const u64 *row, const u64 *ap, const u64 *table) {
     u64 sum = table[T_KAPPA], st[12];
-    for (int i = 0; i < 12; i++) st[i] = row[s.w_input + i];
-    if (s.w_swap != NO_SWAP) {
-        const u64 swap = row[s.w_swap];
-        sum = gl::add(sum, gl::mul(ap[0], gl::mul(swap, gl::sub(swap, 1))));
-        for (int i = 0; i < 4; i++) {
-            const u64 delta = row[s.w_delta + i];
-            sum = gl::add(sum, gl::mul(ap[1 + i], gl::sub(gl::mul(swap, gl::sub(st[i + 4], st[i])), delta)));
-            st[i] = gl::add(st[i], delta); st[i + 4] = gl::sub(st[i + 4], delta);
-        }
-    }
+    swapped_inputs(s, [&](u32 w) { return row[w]; }, [&](u32 q, u64 cst) { sum = gl::add(sum, gl::mul(ap[q], cst)); }, st);
     head_inputs(s, c, st);
     for (int i = 0; i < 12; i++) sum = gl::add(sum, gl::mul(table[T_HEAD + i], s.head == HEAD_SBOX ? poseidon::sbox7(st[i]) : st[i]));
     for (u32 j = 0; j < s.nw; j++) {
@@ -189,4 +233,5 @@ GL_HD u64 folded_sum(const Schedule &s, const Consts &c, const u64 *row, const u
     return gl::canon(sum);
 }
 
+#undef QFOLD_UNROLL
 }  // namespace qfold

@@ -4,7 +4,9 @@ shapes where they can go wrong: 2^5 and 2^6 rows (one and two workgroups of quot
 (q_n < lde_n: the q_shift store path), lockstep batches of 1 and 3 with their own alphas, two challenges. The quotient stage's
 output is held to the oracle's `quotient_chunk_coeffs` trace through the staged API: the cap the proof carries for the quotient
 oracle must be the cap of that trace committed by qpgpu_oracle_*; the whole proof must equal the oracle's bytes as well. Exact
-arithmetic: no tolerance anywhere. The host side of the fold is tests/test_quotient_fold_host.py."""
+arithmetic: no tolerance anywhere. The round-by-round form of the hash gates (QPGPU_QUOTIENT_FOLD=0: one kernel over the forward
+walk of the same schedule, qfold::walk) is held to the same bytes for every schedule shape: with and without the swap, with and
+without round 0's wires. The host side of the fold is tests/test_quotient_fold_host.py."""
 import numpy as np
 import pytest
 
@@ -94,6 +96,62 @@ def test_fold_on_equals_fold_off(pkg, gpu, d, rate_bits, monkeypatch):
             circ.close()
     assert proofs["1"] == proofs["0"]
     assert proofs["1"][0] == proofs["1"][1] and len(set(proofs["1"])) == 3
+
+
+def _fold_on_and_off(monkeypatch, run):
+    """run() under QPGPU_QUOTIENT_FOLD=1 and =0 (read at circuit load): {"1": proofs, "0": proofs}."""
+    out = {}
+    for fold in ("1", "0"):
+        monkeypatch.setenv("QPGPU_QUOTIENT_FOLD", fold)
+        out[fold] = run()
+    return out
+
+
+def test_fold_on_equals_fold_off_without_swap(pkg, gpu, orc, monkeypatch):
+    """The Poseidon2 layout without a swap wire (q0 = 0: the walk's first constraint is a target wire's) through the round-by-round
+    kernel: a single proof and a lockstep batch of three at 2^6 rows, fold on == fold off == the oracle, byte for byte."""
+    pack, wires, pis = pkg.synth_circuit(6, seed=91, p2_alt_layout=True, **KW)
+    assert pkg.pack_p2_layout(pack)["w_swap"] == pkg.P2_NO_SWAP
+    made = {}
+
+    def run():
+        circ = pkg.Circuit(gpu, pack, max_batch=3)
+        try:
+            ws, ps = batch_witnesses(circ, wires, pis, 3)
+            made["w"] = (ws, ps)
+            return prove_batch(gpu, circ, ws[:1], ps[:1]) + prove_batch(gpu, circ, ws, ps)
+        finally:
+            circ.close()
+
+    proofs = _fold_on_and_off(monkeypatch, run)
+    ws, ps = made["w"]
+    oc = OracleCircuit(orc, pack)
+    try:
+        want = [oc.prove(w, p) for w, p in zip(ws, ps)]
+    finally:
+        oc.close()
+    assert proofs["1"] == proofs["0"] == want[:1] + want
+    assert len(set(want)) == 3
+
+
+def test_fold_on_equals_fold_off_with_first_round_wires(pkg, gpu, orc, monkeypatch):
+    """The layout that records round 0's S-box inputs too (HEAD_RAW: 31 segments, 118 target wires, no swap) through the
+    round-by-round kernel: the leaf circuit at its own 2^8 rows, one proof, fold on == fold off == the oracle."""
+    L = pkg.leaf
+    c = L.LeafCircuit(p2_layout=FRW_LAYOUT, config=pkg.circuit_config("leaf").replace(num_wires=143))
+    lay = pkg.pack_p2_layout(c.pack)
+    assert lay["first_round_wires"] == 1 and lay["w_swap"] == pkg.P2_NO_SWAP
+    x = lc.dummy_inputs(L)
+
+    def run():
+        pr = L.LeafProver(pkg, gpu, c)
+        try:
+            return pr.prove(x)[0]
+        finally:
+            pr.close()
+
+    proofs = _fold_on_and_off(monkeypatch, run)
+    assert proofs["1"] == proofs["0"] == oracle_side(orc, c, x)[1]
 
 
 def test_leaf_circuit_proof_bytes(pkg, gpu, orc):

@@ -1,5 +1,5 @@
-"""The folded form of the hash gates' quotient terms on the host (csrc/quotient_fold.hpp: the backward walk over the linear layers and
-the folded sum, the same GL_HD code the kernels compile) against the plain alpha-weighted sum over verify_math.hpp's constraints, as a
+"""The folded form of the hash gates' quotient terms on the host (csrc/quotient_fold.hpp: the backward walk over the linear layers, the
+folded sum and the forward walk of the round-by-round kernel, the same GL_HD code the kernels compile) against the plain alpha-weighted sum over verify_math.hpp's constraints, as a
 stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer: tools/host_checks/quotient_fold_check.cpp. No GPU; a few
 seconds. The kernels are tested on the device by tests/test_quotient_fold_gpu.py."""
 import os

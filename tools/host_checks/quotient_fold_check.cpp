@@ -1,5 +1,6 @@
 // quotient_fold_check.cpp — the folded form of the hash gates' quotient terms (csrc/quotient_fold.hpp: the backward walk that
-// turns alpha powers into per-S-box weights, and the folded sum the per-point kernels compute) against the plain
+// turns alpha powers into per-S-box weights, and the folded sum the per-point kernels compute) and the forward walk the
+// round-by-round kernel is instantiated over (qfold::walk), both against the plain
 // sum_q alpha^(t0+q) c_q over the constraints of the host gate evaluation (verify_math.hpp, base-field values), stand-alone and
 // without a GPU, meant to be built with -fsanitize=address,undefined. Random wire rows that do NOT satisfy the gate (every
 // constraint non-zero) and rows made to satisfy it; PoseidonGate with swap 0 and 1, the Poseidon2 gate in its four
@@ -78,6 +79,17 @@ static void check_gate(const char *name, const GateInfo &g, const P2GateLayout &
             const u64 folded = qfold::folded_sum(s, K, row.data(), apow.data() + T0, table.data());
             EXPECT(folded == gl::canon(plain));
             if (sat) EXPECT(folded == 0);
+            // the forward walk (the round-by-round kernel's form): the same constraints in the same order, weighted as it emits them
+            u64 walked = 0;
+            size_t emitted = 0;
+            qfold::walk(s, K, [&](uint32_t wire) { return row[wire]; }, [&](uint32_t q, u64 cst) {
+                EXPECT(q < nq);
+                walked = gl::add(walked, gl::mul(apow[T0 + q], cst));
+                emitted++;
+            });
+            EXPECT(emitted == nq);
+            EXPECT(gl::canon(walked) == gl::canon(plain));
+            if (sat) EXPECT(gl::canon(walked) == 0);
             rows++;
         }
     }
