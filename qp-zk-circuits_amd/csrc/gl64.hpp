@@ -2,7 +2,8 @@
 //
 // Replaces plonky2::field::goldilocks_field (qp-plonky2-field 1.5.5; reference type alias
 // common/src/circuit.rs:18). p = 2^64 - 2^32 + 1. The GPU has no 64x64 multiplier: a product is
-// four 32x32->64 v_mad_u64_u32 plus the 2^64 = 2^32-1, 2^96 = -1 folding, all in registers.
+// four 32x32->64 v_mad_u64_u32 (mul64wide) plus the 2^64 = 2^32-1, 2^96 = -1 folding (a fifth v_mad_u64_u32 by 2^32-1), all in
+// registers.
 //
 // Representation: values in registers may be any u64 ("loose"); gl_canon() brings them to [0,p)
 // before they are written where the reference would serialise them.
@@ -142,7 +143,9 @@ inline u64 reduce96(u64 lo, u32 hi) {
 #endif
 
 GL_HD void mul64wide(u64 a, u64 b, u64 &lo, u64 &hi) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) && defined(GL_MUL_WIDE_CLASSIC)
+    // the schoolbook order with 32-bit addends: each of the four addends is zero-extended into a register pair by a v_mov.
+    // Kept for the units that measured slower with the form below; such a unit defines GL_MUL_WIDE_CLASSIC before this header.
     u32 a0 = (u32)a, a1 = (u32)(a >> 32), b0 = (u32)b, b1 = (u32)(b >> 32);
     u64 p00 = (u64)a0 * b0;
     u64 p01 = (u64)a0 * b1 + (p00 >> 32);   // v_mad_u64_u32, no overflow
@@ -150,6 +153,27 @@ GL_HD void mul64wide(u64 a, u64 b, u64 &lo, u64 &hi) {
     u64 p11 = (u64)a1 * b1 + (p01 >> 32);   // no overflow: (2^32-1)^2 + 2^32-1 < 2^64
     lo = (p10 << 32) | (u32)p00;
     hi = p11 + (p10 >> 32);
+#elif defined(__HIP_DEVICE_COMPILE__)
+    // Both cross terms go through ONE 64-bit addend: with h00 = hi32(a0 b0), S = a1 b0 + (a0 b1 + h00) can reach 65 bits
+    // (S <= 2^65 - 3 2^32); M = S mod 2^64 comes out of the second multiply-add and the 65th bit cM is that instruction's own
+    // carry-out. a b = l00 + S 2^32 + a1 b1 2^64 is an identity, so hi = a1 b1 + (S >> 32) = floor(a b / 2^64) < 2^64 (the last
+    // multiply-add cannot wrap) and lo = lo32(M) 2^32 + l00 (disjoint words). Two zero-extensions into an aligned register pair
+    // (h00, and hi32(M) beside the carry word) instead of four; the carry word by the VOP2 select right behind the multiply-add
+    // that wrote vcc, as in mul_finish (GL_MASK_OF_VCC: implicit mask, no operand-read hazard). Counted in a gfx950 kernel of four
+    // independent products: 4 v_mad_u64_u32 + 2 v_mov + v_cndmask = 7 vector instructions against 4 + 4 + v_lshl_add_u64 = 9; a
+    // plain gl::mul 15 against 17, a lazy product of mul_group<4> 12 against 14. Measured (profiles/mul_wide_notes.txt): a0 b0 stays ONE
+    // v_mad_u64_u32 + v_mov; v_mul_lo_u32 + v_mul_hi_u32 in its place is one v_mov fewer on paper and slower in every kernel.
+    const u32 a0 = (u32)a, a1 = (u32)(a >> 32), b0 = (u32)b, b1 = (u32)(b >> 32);
+    const u64 p00 = (u64)a0 * b0;
+    u64 m = (u64)a0 * b1 + (p00 >> 32);               // < 2^64: (2^32-1)^2 + 2^32-2
+    u32 cm;
+    asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\t"       // m = a1 b0 + m, carry cM in vcc
+        "v_cndmask_b32_e32 %1, 0, %[one], vcc"        // cm = cM
+        : "+v"(m), "=v"(cm)
+        : "v"(a1), "v"(b0), [one] "v"(1u)
+        : "vcc");
+    hi = (u64)a1 * b1 + (((u64)cm << 32) | (u32)(m >> 32));
+    lo = ((u64)(u32)m << 32) | (u32)p00;
 #else
     unsigned __int128 m = (unsigned __int128)a * b;
     lo = (u64)m; hi = (u64)(m >> 64);
@@ -163,9 +187,9 @@ GL_HD u64 mul(u64 a, u64 b) {
 #if defined(__HIP_DEVICE_COMPILE__)
 // ---- lazy products for throughput builds: the rare folds of a group of independent products behind ONE wave-uniform branch ----
 // reduce128 begins with t = lo - hi_hi, whose borrow (lo < hi_hi < 2^32) random data sees about once in 2^32 products, and spends
-// three of the product's 22 vector instructions on folding it. The lazy form returns t and the wave mask of the lanes whose fold
+// three of the product's 15 vector instructions (counts of one gfx950 kernel of four products, see mul64wide) on folding it. The lazy form returns t and the wave mask of the lanes whose fold
 // is still due (a scalar register pair); mul_group ORs the masks of N independent products, tests the union once (GL_ANY_RARE: a
-// scalar compare and branch, no vector issue slot; `unlikely` keeps the folds out of line) and finishes the products: 19 vector
+// scalar compare and branch, no vector issue slot; `unlikely` keeps the folds out of line) and finishes the products: 12 vector
 // instructions each. A taken or not-taken scalar branch still costs its wave tens of cycles of latency, which only other resident
 // waves cover — hence one branch per group, and hence the plain forms wherever a launch is small (qpgpu_tp_min_threads).
 // Measured (profiles/r03_rare_fold.txt): Poseidon permutation 2.61 -> 2.81 G/s in registers at full occupancy. The same treatment

@@ -1,5 +1,5 @@
 // merkle_kernels_tp.hip — throughput build of the thread-per-hash kernels (merkle_hash_impl.hpp): the S-box products of the
-// Poseidon permutation are compiled as rare-fold groups (gl64.hpp: lazy forms; a product is 19 instead of 22 vector instructions
+// Poseidon permutation are compiled as rare-fold groups (gl64.hpp: lazy forms; a product is 12 instead of 15 vector instructions
 // and a stage of a layer has one wave-uniform branch), which pays when enough waves are resident to hide a scalar branch's
 // latency. merkle_kernels.hip routes launches of qpgpu_tp_min_threads() threads or more here.
 #define POSEIDON_GROUPED_SBOX 1

@@ -16,6 +16,8 @@
 // The exchanges pass the low and the high 32-bit halves through the same 4-byte slots one after the other (as the split
 // passes of ntt_kernel_impl.hpp do): 34 KB of LDS per workgroup at d = 13, so four 256-thread workgroups share a CU and the
 // register budget is pinned to four wavefronts per SIMD.
+// this unit keeps the schoolbook product: with the single-addend form ntt_lde_column_kernel<5> measured 17.5 % slower (profiles/mul_wide_notes.txt item 6)
+#define GL_MUL_WIDE_CLASSIC
 #include <hip/hip_runtime.h>
 #include "gl64.hpp"
 #include "ntt_pass.hpp"

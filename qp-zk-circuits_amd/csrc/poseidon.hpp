@@ -22,7 +22,7 @@ GL_HD u64 sbox7(u64 x) {
 }
 // The S-boxes as permute() applies them: a whole layer, or lane 0 alone in a partial round. A unit that defines
 // POSEIDON_GROUPED_SBOX (the throughput build of the hashing kernels, merkle_kernels_tp.hip) gets the products of a stage as one
-// rare-fold group (gl::mul_group: 19 instead of 22 vector instructions per product, one scalar branch per stage).
+// rare-fold group (gl::mul_group: 12 instead of 15 vector instructions per product, one scalar branch per stage).
 #if defined(__HIP_DEVICE_COMPILE__) && defined(POSEIDON_GROUPED_SBOX)
 template <int N>
 __device__ __forceinline__ void sbox7_layer(u64 (&x)[N]) {

@@ -370,7 +370,7 @@ __global__ void __launch_bounds__(256) quotient_hash_rounds_kernel(QuotientArgs 
 }
 
 // ---- (3'), (4') the hash gates with their linear layers folded into the alpha weights (quotient_fold.hpp) ----
-// x^7 of N independent values as rare-fold product groups (gl::mul_group: 19 instead of 22 vector instructions per product, one
+// x^7 of N independent values as rare-fold product groups (gl::mul_group: 12 instead of 15 vector instructions per product, one
 // scalar branch per group and stage). These launches are large (q_n x batch threads), the regime that form is for.
 template <int N>
 __device__ __forceinline__ void sbox7_group(u64 (&x)[N]) {
