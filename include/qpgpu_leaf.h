@@ -203,6 +203,40 @@ int qpgpu_zk_tree_read_level(const qpgpu_zk_tree *t, unsigned level, size_t firs
  * >= the leaf count is QPGPU_EINVAL. */
 int qpgpu_zk_tree_open(const qpgpu_zk_tree *t, const uint64_t *indices, size_t n, uint8_t *siblings_out, uint8_t *positions_out);
 
+/* ---- following the chain: append to the resident tree, open paths at an earlier root ----
+ * The chain's tree is append-only, and a spend is proven against the zk_tree_root of the block it names, usually a recent block and not
+ * the newest. A tree built with room to grow takes each block's transfers as an append that rehashes only the ancestors of the new
+ * leaves (at level l, nodes floor(n / 4^l) .. ceil((n + k) / 4^l) - 1 for k leaves appended at count n), and a snapshot taken at a
+ * block (528 bytes, kept by the caller) lets paths be opened against the tree as it stood then: at count n the only node of level
+ * l >= 1 that a later append can change is the level's last one, so those `depth` nodes and n describe that tree. */
+typedef struct {
+    uint64_t count;            /* leaves at the time of the snapshot */
+    uint32_t depth, reserved;  /* the tree's depth; 0 */
+    uint8_t last[16][32];      /* last[l - 1] = the last node of level l, l = 1 .. depth; the rest zero; the root is last[depth - 1] */
+} qpgpu_zk_snapshot;
+
+/* qpgpu_zk_tree_build with storage laid out for `capacity` leaves: 1 <= count <= capacity <= QPGPU_ZK_TREE_MAX_LEAVES, and
+ * 4^depth >= capacity (depth = 0: the smallest such depth), so that an append never moves a node or changes the depth. Every other
+ * rule, refusal and result is qpgpu_zk_tree_build's; the tree equals the one qpgpu_zk_tree_build gives for the same leaves and depth. */
+int qpgpu_zk_tree_build_reserved(struct qpgpu_ctx *ctx, const void *leaves, size_t count, size_t capacity, unsigned depth, unsigned flags,
+                                 qpgpu_zk_tree **out, char *err);
+/* the leaves the tree has room for; the leaf count for a tree from qpgpu_zk_tree_build */
+size_t qpgpu_zk_tree_capacity(const qpgpu_zk_tree *t);
+/* k more leaves behind the last: leaf hashes (k x 32 bytes, host) or, with QPGPU_ZK_TREE_FROM_TRANSFERS, qpgpu_zk_leaf[k]. Afterwards the
+ * tree equals the one built from all its leaves. snap_out (may be NULL): the snapshot after the append. QPGPU_EINVAL, with the tree
+ * (count, every node, every earlier snapshot's paths) exactly as before: k = 0, count + k above the capacity, a tree from
+ * qpgpu_zk_tree_build (its capacity is its count; the message says so), an unknown flag, a leaf hash with a non-canonical limb (the
+ * message names the lowest such index in the tree, count + j). err: QPGPU_LEAF_ERR_CAP bytes, may be NULL. */
+int qpgpu_zk_tree_append(qpgpu_zk_tree *t, const void *leaves, size_t k, unsigned flags, qpgpu_zk_snapshot *snap_out, char *err);
+/* the snapshot of the tree as it stands: what the last append returned, or the state after the build */
+int qpgpu_zk_tree_snapshot(const qpgpu_zk_tree *t, qpgpu_zk_snapshot *out);
+/* qpgpu_zk_tree_open against the tree as it stood at the snapshot: what qpgpu_zk_tree_open returns on a tree built from the first
+ * snap->count leaves at the same depth, leading to the root snap->last[depth - 1]. QPGPU_EINVAL: snap->count = 0 or above the tree's
+ * leaf count, snap->depth other than the tree's, an index >= snap->count (the message names the entry). The snapshot must be one this
+ * tree gave; that is not checked, and a forged or foreign snapshot yields paths that do not verify against any root of the chain. */
+int qpgpu_zk_tree_open_at(const qpgpu_zk_tree *t, const qpgpu_zk_snapshot *snap, const uint64_t *indices, size_t n, uint8_t *siblings_out,
+                          uint8_t *positions_out);
+
 /* ---- the leaf circuit's constraints, natively ----
  * What WormholeCircuit constrains about a CircuitInputs (wormhole/circuit/src/circuit.rs:233-323 and the fragments it wires:
  * unspendable_account.rs:215-237, nullifier.rs:285-325, block_header/mod.rs:93-108, zk_merkle_proof.rs:480-626), evaluated on

@@ -145,6 +145,15 @@ extern "C" {
     pub fn qpgpu_zk_tree_root(t: *const QpgpuZkTree, out: *mut u8) -> i32;
     pub fn qpgpu_zk_tree_read_level(t: *const QpgpuZkTree, level: u32, first: usize, n: usize, out: *mut u8) -> i32;
     pub fn qpgpu_zk_tree_open(t: *const QpgpuZkTree, indices: *const u64, n: usize, siblings_out: *mut u8, positions_out: *mut u8) -> i32;
+    // the same tree with room to grow: append a block's leaves (only their ancestors are rehashed), keep the 528-byte snapshot per block,
+    // open paths against the tree as it stood at a snapshot (the root is snap.last[depth - 1])
+    pub fn qpgpu_zk_tree_build_reserved(ctx: *mut QpgpuCtx, leaves: *const c_void, count: usize, capacity: usize, depth: u32, flags: u32,
+                                        out: *mut *mut QpgpuZkTree, err: *mut c_char) -> i32;
+    pub fn qpgpu_zk_tree_capacity(t: *const QpgpuZkTree) -> usize;
+    pub fn qpgpu_zk_tree_append(t: *mut QpgpuZkTree, leaves: *const c_void, k: usize, flags: u32, snap_out: *mut QpgpuZkSnapshot, err: *mut c_char) -> i32;
+    pub fn qpgpu_zk_tree_snapshot(t: *const QpgpuZkTree, out: *mut QpgpuZkSnapshot) -> i32;
+    pub fn qpgpu_zk_tree_open_at(t: *const QpgpuZkTree, snap: *const QpgpuZkSnapshot, indices: *const u64, n: usize, siblings_out: *mut u8,
+                                 positions_out: *mut u8) -> i32;
     pub fn qpgpu_wrapper_circuit_build(inner_pack: *const u64, inner_words: usize, inner_cs_cap: *const u64, cap_words: usize, num_proofs: u32,
                                        num_routed_wires: u32, min_degree_bits: u32, inner_hasher: i32, flags: u32, pack_out: *mut u64, pack_cap_words: usize,
                                        pack_words: *mut usize, target_map_out: *mut u64, map_cap: usize, map_count: *mut usize, info_out: *mut u64,
@@ -155,6 +164,10 @@ extern "C" {
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct QpgpuZkLeaf { pub to_account: [u8; 32], pub transfer_count: u64, pub asset_id: u32, pub input_amount: u32 }
 pub const QPGPU_ZK_TREE_FROM_TRANSFERS: u32 = 1;
+/// qpgpu_zk_snapshot (include/qpgpu_leaf.h): the tree as it stood at `count` leaves, kept per block; 528 bytes.
+/// last[l - 1] = the last node of level l, l = 1 ..= depth, the rest zero; the root is last[depth - 1]
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct QpgpuZkSnapshot { pub count: u64, pub depth: u32, pub reserved: u32, pub last: [[u8; 32]; 16] }
 /// qpgpu_circuit_config (include/qpgpu_wire.h): plonky2's CircuitConfig + FriConfig (ConstantArityBits reduction) as plain data
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct QpgpuCircuitConfig {

@@ -77,6 +77,11 @@ def load_library():
         "qpgpu_zk_tree_root": (c.c_int, [vp, vp]),
         "qpgpu_zk_tree_read_level": (c.c_int, [vp, c.c_uint, c.c_size_t, c.c_size_t, vp]),
         "qpgpu_zk_tree_open": (c.c_int, [vp, vp, c.c_size_t, vp, vp]),
+        "qpgpu_zk_tree_build_reserved": (c.c_int, [vp, vp, c.c_size_t, c.c_size_t, c.c_uint, c.c_uint, c.POINTER(vp), c.c_char_p]),
+        "qpgpu_zk_tree_capacity": (c.c_size_t, [vp]),
+        "qpgpu_zk_tree_append": (c.c_int, [vp, vp, c.c_size_t, c.c_uint, vp, c.c_char_p]),
+        "qpgpu_zk_tree_snapshot": (c.c_int, [vp, vp]),
+        "qpgpu_zk_tree_open_at": (c.c_int, [vp, vp, vp, c.c_size_t, vp, vp]),
         "qpgpu_poseidon2_hash_pad10": (c.c_int, [u64p, c.c_size_t, u64p, c.c_size_t, u64p]),
         "qpgpu_crash_trace_armed": (c.c_int, []),
         "qpgpu_circuit_num_public_inputs": (c.c_size_t, [vp]),

@@ -2,6 +2,7 @@
 // block's tree in HBM, its root, its levels and the Merkle paths of many leaves per call. The rules are common/src/zk_merkle.rs as
 // leaf_witness.cpp restates them on the host; the geometry and the argument checks are zk_tree.hpp's, the kernels zk_tree_kernels.hip's.
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -13,13 +14,25 @@ static_assert(sizeof(qpgpu_zk_leaf) == zk_tree::LEAF_RECORD_BYTES, "qpgpu_zk_lea
 static_assert(QPGPU_ZK_TREE_MAX_LEAVES == zk_tree::MAX_LEAVES && QPGPU_LEAF_MAX_DEPTH == zk_tree::MAX_DEPTH &&
               QPGPU_ZK_TREE_FROM_TRANSFERS == zk_tree::FLAG_FROM_TRANSFERS, "qpgpu_leaf.h and zk_tree.hpp disagree");
 
+static_assert(sizeof(qpgpu_zk_snapshot) == sizeof(zk_tree::Snapshot) && sizeof(qpgpu_zk_snapshot) == 16 + zk_tree::SNAPSHOT_NODES_BYTES &&
+              offsetof(qpgpu_zk_snapshot, last) == offsetof(zk_tree::Snapshot, last), "qpgpu_zk_snapshot is copied into zk_tree::Snapshot whole");
+
 struct qpgpu_zk_tree {
     qpgpu_ctx *ctx = nullptr;
-    zk_tree::Plan plan;
-    uint8_t *d_nodes = nullptr;      // plan.total() nodes of 32 bytes
+    zk_tree::Plan plan;              // offsets laid out for `capacity`, sizes of the live count
+    uint64_t capacity = 0;
+    bool reserved = false;           // from qpgpu_zk_tree_build_reserved: appends are allowed
+    uint8_t *d_nodes = nullptr;      // plan.total() nodes of 32 bytes, then Aux
+    uint8_t *d_aux() const { return d_nodes + (size_t)plan.total() * zk_tree::NODE_BYTES; }
 };
 
 namespace {
+
+// behind the nodes: the word that names a refused leaf and the snapshot nodes an append or a snapshot call gathers, read back in one copy
+struct Aux {
+    uint32_t bad_leaf, pad[7];       // (the nodes stay 32-byte aligned)
+    uint8_t snap[zk_tree::SNAPSHOT_NODES_BYTES];
+};
 
 // a device allocation that lives for one call
 struct Scratch {
@@ -47,6 +60,47 @@ int read_nodes(qpgpu_ctx *ctx, void *dst, const void *d_src, size_t bytes, const
     if (bytes == 0) return QPGPU_OK;
     ZK_HIP(ctx, nullptr, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream), what);
     ZK_HIP(ctx, nullptr, hipStreamSynchronize(ctx->stream), what);
+    return QPGPU_OK;
+}
+
+// the body of both builds: `plan` holds `count` leaves in a layout for `capacity`
+int build_tree(qpgpu_ctx *ctx, const void *leaves, const zk_tree::Plan &plan, uint64_t capacity, bool reserved, unsigned flags, qpgpu_zk_tree **out,
+               char *err, const char *what) {
+    const size_t count = (size_t)plan.count;
+    int rc = ctx->ensure_p2_app();
+    if (rc) { if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "%s", ctx->err.c_str()); return rc; }
+
+    // the nodes, and behind them the word that names a refused leaf
+    const size_t node_bytes = (size_t)plan.total() * zk_tree::NODE_BYTES;
+    Scratch nodes, records;
+    ZK_HIP(ctx, err, nodes.alloc(node_bytes + sizeof(Aux)), what);
+    uint8_t *d_nodes = nodes.as<uint8_t>();
+    uint32_t *d_bad = (uint32_t *)(d_nodes + node_bytes + offsetof(Aux, bad_leaf));
+    ZK_HIP(ctx, err, hipMemsetAsync(d_bad, 0xFF, sizeof(uint32_t), ctx->stream), what);
+    if (flags & zk_tree::FLAG_FROM_TRANSFERS) {
+        ZK_HIP(ctx, err, records.alloc(count * zk_tree::LEAF_RECORD_BYTES), what);
+        ZK_HIP(ctx, err, hipMemcpyAsync(records.p, leaves, count * zk_tree::LEAF_RECORD_BYTES, hipMemcpyHostToDevice, ctx->stream), what);
+        ZK_HIP(ctx, err, zk_tree_leaf_hashes(records.as<uint8_t>(), count, d_nodes, ctx->d_p2_app, ctx->stream), what);
+    } else {
+        ZK_HIP(ctx, err, hipMemcpyAsync(d_nodes, leaves, count * zk_tree::NODE_BYTES, hipMemcpyHostToDevice, ctx->stream), what);
+    }
+    ctx->prof_begin("zk_tree_levels");
+    const hipError_t e_levels = zk_tree_reduce(d_nodes, plan, d_bad, ctx->d_p2_app, ctx->stream);
+    ctx->prof_end();
+    ZK_HIP(ctx, err, e_levels, what);
+    uint32_t bad = 0;
+    ZK_HIP(ctx, err, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream), what);
+    ZK_HIP(ctx, err, hipStreamSynchronize(ctx->stream), what);
+    if (bad != 0xFFFFFFFFu) {
+        char why[96];
+        std::snprintf(why, sizeof why, "leaf %u: hash bytes are noncanonical (a limb >= p)", bad);
+        return refuse(ctx, err, QPGPU_EINVAL, what, why);
+    }
+    qpgpu_zk_tree *t = new (std::nothrow) qpgpu_zk_tree;
+    if (!t) return refuse(ctx, err, QPGPU_ENOMEM, what, "out of host memory");
+    t->ctx = ctx; t->plan = plan; t->capacity = capacity; t->reserved = reserved; t->d_nodes = d_nodes;
+    nodes.p = nullptr;               // owned by the handle from here
+    *out = t;
     return QPGPU_OK;
 }
 
@@ -79,41 +133,20 @@ int qpgpu_zk_tree_build(qpgpu_ctx *ctx, const void *leaves, size_t count, unsign
     if (!leaves || !out) return refuse(ctx, err, QPGPU_EINVAL, what, "null argument");
     zk_tree::Plan plan;
     if (const char *why = zk_tree::make_plan(count, depth, flags, plan)) return refuse(ctx, err, QPGPU_EINVAL, what, why);
-    int rc = ctx->ensure_p2_app();
-    if (rc) { if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "%s", ctx->err.c_str()); return rc; }
+    return build_tree(ctx, leaves, plan, count, false, flags, out, err, what);
+}
 
-    // the nodes, and behind them the word that names a refused leaf
-    const size_t node_bytes = (size_t)plan.total() * zk_tree::NODE_BYTES;
-    Scratch nodes, records;
-    ZK_HIP(ctx, err, nodes.alloc(node_bytes + sizeof(uint32_t)), what);
-    uint8_t *d_nodes = nodes.as<uint8_t>();
-    uint32_t *d_bad = (uint32_t *)(d_nodes + node_bytes);
-    ZK_HIP(ctx, err, hipMemsetAsync(d_bad, 0xFF, sizeof(uint32_t), ctx->stream), what);
-    if (flags & zk_tree::FLAG_FROM_TRANSFERS) {
-        ZK_HIP(ctx, err, records.alloc(count * zk_tree::LEAF_RECORD_BYTES), what);
-        ZK_HIP(ctx, err, hipMemcpyAsync(records.p, leaves, count * zk_tree::LEAF_RECORD_BYTES, hipMemcpyHostToDevice, ctx->stream), what);
-        ZK_HIP(ctx, err, zk_tree_leaf_hashes(records.as<uint8_t>(), count, d_nodes, ctx->d_p2_app, ctx->stream), what);
-    } else {
-        ZK_HIP(ctx, err, hipMemcpyAsync(d_nodes, leaves, count * zk_tree::NODE_BYTES, hipMemcpyHostToDevice, ctx->stream), what);
-    }
-    ctx->prof_begin("zk_tree_levels");
-    const hipError_t e_levels = zk_tree_reduce(d_nodes, plan, d_bad, ctx->d_p2_app, ctx->stream);
-    ctx->prof_end();
-    ZK_HIP(ctx, err, e_levels, what);
-    uint32_t bad = 0;
-    ZK_HIP(ctx, err, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream), what);
-    ZK_HIP(ctx, err, hipStreamSynchronize(ctx->stream), what);
-    if (bad != 0xFFFFFFFFu) {
-        char why[96];
-        std::snprintf(why, sizeof why, "leaf %u: hash bytes are noncanonical (a limb >= p)", bad);
-        return refuse(ctx, err, QPGPU_EINVAL, what, why);
-    }
-    qpgpu_zk_tree *t = new (std::nothrow) qpgpu_zk_tree;
-    if (!t) return refuse(ctx, err, QPGPU_ENOMEM, what, "out of host memory");
-    t->ctx = ctx; t->plan = plan; t->d_nodes = d_nodes;
-    nodes.p = nullptr;               // owned by the handle from here
-    *out = t;
-    return QPGPU_OK;
+int qpgpu_zk_tree_build_reserved(qpgpu_ctx *ctx, const void *leaves, size_t count, size_t capacity, unsigned depth, unsigned flags,
+                                 qpgpu_zk_tree **out, char *err) {
+    if (err) err[0] = 0;
+    if (out) *out = nullptr;
+    if (!ctx) { if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "zk_tree_build_reserved: null context"); return QPGPU_EINVAL; }
+    QP_DEV(ctx);
+    static const char *const what = "zk_tree_build_reserved";
+    if (!leaves || !out) return refuse(ctx, err, QPGPU_EINVAL, what, "null argument");
+    zk_tree::Plan plan;
+    if (const char *why = zk_tree::make_plan_reserved(count, capacity, depth, flags, plan)) return refuse(ctx, err, QPGPU_EINVAL, what, why);
+    return build_tree(ctx, leaves, plan, capacity, true, flags, out, err, what);
 }
 
 void qpgpu_zk_tree_free(qpgpu_zk_tree *t) {
@@ -163,6 +196,102 @@ int qpgpu_zk_tree_open(const qpgpu_zk_tree *t, const uint64_t *indices, size_t n
     ZK_HIP(ctx, nullptr, hipMemcpyAsync(idx.p, indices, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream), what);
     ctx->prof_begin("zk_tree_open");
     const hipError_t e_open = zk_tree_open_paths(t->d_nodes, t->plan, idx.as<uint64_t>(), n, sib.as<uint8_t>(), pos.as<uint8_t>(), ctx->stream);
+    ctx->prof_end();
+    ZK_HIP(ctx, nullptr, e_open, what);
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(siblings_out, sib.p, rows * zk_tree::PATH_LEVEL_BYTES, hipMemcpyDeviceToHost, ctx->stream), what);
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(positions_out, pos.p, rows, hipMemcpyDeviceToHost, ctx->stream), what);
+    ZK_HIP(ctx, nullptr, hipStreamSynchronize(ctx->stream), what);
+    return QPGPU_OK;
+}
+
+size_t qpgpu_zk_tree_capacity(const qpgpu_zk_tree *t) { return t ? (size_t)t->capacity : 0; }
+
+// The new leaves go into their level-0 slots, where they are invisible while the count stands, and are tested there; the rehash kernels
+// do nothing once the refusal word is set; the count advances on the host after the one synchronisation. A refused append therefore
+// leaves every live node as it was.
+int qpgpu_zk_tree_append(qpgpu_zk_tree *t, const void *leaves, size_t k, unsigned flags, qpgpu_zk_snapshot *snap_out, char *err) {
+    if (err) err[0] = 0;
+    if (!t) { if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "zk_tree_append: null tree"); return QPGPU_EINVAL; }
+    qpgpu_ctx *ctx = t->ctx;
+    QP_DEV(ctx);
+    static const char *const what = "zk_tree_append";
+    if (const char *why = zk_tree::check_append(t->plan, t->capacity, t->reserved, k, flags)) return refuse(ctx, err, QPGPU_EINVAL, what, why);
+    if (!leaves) return refuse(ctx, err, QPGPU_EINVAL, what, "null argument");
+    const uint64_t n_old = t->plan.count;
+    zk_tree::Plan grown;
+    if (const char *why = zk_tree::make_plan_reserved(n_old + k, t->capacity, t->plan.depth, flags, grown)) return refuse(ctx, err, QPGPU_EINVAL, what, why);
+
+    uint8_t *d_aux = t->d_aux(), *d_new = t->d_nodes + n_old * zk_tree::NODE_BYTES;
+    uint32_t *d_bad = (uint32_t *)(d_aux + offsetof(Aux, bad_leaf));
+    Scratch records;
+    ZK_HIP(ctx, err, hipMemsetAsync(d_bad, 0xFF, sizeof(uint32_t), ctx->stream), what);
+    if (flags & zk_tree::FLAG_FROM_TRANSFERS) {          // permutation outputs: canonical by construction
+        ZK_HIP(ctx, err, records.alloc(k * zk_tree::LEAF_RECORD_BYTES), what);
+        ZK_HIP(ctx, err, hipMemcpyAsync(records.p, leaves, k * zk_tree::LEAF_RECORD_BYTES, hipMemcpyHostToDevice, ctx->stream), what);
+        ZK_HIP(ctx, err, zk_tree_leaf_hashes(records.as<uint8_t>(), k, d_new, ctx->d_p2_app, ctx->stream), what);
+    } else {
+        ZK_HIP(ctx, err, hipMemcpyAsync(d_new, leaves, k * zk_tree::NODE_BYTES, hipMemcpyHostToDevice, ctx->stream), what);
+    }
+    ctx->prof_begin("zk_tree_append");
+    hipError_t e = (flags & zk_tree::FLAG_FROM_TRANSFERS) ? hipSuccess : zk_tree_check_leaves(t->d_nodes, grown, n_old, k, d_bad, ctx->stream);
+    if (e == hipSuccess) e = zk_tree_rehash(t->d_nodes, grown, n_old, d_bad, d_aux + offsetof(Aux, snap), ctx->d_p2_app, ctx->stream);
+    ctx->prof_end();
+    ZK_HIP(ctx, err, e, what);
+    Aux aux;
+    ZK_HIP(ctx, err, hipMemcpyAsync(&aux, d_aux, sizeof aux, hipMemcpyDeviceToHost, ctx->stream), what);
+    ZK_HIP(ctx, err, hipStreamSynchronize(ctx->stream), what);      // also ends the kernel's use of `records`
+    if (aux.bad_leaf != 0xFFFFFFFFu) {
+        char why[96];
+        std::snprintf(why, sizeof why, "leaf %u: hash bytes are noncanonical (a limb >= p)", aux.bad_leaf);
+        return refuse(ctx, err, QPGPU_EINVAL, what, why);
+    }
+    t->plan = grown;
+    if (snap_out) {
+        std::memset(snap_out, 0, sizeof *snap_out);
+        snap_out->count = grown.count; snap_out->depth = grown.depth;
+        std::memcpy(snap_out->last, aux.snap, sizeof aux.snap);
+    }
+    return QPGPU_OK;
+}
+
+int qpgpu_zk_tree_snapshot(const qpgpu_zk_tree *t, qpgpu_zk_snapshot *out) {
+    if (!t) return QPGPU_EINVAL;
+    qpgpu_ctx *ctx = t->ctx;
+    QP_DEV(ctx);
+    static const char *const what = "zk_tree_snapshot";
+    if (!out) return refuse(ctx, nullptr, QPGPU_EINVAL, what, "null argument");
+    uint8_t *d_snap = t->d_aux() + offsetof(Aux, snap);
+    ZK_HIP(ctx, nullptr, zk_tree_gather_snapshot(t->d_nodes, t->plan, d_snap, ctx->stream), what);
+    std::memset(out, 0, sizeof *out);
+    out->count = t->plan.count; out->depth = t->plan.depth;
+    return read_nodes(ctx, out->last, d_snap, zk_tree::SNAPSHOT_NODES_BYTES, what);
+}
+
+int qpgpu_zk_tree_open_at(const qpgpu_zk_tree *t, const qpgpu_zk_snapshot *snap, const uint64_t *indices, size_t n, uint8_t *siblings_out,
+                          uint8_t *positions_out) {
+    if (!t) return QPGPU_EINVAL;
+    qpgpu_ctx *ctx = t->ctx;
+    QP_DEV(ctx);
+    static const char *const what = "zk_tree_open_at";
+    if (!snap || (n && (!indices || !siblings_out || !positions_out))) return refuse(ctx, nullptr, QPGPU_EINVAL, what, "null argument");
+    uint64_t bad = 0;
+    if (const char *why = zk_tree::check_open_at(t->plan, snap->count, snap->depth, indices, n, &bad)) {
+        char msg[96];
+        if (std::strcmp(why, "leaf index out of range") == 0) std::snprintf(msg, sizeof msg, "entry %llu: %s", (unsigned long long)bad, why);
+        else std::snprintf(msg, sizeof msg, "%s", why);
+        return refuse(ctx, nullptr, QPGPU_EINVAL, what, msg);
+    }
+    if (n == 0) return QPGPU_OK;
+    zk_tree::Snapshot at;
+    std::memcpy(&at, snap, sizeof at);
+    const size_t rows = n * t->plan.depth;
+    Scratch idx, sib, pos;
+    ZK_HIP(ctx, nullptr, idx.alloc(n * sizeof(uint64_t)), what);
+    ZK_HIP(ctx, nullptr, sib.alloc(rows * zk_tree::PATH_LEVEL_BYTES), what);
+    ZK_HIP(ctx, nullptr, pos.alloc(rows), what);
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(idx.p, indices, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream), what);
+    ctx->prof_begin("zk_tree_open_at");
+    const hipError_t e_open = zk_tree_open_paths_at(t->d_nodes, t->plan, at, idx.as<uint64_t>(), n, sib.as<uint8_t>(), pos.as<uint8_t>(), ctx->stream);
     ctx->prof_end();
     ZK_HIP(ctx, nullptr, e_open, what);
     ZK_HIP(ctx, nullptr, hipMemcpyAsync(siblings_out, sib.p, rows * zk_tree::PATH_LEVEL_BYTES, hipMemcpyDeviceToHost, ctx->stream), what);

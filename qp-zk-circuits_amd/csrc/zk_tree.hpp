@@ -65,6 +65,65 @@ inline const char *check_open(const Plan &p, const uint64_t *indices, uint64_t n
     return nullptr;
 }
 
+// ---- an append-only tree with room to grow (qpgpu_zk_tree_build_reserved / _append / _open_at) ----
+// Appending k leaves at count n changes, at level l, exactly the nodes floor(n / 4^l) .. ceil((n + k) / 4^l) - 1: a node is dirty when
+// its leaf range [i 4^l, (i + 1) 4^l) meets [n, n + k). So at count n the only node of level l >= 1 that a later append can change is
+// the level's last one, and those `depth` nodes plus n describe the tree as it stood at n.
+
+// The same layout as qpgpu_zk_snapshot (include/qpgpu_leaf.h), the nodes as words: passed to zk_open_at_kernel by value.
+struct Snapshot {
+    uint64_t count = 0;
+    uint32_t depth = 0, reserved = 0;
+    uint64_t last[MAX_DEPTH][4] = {{0}};                 // last[l - 1] = the last node of level l, l = 1 .. depth; the root is last[depth - 1]
+};
+constexpr size_t SNAPSHOT_NODES_BYTES = MAX_DEPTH * NODE_BYTES;
+
+// the smallest depth with 4^depth >= capacity is min_depth(capacity). off[l] is laid out for `capacity` leaves, size[l] is that of the
+// live `count`: an append never moves a node, and the kernels and check_range read the plan as they read make_plan's (which this is
+// for capacity == count). total() is the nodes allocated.
+inline const char *make_plan_reserved(uint64_t count, uint64_t capacity, unsigned depth, unsigned flags, Plan &p) {
+    if (count == 0) return "count is 0";
+    if (capacity > MAX_LEAVES) return "capacity exceeds 2^24 leaves";
+    if (count > capacity) return "count exceeds the capacity";
+    if (flags & ~KNOWN_FLAGS) return "unknown flag";
+    if (depth > MAX_DEPTH) return "depth exceeds 16";
+    const unsigned dmin = min_depth(capacity);
+    if (depth == 0) depth = dmin;
+    if (depth < dmin) return "depth too small: 4^depth is below capacity";
+    p = Plan();
+    p.count = count; p.depth = depth;
+    uint64_t at = 0;
+    for (unsigned l = 0; l <= depth; l++) { p.size[l] = level_size(count, l); p.off[l] = at; at += level_size(capacity, l); }
+    p.off[depth + 1] = at;
+    return nullptr;
+}
+
+// the nodes of `level` that an append of k >= 1 leaves at count n rehashes (level 0: the new leaves themselves)
+inline void dirty_range(uint64_t n, uint64_t k, unsigned level, uint64_t &first, uint64_t &cnt) {
+    first = n >> (2 * level);
+    cnt = level_size(n + k, level) - first;
+}
+
+// reserved: the tree came from qpgpu_zk_tree_build_reserved
+inline const char *check_append(const Plan &p, uint64_t capacity, bool reserved, uint64_t k, unsigned flags) {
+    if (flags & ~KNOWN_FLAGS) return "unknown flag";
+    if (!reserved) return "the tree was built by qpgpu_zk_tree_build, whose capacity is its count: nothing can be appended (use qpgpu_zk_tree_build_reserved)";
+    if (k == 0) return "k is 0";
+    if (p.count > capacity || k > capacity - p.count) return "count + k exceeds the tree's capacity";
+    return nullptr;
+}
+
+// a snapshot against the tree it is opened on, then check_open against the snapshot's count
+inline const char *check_open_at(const Plan &p, uint64_t snap_count, uint32_t snap_depth, const uint64_t *indices, uint64_t n, uint64_t *bad) {
+    if (snap_count == 0) return "snapshot count is 0";
+    if (snap_count > p.count) return "snapshot count exceeds the tree's leaf count";
+    if (snap_depth != p.depth) return "snapshot depth differs from the tree's";
+    if (n > (uint64_t)SIZE_MAX / (PATH_LEVEL_BYTES * MAX_DEPTH)) return "too many paths for one call";
+    for (uint64_t i = 0; i < n; i++)
+        if (indices[i] >= snap_count) { if (bad) *bad = i; return "leaf index out of range"; }
+    return nullptr;
+}
+
 }  // namespace zk_tree
 
 #ifndef ZK_TREE_PLAN_ONLY   // the stand-alone host check takes the geometry alone
@@ -79,4 +138,16 @@ hipError_t zk_tree_reduce(uint8_t *d_nodes, const zk_tree::Plan &plan, uint32_t 
 // n paths: d_siblings n x depth x 96 bytes, d_positions n x depth bytes
 hipError_t zk_tree_open_paths(const uint8_t *d_nodes, const zk_tree::Plan &plan, const uint64_t *d_indices, uint64_t n, uint8_t *d_siblings,
                               uint8_t *d_positions, hipStream_t st);
+// leaves first .. first + k of level 0 (just uploaded, beyond the live count): *d_bad_leaf (preset to 0xFFFFFFFF) receives the lowest
+// tree index of one with a non-canonical limb
+hipError_t zk_tree_check_leaves(const uint8_t *d_nodes, const zk_tree::Plan &plan, uint64_t first, uint64_t k, uint32_t *d_bad_leaf, hipStream_t st);
+// after an append: `grown` is the plan at the new count, n_old the count before it, level 0 is in place. Rehashes the dirty nodes of
+// levels 1 .. depth and gathers the grown tree's snapshot nodes into d_snap_nodes (16 x 32 bytes); does neither when *d_bad_leaf is set.
+hipError_t zk_tree_rehash(uint8_t *d_nodes, const zk_tree::Plan &grown, uint64_t n_old, const uint32_t *d_bad_leaf, uint8_t *d_snap_nodes,
+                          const poseidon2::Params *p2, hipStream_t st);
+// the snapshot nodes of the tree as it stands
+hipError_t zk_tree_gather_snapshot(const uint8_t *d_nodes, const zk_tree::Plan &plan, uint8_t *d_snap_nodes, hipStream_t st);
+// zk_tree_open_paths on the tree as it stood at snap.count (checked against the plan on the host: zk_tree::check_open_at)
+hipError_t zk_tree_open_paths_at(const uint8_t *d_nodes, const zk_tree::Plan &plan, const zk_tree::Snapshot &snap, const uint64_t *d_indices,
+                                 uint64_t n, uint8_t *d_siblings, uint8_t *d_positions, hipStream_t st);
 #endif  // ZK_TREE_PLAN_ONLY

@@ -5,6 +5,12 @@
 //   zk_node_kernel        one thread per parent: four children sorted as 32-byte strings, sixteen limbs absorbed, three permutations
 //   zk_top_kernel         the levels that fit one workgroup, in one launch, a workgroup barrier between levels
 //   zk_open_kernel        one thread per (query, level): the group of four sorted, the running node taken out; no hashing
+// and for a tree that is appended to (zk_tree.hpp: dirty ranges, snapshots):
+//   zk_leaf_check_kernel  one thread per appended leaf hash: the canonicity test, before anything is rehashed
+//   zk_node_range_kernel  zk_node_kernel over the dirty parents of a level, while there are more than a workgroup of them
+//   zk_append_top_kernel  zk_top_kernel over the dirty ranges of every remaining level, then the snapshot of the grown tree
+//   zk_snapshot_kernel    the snapshot alone
+//   zk_open_at_kernel     zk_open_kernel on the tree as it stood at a snapshot
 //
 // The hash is the application hash of the Wormhole circuits: the pad `|| 1 || 0*` sponge with additive absorption over
 // poseidon2::permute_qp (qp-poseidon-core's set), the permutation behind p2_pad10_sponge_kernel<true>; the context's proof-system
@@ -151,6 +157,80 @@ __global__ void __launch_bounds__(256) zk_open_kernel(const u8 *nodes, zk_tree::
     positions[t] = (u8)pos;
 }
 
+// ---- the append-only tree (zk_tree.hpp: dirty ranges and snapshots) ----
+
+// thread j: leaf first + j of level 0, uploaded beyond the live count and not yet part of the tree, is tested before any node is rehashed
+__global__ void __launch_bounds__(256) zk_leaf_check_kernel(const u8 *level0, u64 first, u64 k, u32 *bad_leaf) {
+    const u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (j >= k) return;
+    if (key_noncanonical(load_key(level0 + 32 * (first + j)))) atomicMin(bad_leaf, (u32)(first + j));     // (indices are below 2^24)
+}
+
+// parents first .. first + cnt of a level: zk_node_kernel over a dirty range. Nothing is written once a new leaf was refused.
+__global__ void __launch_bounds__(256) zk_node_range_kernel(const u8 *in, u64 n_in, u8 *out, u64 first, u64 cnt, const u32 *bad_leaf,
+                                                            const poseidon2::Params *p2) {
+    const u64 t = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (t >= cnt || *bad_leaf != 0xFFFFFFFFu) return;
+    hash_parent(in, n_in, first + t, out, nullptr, *p2);
+}
+
+// snap[l - 1] = the last node of level l, l = 1 .. depth, the rest zero; by the first 16 threads of a workgroup
+__device__ __forceinline__ void gather_snapshot(const u8 *nodes, const zk_tree::Plan &plan, u8 *snap) {
+    if (threadIdx.x >= zk_tree::MAX_DEPTH) return;
+    const u32 l = threadIdx.x + 1;
+    const Key zero{0, 0, 0, 0};
+    store_key(snap + 32 * threadIdx.x, l <= plan.depth ? load_key(nodes + 32 * (plan.off[l] + plan.size[l] - 1)) : zero);
+}
+
+// zk_top_kernel over dirty ranges: `plan` is the tree at its new count, n_old the count before the append. Levels first + 1 .. depth,
+// each with at most blockDim.x dirty parents, by one workgroup with a barrier between levels; then the snapshot of the grown tree.
+// The refusal word is read by every thread before the first barrier and written by nobody here: the early return is uniform.
+__global__ void __launch_bounds__(256) zk_append_top_kernel(u8 *nodes, zk_tree::Plan plan, u32 first, u64 n_old, const u32 *bad_leaf, u8 *snap,
+                                                            const poseidon2::Params *p2) {
+    if (*bad_leaf != 0xFFFFFFFFu) return;
+    for (u32 l = first; l < plan.depth; l++) {
+        const u64 lo = n_old >> (2 * (l + 1)), cnt = plan.size[l + 1] - lo;
+        if (threadIdx.x < cnt) hash_parent(nodes + 32 * plan.off[l], plan.size[l], lo + threadIdx.x, nodes + 32 * plan.off[l + 1], nullptr, *p2);
+        __syncthreads();
+    }
+    gather_snapshot(nodes, plan, snap);
+}
+
+__global__ void __launch_bounds__(64) zk_snapshot_kernel(const u8 *nodes, zk_tree::Plan plan, u8 *snap) { gather_snapshot(nodes, plan, snap); }
+
+// node i of level l of the tree as it stood at snap.count, n_l = ceil(snap.count / 4^l) its size then: beyond the end the empty hash,
+// the last node of a level above the leaves from the snapshot (later appends may have rehashed it), every other node still resident
+__device__ __forceinline__ Key load_key_at(const u8 *level, const zk_tree::Snapshot &snap, u32 l, u64 n_l, u64 i) {
+    if (i >= n_l) return Key{0, 0, 0, 0};
+    if (l >= 1 && i == n_l - 1) {
+        const uint64_t *w = snap.last[l - 1];
+        return Key{__builtin_bswap64(w[0]), __builtin_bswap64(w[1]), __builtin_bswap64(w[2]), __builtin_bswap64(w[3])};
+    }
+    return load_key(level + 32 * i);
+}
+
+// zk_open_kernel against an earlier count of the same tree: the group and the running node go through load_key_at
+__global__ void __launch_bounds__(256) zk_open_at_kernel(const u8 *nodes, zk_tree::Plan plan, zk_tree::Snapshot snap, const u64 *indices, u64 n,
+                                                         u8 *siblings, u8 *positions) {
+    const u64 t = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (t >= n * plan.depth) return;
+    const u64 q = t / plan.depth;
+    const u32 l = (u32)(t - q * plan.depth);
+    const u64 idx = indices[q] >> (2 * l);       // checked against the snapshot's count on the host
+    const u64 n_l = (snap.count + ((1ull << (2 * l)) - 1)) >> (2 * l), g = idx & ~(u64)3;
+    const u8 *level = nodes + 32 * plan.off[l];
+    Key a = load_key_at(level, snap, l, n_l, g), b = load_key_at(level, snap, l, n_l, g + 1), c = load_key_at(level, snap, l, n_l, g + 2),
+        d = load_key_at(level, snap, l, n_l, g + 3);
+    const Key cur = load_key_at(level, snap, l, n_l, idx);
+    key_sort4(a, b, c, d);
+    const u32 pos = key_equal(a, cur) ? 0u : key_equal(b, cur) ? 1u : key_equal(c, cur) ? 2u : 3u;
+    u8 *o = siblings + 96 * t;
+    store_key(o, pos < 1 ? b : a);
+    store_key(o + 32, pos < 2 ? c : b);
+    store_key(o + 64, pos < 3 ? d : c);
+    positions[t] = (u8)pos;
+}
+
 }  // namespace
 
 hipError_t zk_tree_leaf_hashes(const uint8_t *d_records, uint64_t count, uint8_t *d_out, const poseidon2::Params *p2, hipStream_t st) {
@@ -182,5 +262,46 @@ hipError_t zk_tree_open_paths(const uint8_t *d_nodes, const zk_tree::Plan &plan,
     if (threads == 0) return hipSuccess;
     if ((threads + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(zk_open_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, d_nodes, plan, d_indices, n, d_siblings, d_positions);
+    return hipGetLastError();
+}
+
+hipError_t zk_tree_check_leaves(const uint8_t *d_nodes, const zk_tree::Plan &plan, uint64_t first, uint64_t k, uint32_t *d_bad_leaf, hipStream_t st) {
+    if (k == 0) return hipSuccess;
+    if (first > zk_tree::MAX_LEAVES || k > zk_tree::MAX_LEAVES - first) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zk_leaf_check_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, d_nodes + 32 * plan.off[0], first, k, d_bad_leaf);
+    return hipGetLastError();
+}
+
+hipError_t zk_tree_rehash(uint8_t *d_nodes, const zk_tree::Plan &grown, uint64_t n_old, const uint32_t *d_bad_leaf, uint8_t *d_snap_nodes,
+                          const poseidon2::Params *p2, hipStream_t st) {
+    if (grown.depth == 0 || grown.depth > zk_tree::MAX_DEPTH || grown.count > zk_tree::MAX_LEAVES || n_old >= grown.count) return hipErrorInvalidValue;
+    for (u32 l = 0; l < grown.depth; l++) {
+        u64 first, cnt;
+        zk_tree::dirty_range(n_old, grown.count - n_old, l + 1, first, cnt);
+        if (cnt <= 256) {                        // this level's dirty range and all above it (they only shrink) fit one workgroup
+            hipLaunchKernelGGL(zk_append_top_kernel, dim3(1), dim3(256), 0, st, d_nodes, grown, l, n_old, d_bad_leaf, d_snap_nodes, p2);
+            return hipGetLastError();
+        }
+        hipLaunchKernelGGL(zk_node_range_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, d_nodes + 32 * grown.off[l], grown.size[l],
+                           d_nodes + 32 * grown.off[l + 1], first, cnt, d_bad_leaf, p2);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipErrorInvalidValue;                 // not reached: level `depth` has one node
+}
+
+hipError_t zk_tree_gather_snapshot(const uint8_t *d_nodes, const zk_tree::Plan &plan, uint8_t *d_snap_nodes, hipStream_t st) {
+    if (plan.depth == 0 || plan.depth > zk_tree::MAX_DEPTH) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zk_snapshot_kernel, dim3(1), dim3(64), 0, st, d_nodes, plan, d_snap_nodes);
+    return hipGetLastError();
+}
+
+hipError_t zk_tree_open_paths_at(const uint8_t *d_nodes, const zk_tree::Plan &plan, const zk_tree::Snapshot &snap, const uint64_t *d_indices,
+                                 uint64_t n, uint8_t *d_siblings, uint8_t *d_positions, hipStream_t st) {
+    const u64 threads = n * plan.depth;
+    if (threads == 0) return hipSuccess;
+    if ((threads + 255) / 256 > 0x7FFFFFFFull || snap.count == 0 || snap.count > plan.count || snap.depth != plan.depth) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zk_open_at_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, d_nodes, plan, snap, d_indices, n, d_siblings,
+                       d_positions);
     return hipGetLastError();
 }

@@ -51,16 +51,16 @@ class LeafInputs(ctypes.Structure):
         ctypes.memmove(ctypes.byref(other), ctypes.byref(self), ctypes.sizeof(LeafInputs))
         return other
 
-    def set_zk_path(self, tree, index):
+    def set_zk_path(self, tree, index, at=None):
         """The Merkle path of leaf `index` of a ZkTree: zk_tree_root, zk_merkle_depth, the sorted siblings and the positions (levels past
-        the depth zeroed)."""
-        siblings, positions = tree.open([index])
+        the depth zeroed). at: a ZkSnapshot of the tree — the path and the root are those of the tree as it stood then."""
+        siblings, positions = tree.open([index], at=at)
         ctypes.memset(self.zk_merkle_siblings, 0, MAX_DEPTH * 96)
         ctypes.memset(self.zk_merkle_positions, 0, MAX_DEPTH)
         ctypes.memmove(self.zk_merkle_siblings, siblings.ctypes.data, tree.depth * 96)
         ctypes.memmove(self.zk_merkle_positions, positions.ctypes.data, tree.depth)
         self.zk_merkle_depth = tree.depth
-        return self.set32("zk_tree_root", tree.root)
+        return self.set32("zk_tree_root", tree.root if at is None else at.root)
 
 
 def _lib():
@@ -171,12 +171,29 @@ def zk_leaf_hash_batch(gpu, transfers):
     return out
 
 
+class ZkSnapshot(ctypes.Structure):
+    """qpgpu_zk_snapshot: the tree as it stood at `count` leaves — the last node of every level above the leaves. 528 bytes, kept by
+    the caller per block; ZkTree.open(indices, at=snapshot) opens paths that lead to its root."""
+    _fields_ = [("count", ctypes.c_uint64), ("depth", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("last", (ctypes.c_uint8 * 32) * MAX_DEPTH)]
+
+    @property
+    def root(self):
+        return bytes(self.last[self.depth - 1]) if 1 <= self.depth <= MAX_DEPTH else None
+
+    def __eq__(self, other):
+        return isinstance(other, ZkSnapshot) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+
 class ZkTree:
     """The chain's 4-ary ZK Merkle tree of one block, resident on the device (qpgpu_zk_tree_*): built from leaf hashes (`leaves`) or from
     the transfers themselves (`transfers`, hashed on the device too). depth = 0 is the smallest depth that holds the leaves. Raises
-    QpGpuError(QPGPU_EINVAL) for arguments the library refuses, a leaf hash with a non-canonical limb among them."""
+    QpGpuError(QPGPU_EINVAL) for arguments the library refuses, a leaf hash with a non-canonical limb among them.
+    capacity: room for that many leaves (qpgpu_zk_tree_build_reserved; depth = 0 is then the smallest depth that holds the capacity):
+    append() takes each later block's leaves, and open(indices, at=snapshot) opens paths at the root of an earlier block."""
 
-    def __init__(self, gpu, leaves=None, transfers=None, depth=0, flags=None):
+    def __init__(self, gpu, leaves=None, transfers=None, depth=0, flags=None, capacity=None):
         if (leaves is None) == (transfers is None):
             raise ValueError("ZkTree: give the leaf hashes or the transfers")
         data = _zk_hashes(leaves) if transfers is None else _zk_transfers(transfers)
@@ -185,14 +202,40 @@ class ZkTree:
             flags = 0 if transfers is None else ZK_TREE_FROM_TRANSFERS
         self.gpu, self.h = gpu, None
         h = ctypes.c_void_p(); err = ctypes.create_string_buffer(160)
-        rc = gpu.lib.qpgpu_zk_tree_build(gpu.ctx, data.ctypes.data if count else None, count, depth, flags, ctypes.byref(h), err)
+        if capacity is None:
+            rc = gpu.lib.qpgpu_zk_tree_build(gpu.ctx, data.ctypes.data if count else None, count, depth, flags, ctypes.byref(h), err)
+        else:
+            rc = gpu.lib.qpgpu_zk_tree_build_reserved(gpu.ctx, data.ctypes.data if count else None, count, capacity, depth, flags, ctypes.byref(h), err)
         if rc != 0:
             assert not h.value, "a refused build leaves no handle"
             raise QpGpuError(rc, err.value.decode())
         self.h = h
         self.depth = int(gpu.lib.qpgpu_zk_tree_depth(h))
         self.leaf_count = int(gpu.lib.qpgpu_zk_tree_leaf_count(h))
+        self.capacity = int(gpu.lib.qpgpu_zk_tree_capacity(h))
         self._root = None
+
+    def append(self, leaves=None, transfers=None):
+        """More leaves behind the last (qpgpu_zk_tree_append), as leaf hashes or as transfers: the ZkSnapshot after the append. A refused
+        append (QpGpuError(QPGPU_EINVAL): nothing to append, no room, a tree built without capacity, a non-canonical leaf hash) leaves the
+        tree as it was."""
+        if (leaves is None) == (transfers is None):
+            raise ValueError("ZkTree.append: give the leaf hashes or the transfers")
+        data = _zk_hashes(leaves) if transfers is None else _zk_transfers(transfers)
+        k = data.shape[0]
+        snap = ZkSnapshot(); err = ctypes.create_string_buffer(160)
+        rc = self.gpu.lib.qpgpu_zk_tree_append(self.h, data.ctypes.data if k else None, k, 0 if transfers is None else ZK_TREE_FROM_TRANSFERS, ctypes.addressof(snap), err)
+        if rc != 0:
+            raise QpGpuError(rc, err.value.decode())
+        self.leaf_count = int(self.gpu.lib.qpgpu_zk_tree_leaf_count(self.h))
+        self._root = None
+        return snap
+
+    def snapshot(self):
+        """The ZkSnapshot of the tree as it stands (qpgpu_zk_tree_snapshot)."""
+        snap = ZkSnapshot()
+        self.gpu._check(self.gpu.lib.qpgpu_zk_tree_snapshot(self.h, ctypes.addressof(snap)))
+        return snap
 
     @property
     def root(self):
@@ -213,11 +256,15 @@ class ZkTree:
         self.gpu._check(self.gpu.lib.qpgpu_zk_tree_read_level(self.h, level, first, n, out.ctypes.data))
         return out
 
-    def open(self, indices):
-        """The paths of many leaves in one call: (siblings uint8 [n, depth, 3, 32] in sorted order, positions uint8 [n, depth])."""
+    def open(self, indices, at=None):
+        """The paths of many leaves in one call: (siblings uint8 [n, depth, 3, 32] in sorted order, positions uint8 [n, depth]).
+        at: a ZkSnapshot of this tree — the paths of the tree as it stood then, leading to at.root (qpgpu_zk_tree_open_at)."""
         idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
         sib = np.empty((idx.size, self.depth, 3, 32), dtype=np.uint8); pos = np.empty((idx.size, self.depth), dtype=np.uint8)
-        self.gpu._check(self.gpu.lib.qpgpu_zk_tree_open(self.h, idx.ctypes.data, idx.size, sib.ctypes.data, pos.ctypes.data))
+        if at is None:
+            self.gpu._check(self.gpu.lib.qpgpu_zk_tree_open(self.h, idx.ctypes.data, idx.size, sib.ctypes.data, pos.ctypes.data))
+        else:
+            self.gpu._check(self.gpu.lib.qpgpu_zk_tree_open_at(self.h, ctypes.addressof(at), idx.ctypes.data, idx.size, sib.ctypes.data, pos.ctypes.data))
         return sib, pos
 
     def close(self):
