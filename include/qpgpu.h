@@ -175,6 +175,13 @@ int qpgpu_circuit_set_blinding_seed(qpgpu_circuit *c, uint64_t seed);
  * fails to verify (reference tests catch the panic, wormhole/tests/src/circuit/nullifier_tests.rs:53-58). Costs one
  * extra pass over the trace and one stream sync. */
 int qpgpu_circuit_set_witness_check(qpgpu_circuit *c, int on);
+/* Quotient stage: by default a circuit whose gates, the hash gates aside, are Constant, PublicInput, Arithmetic and BaseSum<2>
+ * on routed wires (the leaf circuit) gets its permutation terms and those gates from one kernel; every other circuit, and any
+ * circuit after on = 0, from the two kernels that pass over the wires once each. Same proof bytes either way. The default at
+ * load is 1, or 0 under QPGPU_QUOTIENT_FUSED=0. qpgpu_circuit_quotient_info: the switch, and whether the one kernel is what
+ * the next proof of this circuit runs (either pointer may be NULL). */
+int qpgpu_circuit_set_quotient_fused(qpgpu_circuit *c, int on);
+int qpgpu_circuit_quotient_info(const qpgpu_circuit *c, int *fused_enabled, int *fused_selected);
 size_t qpgpu_proof_size(const qpgpu_circuit *c);   /* bytes written by qpgpu_prove for this circuit */
 /*
  * prove(): wires = the full witness matrix (num_wires x 2^degree_bits, column-major, as

@@ -103,6 +103,8 @@ def load_library():
         "qpgpu_proof_size": (c.c_size_t, [vp]),
         "qpgpu_circuit_set_blinding_seed": (c.c_int, [vp, c.c_uint64]),
         "qpgpu_circuit_set_witness_check": (c.c_int, [vp, c.c_int]),
+        "qpgpu_circuit_set_quotient_fused": (c.c_int, [vp, c.c_int]),
+        "qpgpu_circuit_quotient_info": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_int)]),
         "qpgpu_circuit_gate_rows": (c.c_int, [vp, c.c_uint, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "qpgpu_prove": (c.c_int, [vp, u64p, u64p, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "qpgpu_prove_dev": (c.c_int, [vp, u64p, u64p, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
@@ -486,6 +488,17 @@ class Circuit:
     def set_witness_check(self, on=True):
         """Make prove() return QPGPU_EUNSAT (-4) for a witness that violates a gate or copy constraint."""
         self.gpu._check(self.gpu.lib.qpgpu_circuit_set_witness_check(self.h, 1 if on else 0))
+
+    def set_quotient_fused(self, on=True):
+        """Quotient stage: permutation terms and wire-local gates in one kernel where the gate list allows it (the default), or
+        always the two kernels. Same proof bytes."""
+        self.gpu._check(self.gpu.lib.qpgpu_circuit_set_quotient_fused(self.h, 1 if on else 0))
+
+    def quotient_info(self):
+        """(the switch, whether the one-pass kernel is what the next proof of this circuit runs)."""
+        a, b = ctypes.c_int(), ctypes.c_int()
+        self.gpu._check(self.gpu.lib.qpgpu_circuit_quotient_info(self.h, ctypes.byref(a), ctypes.byref(b)))
+        return bool(a.value), bool(b.value)
 
     def set_blinding_seed(self, seed):
         """Zero-knowledge packs: fixes the salts of the next proof (reproducible bytes)."""

@@ -46,6 +46,8 @@ struct qpgpu_circuit {
     Stager stage;                    // pinned host staging for the small per-proof tables (no sync on upload)
     bool seed_set = false;
     bool check_witness = false;
+    bool quotient_fused = true;          // stage s6: quotient_perm_gates_kernel where the gate list allows it (QPGPU_QUOTIENT_FUSED at load, qpgpu_circuit_set_quotient_fused)
+    bool quotient_plain_map = false;     // QPGPU_QUOTIENT_XCD_MAP=0 at load: that kernel's workgroups in proof-major order (measurement)
     gl::u64 *d_check = nullptr;          // [max_batch][2]: first bad row, permutation flag
     gl::u64 blinding_seed = 0;           // test hook: proof b of the next batch uses the key derived from blinding_seed + b
     WitnessPlan *wplan = nullptr;    // stage s1, built on first use (witness_plan.cpp)

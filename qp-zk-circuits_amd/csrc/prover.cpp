@@ -250,6 +250,11 @@ int qpgpu_circuit_load_batch(qpgpu_ctx *ctx, const uint64_t *pack_words, size_t 
         if (e != hipSuccess) return fail(ctx->hip_fail(e, "hipHostMalloc(stage)"));
         c->stage.h = (u64 *)hp;
     }
+    // Stage s6 takes the permutation terms and the wire-local gates in one kernel where the gate list allows it
+    // (pk_quotient_fused_gates). QPGPU_QUOTIENT_FUSED=0 starts the circuit on the two launches instead (qpgpu_circuit_set_quotient_fused
+    // switches later); QPGPU_QUOTIENT_XCD_MAP=0 keeps the one kernel but drops its XCD-grouped workgroup order, for measurements.
+    if (const char *e = getenv("QPGPU_QUOTIENT_FUSED")) if (*e == '0') c->quotient_fused = false;
+    if (const char *e = getenv("QPGPU_QUOTIENT_XCD_MAP")) if (*e == '0') c->quotient_plain_map = true;
     // routing knob of stage s1, read here like the staging hook above: which generator form the hash-gate rows of a wide dependency
     // level get (witness_plan.cpp: generate_batch). 0: always the lane-cooperative one, 1: always a thread per row, unset: by width.
     if (const char *e = getenv("QPGPU_WITNESS_WIDE_ROWS")) if (*e == '0' || *e == '1') c->witness_wide_rows = *e - '0';
@@ -275,6 +280,22 @@ size_t qpgpu_circuit_num_public_inputs(const qpgpu_circuit *c) { return c ? (siz
 int qpgpu_circuit_set_witness_check(qpgpu_circuit *c, int on) {
     if (!c) return QPGPU_EINVAL;
     c->check_witness = on != 0;
+    return QPGPU_OK;
+}
+
+int qpgpu_circuit_set_quotient_fused(qpgpu_circuit *c, int on) {
+    if (!c) return QPGPU_EINVAL;
+    c->quotient_fused = on != 0;
+    return QPGPU_OK;
+}
+
+int qpgpu_circuit_quotient_info(const qpgpu_circuit *c, int *fused_enabled, int *fused_selected) {
+    if (!c) return QPGPU_EINVAL;
+    const CircuitPack &p = c->pack;
+    const bool fits = pk_quotient_fused_gates(c->h_gates.data(), (uint32_t)c->h_gates.size(), (uint32_t)p.num_routed_wires,
+                                              (uint32_t)p.quotient_degree_factor, (uint32_t)p.num_partial_products + 1, nullptr);
+    if (fused_enabled) *fused_enabled = c->quotient_fused ? 1 : 0;
+    if (fused_selected) *fused_selected = c->quotient_fused && fits ? 1 : 0;
     return QPGPU_OK;
 }
 
@@ -429,6 +450,7 @@ static int prove_batch_impl(qpgpu_circuit *c, uint32_t nb, const u64 *d_wires, c
     qa.num_routed = (uint32_t)R; qa.chunk = (uint32_t)p.quotient_degree_factor; qa.nchunks = nchunks; qa.sig0 = (uint32_t)sig0;
     qa.num_selectors = (uint32_t)p.num_selectors; qa.num_gates = (uint32_t)p.gates.size(); qa.nterms = (uint32_t)nterms;
     qa.batch = nb; qa.ps_wires = c->wires.ps_lde; qa.ps_zs = c->zs.ps_lde; qa.ps_small = SW; qa.ps_acc = (u64)nch * lde_n; qa.ps_out = (u64)nch * q_n;
+    qa.fused = c->quotient_fused ? 1 : 0; qa.fused_plain_map = c->quotient_plain_map ? 1 : 0;
     QP_HIP(ctx, pk_quotient(qa, c->h_gates.data(), st));
     // coset_ifft(g) on the quotient domain: ifft then scale coefficient i by g^-i; the qdf*n coefficients of a challenge
     // are its qdf chunks of n, contiguous

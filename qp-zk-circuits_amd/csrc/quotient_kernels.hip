@@ -2,6 +2,8 @@
 // runs the same gate kernels on the trace rows.
 //   quotient_perm_kernel                                  L_0(x)(Z(x) - 1) and the partial-product checks
 //   quotient_gates_kernel                                 every gate but the two hash gates
+//   quotient_perm_gates_kernel                            both of the above in one pass over the routed wires, for circuits whose
+//                                                         other gates are Constant, PublicInput, Arithmetic and BaseSum<2> only
 //   quotient_poseidon_kernel, quotient_poseidon2_kernel   the hash gates, linear layers folded into the alpha weights by
 //   quotient_fold_sweep_kernel                            (quotient_fold.hpp: Schedule, sweep)
 //   quotient_hash_rounds_kernel                           the hash gates round by round: the forward walk of the same Schedule
@@ -15,6 +17,7 @@
 #include "gl64.hpp"
 #include "poseidon.hpp"
 #include "quotient_kernels.hpp"
+#include "quotient_map.hpp"
 
 using gl::e2;
 using gl::u32;
@@ -340,6 +343,163 @@ __global__ void __launch_bounds__(256) quotient_gates_kernel(QuotientArgs a, u32
     }
 }
 
+// (1+2) The permutation terms and the wire-local gates (Constant, PublicInput, Arithmetic, BaseSum<2>) in one pass over the routed
+// wires: what quotient_perm_kernel and quotient_gates_kernel leave in acc (or, without a hash gate, in out) for a circuit whose
+// other gates are all of these four types and read routed wires only (fused_gates below decides). The walk goes by the permutation
+// argument's chunks of FUSED_CHUNK wires, from the last chunk down to chunk 0: a chunk's wires and sigmas are loaded once, serve
+// pn and pd of every challenge, and while the wires are in registers the gates take what they need of them: Arithmetic operations
+// 2cc and 2cc+1, the BaseSum limbs (top limb first, so the limb sum is the Horner value quotient_gates_kernel forms; chunk 0 ends
+// with the sum wire), and in chunk 0 the Constant and PublicInput wires. One Acc192 per gate and challenge; filters and the add
+// into the running sums once at the end. The 1-D grid's workgroup id -> (tile, proof) is qmap::place (quotient_map.hpp).
+constexpr u32 FUSED_CHUNK = 8;
+constexpr u32 FUSED_NONE = 0xFFFFFFFFu;
+
+template <int NCH>
+__global__ void __launch_bounds__(256, NCH <= 2 ? 4 : 2) quotient_perm_gates_kernel(QuotientArgs a, FusedGates fg, u32 tiles, u32 grouped, int finalize) {
+    const qmap::Place pl = qmap::place(blockIdx.x, tiles, a.batch, grouped != 0);
+    if (!pl.valid) return;
+    const u64 j = pl.tile * (u64)blockDim.x + threadIdx.x;
+    if (j >= a.q_n) return;
+    {
+        const u64 pr = pl.proof;
+        a.wires += pr * a.ps_wires; a.zs_pp += pr * a.ps_zs;
+        a.alpha_pows += pr * a.ps_small; a.beta_k_is += pr * a.ps_small; a.betas += pr * a.ps_small; a.gammas += pr * a.ps_small; a.pi_hash += pr * a.ps_small;
+        a.acc += pr * a.ps_acc; a.out += pr * a.ps_out;
+    }
+    const u32 logL = a.log_lde, R = a.num_routed, nchunks = a.nchunks, npp = nchunks - 1;
+    const u64 i = brev32((u32)j, logL);
+    const u64 jn = brev32((u32)((i + a.rate) & (a.lde_n - 1)), logL);   // slot of the next row g*x
+    const u64 x = a.x_coset[j], S = a.lde_n;
+    const u64 *consts_base = a.cs + (u64)a.num_selectors * S + j;
+    const u64 *gp = a.alpha_pows + NCH + NCH * nchunks;                 // weights of the gate constraints
+    const u32 n_ops = fg.n_ops, n_limbs = fg.n_limbs;
+    gl::Acc192 acc[NCH], asum[NCH], bsum[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) { acc[c] = gl::acc_zero(); asum[c] = gl::acc_zero(); bsum[c] = gl::acc_zero(); }
+    u64 nxt[NCH];       // the partial product behind the chunk being walked: Z(g x) behind the last one
+    {
+        const u64 l0 = a.l0_coset[j];
+#pragma unroll
+        for (int k = 0; k < NCH; k++) {
+            const u64 term = gl::mul(l0, gl::sub(a.zs_pp[(u64)k * S + j], 1));
+#pragma unroll
+            for (int c = 0; c < NCH; c++) gl::acc_mul(acc[c], term, a.alpha_pows[(u64)c * a.nterms + k]);
+            nxt[k] = a.zs_pp[(u64)k * S + jn];
+        }
+    }
+    u64 s2 = 0;         // the BaseSum limbs seen so far, top limb first (Horner)
+    u64 gsum[NCH];      // filtered sums of the gates that are done
+#pragma unroll
+    for (int c = 0; c < NCH; c++) gsum[c] = 0;
+    auto fold_gate = [&](u32 gi, const gl::Acc192 (&sum)[NCH]) {
+        const u64 f = gate_filter(a, gi, a.cs[(u64)a.gates[gi].selector_index * S + j]);
+#pragma unroll
+        for (int c = 0; c < NCH; c++) gsum[c] = gl::add(gsum[c], gl::mul(f, gl::acc_reduce(sum[c])));
+    };
+    // One chunk per turn, from the last one down. A whole chunk is one straight run of code: its eight wires and eight sigmas are
+    // loaded together ahead of the arithmetic, and what a gate does not want of a wire goes in with weight zero (a scalar select)
+    // instead of round a branch, which would put every wire's loads behind the wire before it. Only the last chunk can hold fewer
+    // than FUSED_CHUNK wires (m of them) and goes wire by wire. (Skipping the limb work of the chunks past the last limb, or the
+    // Arithmetic work past the last operation, behind chunk-uniform branches costs the two-challenge kernel 20 to 28 bytes of
+    // scratch at four waves per SIMD: profiles/quotient_pass_notes.txt.)
+    auto wire = [&](u32 r, u64 v, u64 sg, u64 (&pn)[NCH], u64 (&pd)[NCH]) {
+#pragma unroll
+        for (int k = 0; k < NCH; k++) {
+            const u64 sid = gl::mul(a.beta_k_is[k * R + r], x);
+            const u64 ssg = gl::mul(a.betas[k], sg);
+            pn[k] = gl::mul(pn[k], gl::add(gl::add(v, sid), a.gammas[k]));
+            pd[k] = gl::mul(pd[k], gl::add(gl::add(v, ssg), a.gammas[k]));
+        }
+        // BaseSumGate<2>: limb l on wire 1 + l, constraint 1 + l (the sum, wire 0, after the walk)
+        const bool limb = r >= 1 && r <= n_limbs;
+        const u64 twice = gl::add(gl::add(s2, s2), v), cst = gl::mul(v, gl::sub(v, 1));
+        s2 = limb ? twice : s2;
+#pragma unroll
+        for (int c = 0; c < NCH; c++) { const u64 wt = gp[(u64)c * a.nterms + (limb ? r : 0)]; gl::acc_mul(bsum[c], cst, limb ? wt : 0); }
+    };
+    // ArithmeticGate: out - (c0 m0 m1 + c1 addend), operation q on wires 4q..4q+3; c0, c1 = the first two constant columns
+    auto arith = [&](u32 q, u64 m0, u64 m1, u64 ad, u64 out, u64 c0, u64 c1) {
+        const bool op = q < n_ops;
+        const u64 cst = gl::sub(out, gl::add(gl::mul(gl::mul(m0, m1), c0), gl::mul(ad, c1)));
+#pragma unroll
+        for (int c = 0; c < NCH; c++) { const u64 wt = gp[(u64)c * a.nterms + (op ? q : 0)]; gl::acc_mul(asum[c], cst, op ? wt : 0); }
+    };
+#pragma unroll 1
+    for (u32 cc = nchunks; cc-- > 0; ) {
+        const u32 r0 = cc * FUSED_CHUNK, m = R - r0 < FUSED_CHUNK ? R - r0 : FUSED_CHUNK;
+        u64 w[FUSED_CHUNK], pn[NCH], pd[NCH], prv[NCH];
+#pragma unroll
+        for (int k = 0; k < NCH; k++) { pn[k] = 1; pd[k] = 1; prv[k] = cc == 0 ? a.zs_pp[(u64)k * S + j] : a.zs_pp[((u64)NCH + (u64)k * npp + cc - 1) * S + j]; }
+        const u64 c0 = consts_base[0], c1 = consts_base[S];
+        if (m == FUSED_CHUNK) {
+            u64 sg[FUSED_CHUNK];
+#pragma unroll
+            for (u32 t = 0; t < FUSED_CHUNK; t++) { w[t] = a.wires[(u64)(r0 + t) * S + j]; sg[t] = a.cs[(u64)(a.sig0 + r0 + t) * S + j]; }
+#pragma unroll
+            for (int t = FUSED_CHUNK - 1; t >= 0; t--) {
+                wire(r0 + t, w[t], sg[t], pn, pd);
+                if (t % 4 == 0) arith((r0 + t) / 4, w[t], w[t + 1], w[t + 2], w[t + 3], c0, c1);
+            }
+        } else {
+#pragma unroll
+            for (int t = FUSED_CHUNK - 1; t >= 0; t--) {
+                w[t] = 0;
+                if ((u32)t < m) { w[t] = a.wires[(u64)(r0 + t) * S + j]; wire(r0 + t, w[t], a.cs[(u64)(a.sig0 + r0 + t) * S + j], pn, pd); }
+                if (t % 4 == 0 && (r0 + t) / 4 < n_ops) arith((r0 + t) / 4, w[t], w[t + 1], w[t + 2], w[t + 3], c0, c1);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NCH; k++) {
+            const u64 term = gl::sub(gl::mul(prv[k], pn[k]), gl::mul(nxt[k], pd[k]));
+#pragma unroll
+            for (int c = 0; c < NCH; c++) gl::acc_mul(acc[c], term, a.alpha_pows[(u64)c * a.nterms + NCH + k * nchunks + cc]);
+            nxt[k] = prv[k];
+        }
+        if (cc == 0) {       // chunk 0 is whole: the gates that live on its wires, and the end of the two that ran along
+            if (fg.base_sum != FUSED_NONE) {
+                const u64 cst = gl::sub(s2, w[0]);
+#pragma unroll
+                for (int c = 0; c < NCH; c++) gl::acc_mul(bsum[c], cst, gp[(u64)c * a.nterms]);
+                fold_gate(fg.base_sum, bsum);
+            }
+            if (fg.arithmetic != FUSED_NONE) fold_gate(fg.arithmetic, asum);
+            if (fg.constant != FUSED_NONE) {      // ConstantGate: const_i - wire_i
+                gl::Acc192 sum[NCH];
+#pragma unroll
+                for (int c = 0; c < NCH; c++) sum[c] = gl::acc_zero();
+#pragma unroll
+                for (u32 q = 0; q < 4; q++)
+                    if (q < fg.n_consts) {
+                        const u64 cst = gl::sub(consts_base[(u64)q * S], w[q]);
+#pragma unroll
+                        for (int c = 0; c < NCH; c++) gl::acc_mul(sum[c], cst, gp[(u64)c * a.nterms + q]);
+                    }
+                fold_gate(fg.constant, sum);
+            }
+            if (fg.public_input != FUSED_NONE) {  // PublicInputGate: wire_i - pi_hash_i
+                gl::Acc192 sum[NCH];
+#pragma unroll
+                for (int c = 0; c < NCH; c++) sum[c] = gl::acc_zero();
+#pragma unroll
+                for (u32 q = 0; q < 4; q++) {
+                    const u64 cst = gl::sub(w[q], a.pi_hash[q]);
+#pragma unroll
+                    for (int c = 0; c < NCH; c++) gl::acc_mul(sum[c], cst, gp[(u64)c * a.nterms + q]);
+                }
+                fold_gate(fg.public_input, sum);
+            }
+        }
+    }
+    if (finalize) {
+        const u64 zi = a.zh_inv[i & (a.rate - 1)];
+#pragma unroll
+        for (int c = 0; c < NCH; c++) a.out[(u64)c * a.q_n + (i >> a.q_shift)] = gl::canon(gl::mul(gl::add(gl::acc_reduce(acc[c]), gsum[c]), zi));
+    } else {
+#pragma unroll
+        for (int c = 0; c < NCH; c++) a.acc[(u64)c * S + j] = gl::add(gl::acc_reduce(acc[c]), gsum[c]);
+    }
+}
+
 // (3), (4) the two hash gates at one point, round by round (QuotientArgs::fold == nullptr): every constraint of qfold::walk weighted
 // by alpha_c^(t0+q) on the fly. PoseidonGate (plonky2::gates::poseidon): wires 0..11 input, 12..23 output, 24 swap, 25..28 delta,
 // 29..64 / 65..86 / 87..134 S-box inputs of the full / partial / full rounds, 123 constraints; the partial rounds run in the textbook
@@ -543,6 +703,27 @@ hipError_t pk_quotient_fold_sweep(const QuotientArgs &a, const GateDev *host_gat
     hipLaunchKernelGGL(quotient_fold_sweep_kernel, dim3(fa.ngates, fa.nch, fa.batch), dim3(64), 0, st, fa);
     return hipGetLastError();
 }
+// Which circuits quotient_perm_gates_kernel serves: every gate that carries constraints and is no hash gate is a ConstantGate, a
+// PublicInputGate, an ArithmeticGate or a BaseSumGate<2>, one of each at most (the kernel keeps one sum per type), and every wire
+// they read is a routed one, i.e. falls into a chunk of the walk: Constant and PublicInput wires into the first four of chunk 0. The chunks are the
+// kernel's FUSED_CHUNK wide. The base of a BaseSumGate is not looked at: the loader admits base 2 only as this gate type
+// (circuit.cpp). Everything else (the recursion gate set, the extension arithmetic, a wide RandomAccess) keeps the
+// two launches.
+bool pk_quotient_fused_gates(const GateDev *host_gates, uint32_t num_gates, uint32_t num_routed, uint32_t chunk, uint32_t nchunks, FusedGates *out) {
+    FusedGates fg{FUSED_NONE, FUSED_NONE, FUSED_NONE, FUSED_NONE, 0, 0, 0};
+    if (chunk != FUSED_CHUNK || num_routed < FUSED_CHUNK || nchunks != (num_routed + FUSED_CHUNK - 1) / FUSED_CHUNK) return false;
+    for (u32 i = 0; i < num_gates; i++) {
+        const GateDev &g = host_gates[i];
+        if (g.num_constraints == 0 || g.type == GATE_POSEIDON || g.type == GATE_POSEIDON2) continue;
+        if (g.type == GATE_CONSTANT && fg.constant == FUSED_NONE && g.param0 <= 4) { fg.constant = i; fg.n_consts = g.param0; }
+        else if (g.type == GATE_PUBLIC_INPUT && fg.public_input == FUSED_NONE) fg.public_input = i;
+        else if (g.type == GATE_ARITHMETIC && fg.arithmetic == FUSED_NONE && g.param0 >= 1 && (uint64_t)4 * g.param0 <= num_routed) { fg.arithmetic = i; fg.n_ops = g.param0; }
+        else if (g.type == GATE_BASE_SUM && fg.base_sum == FUSED_NONE && g.param0 >= 1 && (uint64_t)g.param0 + 1 <= num_routed) { fg.base_sum = i; fg.n_limbs = g.param0; }
+        else return false;
+    }
+    if (out) *out = fg;
+    return true;
+}
 // The stage's launches: the permutation terms (perm), every other gate, then the hash gates (heavy, one launch each); with
 // `finalize` the last of them also applies 1/Z_H and stores. Without either: the gate sums alone, for the witness check.
 template <int NCH>
@@ -550,10 +731,18 @@ static hipError_t quotient_launch(const QuotientArgs &a, const GateDev *host_gat
     dim3 b(256), g((unsigned)((a.q_n + 255) / 256), 1, a.batch);
     const u32 t0 = a.nch + a.nch * a.nchunks;
     const u32 n_hash = pk_count_hash_gates(host_gates, a.num_gates);
-    if (perm) hipLaunchKernelGGL((quotient_perm_kernel<NCH>), g, b, 0, st, a);
     const int fin_gates = finalize && n_hash == 0;
-    if (wide_random_access(a, host_gates)) hipLaunchKernelGGL((quotient_gates_kernel<NCH, true>), g, b, 0, st, a, t0, fin_gates);
-    else hipLaunchKernelGGL((quotient_gates_kernel<NCH, false>), g, b, 0, st, a, t0, fin_gates);
+    FusedGates fg;
+    const u32 tiles = g.x;
+    const bool grouped = a.fused_plain_map == 0;
+    if (perm && a.fused && pk_quotient_fused_gates(host_gates, a.num_gates, a.num_routed, a.chunk, a.nchunks, &fg) &&
+        qmap::grid_size(tiles, a.batch, grouped) <= 0x7FFFFFFFull) {
+        hipLaunchKernelGGL((quotient_perm_gates_kernel<NCH>), dim3((unsigned)qmap::grid_size(tiles, a.batch, grouped)), b, 0, st, a, fg, tiles, grouped ? 1u : 0u, fin_gates);
+    } else {
+        if (perm) hipLaunchKernelGGL((quotient_perm_kernel<NCH>), g, b, 0, st, a);
+        if (wide_random_access(a, host_gates)) hipLaunchKernelGGL((quotient_gates_kernel<NCH, true>), g, b, 0, st, a, t0, fin_gates);
+        else hipLaunchKernelGGL((quotient_gates_kernel<NCH, false>), g, b, 0, st, a, t0, fin_gates);
+    }
     u32 slot = 0;
     for (u32 i = 0; i < a.num_gates; i++)
         if (is_hash_gate(host_gates[i])) {

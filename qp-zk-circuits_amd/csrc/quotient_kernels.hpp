@@ -31,7 +31,14 @@ struct QuotientArgs {
     // for this batch's alphas; nullptr = the hash-gate kernel walks the rounds with their linear layers (qfold::walk, the fold's A/B partner)
     const uint64_t *fold;
     uint64_t ps_fold;
+    // pk_quotient: 1 = quotient_perm_gates_kernel where the gate list allows it (pk_quotient_fused_gates), 0 = always the two
+    // launches; fused_plain_map = 1 gives that kernel the proof-major workgroup order of the (tiles, 1, batch) grids (measurement)
+    uint32_t fused, fused_plain_map;
 };
+
+// the gates quotient_perm_gates_kernel evaluates on its walk: their indices in the gate list (0xFFFFFFFF = the circuit has none)
+// and sizes (ConstantGate constants, ArithmeticGate operations, BaseSumGate limbs)
+struct FusedGates { uint32_t constant, public_input, arithmetic, base_sum, n_consts, n_ops, n_limbs; };
 
 // the backward walk that fills QuotientArgs::fold: one workgroup per (hash gate, challenge, proof)
 struct FoldSweepArgs {
@@ -45,6 +52,8 @@ struct FoldSweepArgs {
 };
 
 hipError_t pk_quotient(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st);
+// true (and *out, unless nullptr): the circuit's permutation terms and non-hash gates go through quotient_perm_gates_kernel
+bool pk_quotient_fused_gates(const GateDev *host_gates, uint32_t num_gates, uint32_t num_routed, uint32_t chunk, uint32_t nchunks, FusedGates *out);
 // hash gates of the list that carry constraints; more than qfold::MAX_GATES: the circuit runs without the fold
 uint32_t pk_count_hash_gates(const GateDev *host_gates, uint32_t num_gates);
 // fills a.fold for the batch from its alpha powers (run before pk_quotient / pk_gate_sums whenever QuotientArgs::fold is set)
