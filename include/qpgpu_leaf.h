@@ -233,9 +233,36 @@ int qpgpu_zk_tree_snapshot(const qpgpu_zk_tree *t, qpgpu_zk_snapshot *out);
 /* qpgpu_zk_tree_open against the tree as it stood at the snapshot: what qpgpu_zk_tree_open returns on a tree built from the first
  * snap->count leaves at the same depth, leading to the root snap->last[depth - 1]. QPGPU_EINVAL: snap->count = 0 or above the tree's
  * leaf count, snap->depth other than the tree's, an index >= snap->count (the message names the entry). The snapshot must be one this
- * tree gave; that is not checked, and a forged or foreign snapshot yields paths that do not verify against any root of the chain. */
+ * tree gave; that is not checked, and a forged or foreign snapshot yields paths that do not verify against any root of the chain
+ * (qpgpu_zk_tree_snapshot_check checks it; qpgpu_zk_tree_open_at_counts needs no snapshot). */
 int qpgpu_zk_tree_open_at(const qpgpu_zk_tree *t, const qpgpu_zk_snapshot *snap, const uint64_t *indices, size_t n, uint8_t *siblings_out,
                           uint8_t *positions_out);
+
+/* ---- earlier roots without a kept snapshot, many roots per call, reorgs ----
+ * The snapshot at count n is determined by the tree alone: every node of level l >= 1 but the level's last is resident and unchanged, and
+ * the last one is the hash of its children of level l - 1 as they stood at n: the empty hash beyond ceil(n / 4^(l-1)), the node derived
+ * one step below for the level's last child, the resident node otherwise. The device derives it in `depth` node hashes per count, so
+ * a caller keeps no snapshots, a kept one can be checked against the tree, and a reorg is the derived snapshot written back. */
+/* the snapshots of the tree as it stood at counts[i] leaves (1 .. the leaf count), i < m, derived from the resident nodes:
+ * equal, byte for byte, to what qpgpu_zk_tree_append / _snapshot returned when the tree had that count. m = 0 returns 0 at once.
+ * QPGPU_EINVAL names the first entry that is 0 or above the leaf count; out is then untouched. */
+int qpgpu_zk_tree_snapshots_at(const qpgpu_zk_tree *t, const uint64_t *counts, size_t m, qpgpu_zk_snapshot *out);
+/* 0 when snap is the snapshot this tree gives at snap->count; QPGPU_EINVAL otherwise, the message ("snapshot differs ...") naming the
+ * first differing level (or the count / depth refusal of qpgpu_zk_tree_open_at). A snapshot kept from a fork that a truncate has since
+ * abandoned differs once the count is reached again: this is the check that qpgpu_zk_tree_open_at leaves to its caller. */
+int qpgpu_zk_tree_snapshot_check(const qpgpu_zk_tree *t, const qpgpu_zk_snapshot *snap);
+/* qpgpu_zk_tree_open_at with a count per path and no snapshot kept by the caller: path i is opened against the tree as it stood at
+ * counts[i] leaves. roots_out (n x 32 bytes, may be NULL): the root each path leads to. One upload, two launches (the snapshots of the
+ * distinct counts, the paths) and one synchronisation, however many distinct counts there are. n = 0 returns 0 at once. QPGPU_EINVAL
+ * names the first entry with counts[i] = 0, counts[i] above the leaf count, or indices[i] >= counts[i]; the outputs are then untouched. */
+int qpgpu_zk_tree_open_at_counts(const qpgpu_zk_tree *t, const uint64_t *counts, const uint64_t *indices, size_t n,
+                                 uint8_t *siblings_out, uint8_t *positions_out, uint8_t *roots_out);
+/* a reorg: back to the first n leaves. Afterwards the tree equals the one qpgpu_zk_tree_build(_reserved) gives for those leaves at
+ * the same depth and capacity (every level, the root, every path, qpgpu_zk_tree_snapshot), and appends continue from n. n = the
+ * leaf count is allowed and changes nothing. QPGPU_EINVAL with the tree exactly as before: n = 0, n above the leaf count.
+ * Allowed on any tree; one from qpgpu_zk_tree_build still refuses appends. snap_out (may be NULL): the snapshot at n.
+ * err: QPGPU_LEAF_ERR_CAP bytes, may be NULL. */
+int qpgpu_zk_tree_truncate(qpgpu_zk_tree *t, size_t n, qpgpu_zk_snapshot *snap_out, char *err);
 
 /* ---- the leaf circuit's constraints, natively ----
  * What WormholeCircuit constrains about a CircuitInputs (wormhole/circuit/src/circuit.rs:233-323 and the fragments it wires:

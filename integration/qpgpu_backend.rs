@@ -154,6 +154,13 @@ extern "C" {
     pub fn qpgpu_zk_tree_snapshot(t: *const QpgpuZkTree, out: *mut QpgpuZkSnapshot) -> i32;
     pub fn qpgpu_zk_tree_open_at(t: *const QpgpuZkTree, snap: *const QpgpuZkSnapshot, indices: *const u64, n: usize, siblings_out: *mut u8,
                                  positions_out: *mut u8) -> i32;
+    // no snapshot kept: the snapshots at earlier counts derived from the resident nodes, a kept one checked against the tree, paths
+    // opened at a count per path (roots_out: n x 32 bytes, may be null), and a reorg back to the first n leaves
+    pub fn qpgpu_zk_tree_snapshots_at(t: *const QpgpuZkTree, counts: *const u64, m: usize, out: *mut QpgpuZkSnapshot) -> i32;
+    pub fn qpgpu_zk_tree_snapshot_check(t: *const QpgpuZkTree, snap: *const QpgpuZkSnapshot) -> i32;
+    pub fn qpgpu_zk_tree_open_at_counts(t: *const QpgpuZkTree, counts: *const u64, indices: *const u64, n: usize, siblings_out: *mut u8,
+                                        positions_out: *mut u8, roots_out: *mut u8) -> i32;
+    pub fn qpgpu_zk_tree_truncate(t: *mut QpgpuZkTree, n: usize, snap_out: *mut QpgpuZkSnapshot, err: *mut c_char) -> i32;
     pub fn qpgpu_wrapper_circuit_build(inner_pack: *const u64, inner_words: usize, inner_cs_cap: *const u64, cap_words: usize, num_proofs: u32,
                                        num_routed_wires: u32, min_degree_bits: u32, inner_hasher: i32, flags: u32, pack_out: *mut u64, pack_cap_words: usize,
                                        pack_words: *mut usize, target_map_out: *mut u64, map_cap: usize, map_count: *mut usize, info_out: *mut u64,

@@ -82,6 +82,10 @@ def load_library():
         "qpgpu_zk_tree_append": (c.c_int, [vp, vp, c.c_size_t, c.c_uint, vp, c.c_char_p]),
         "qpgpu_zk_tree_snapshot": (c.c_int, [vp, vp]),
         "qpgpu_zk_tree_open_at": (c.c_int, [vp, vp, vp, c.c_size_t, vp, vp]),
+        "qpgpu_zk_tree_snapshots_at": (c.c_int, [vp, vp, c.c_size_t, vp]),
+        "qpgpu_zk_tree_snapshot_check": (c.c_int, [vp, vp]),
+        "qpgpu_zk_tree_open_at_counts": (c.c_int, [vp, vp, vp, c.c_size_t, vp, vp, vp]),
+        "qpgpu_zk_tree_truncate": (c.c_int, [vp, c.c_size_t, vp, c.c_char_p]),
         "qpgpu_poseidon2_hash_pad10": (c.c_int, [u64p, c.c_size_t, u64p, c.c_size_t, u64p]),
         "qpgpu_crash_trace_armed": (c.c_int, []),
         "qpgpu_circuit_num_public_inputs": (c.c_size_t, [vp]),

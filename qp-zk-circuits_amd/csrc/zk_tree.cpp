@@ -2,10 +2,12 @@
 // block's tree in HBM, its root, its levels and the Merkle paths of many leaves per call. The rules are common/src/zk_merkle.rs as
 // leaf_witness.cpp restates them on the host; the geometry and the argument checks are zk_tree.hpp's, the kernels zk_tree_kernels.hip's.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <vector>
 #include "../../include/qpgpu_leaf.h"
 #include "ctx.hpp"
 #include "zk_tree.hpp"
@@ -297,6 +299,142 @@ int qpgpu_zk_tree_open_at(const qpgpu_zk_tree *t, const qpgpu_zk_snapshot *snap,
     ZK_HIP(ctx, nullptr, hipMemcpyAsync(siblings_out, sib.p, rows * zk_tree::PATH_LEVEL_BYTES, hipMemcpyDeviceToHost, ctx->stream), what);
     ZK_HIP(ctx, nullptr, hipMemcpyAsync(positions_out, pos.p, rows, hipMemcpyDeviceToHost, ctx->stream), what);
     ZK_HIP(ctx, nullptr, hipStreamSynchronize(ctx->stream), what);
+    return QPGPU_OK;
+}
+
+// ---- the tree at earlier counts out of the tree alone, and reorgs (zk_tree.hpp: last_node; zk_snapshots_at_kernel) ----
+
+int qpgpu_zk_tree_snapshots_at(const qpgpu_zk_tree *t, const uint64_t *counts, size_t m, qpgpu_zk_snapshot *out) {
+    if (!t) return QPGPU_EINVAL;
+    qpgpu_ctx *ctx = t->ctx;
+    QP_DEV(ctx);
+    static const char *const what = "zk_tree_snapshots_at";
+    if (m == 0) return QPGPU_OK;
+    if (!counts || !out) return refuse(ctx, nullptr, QPGPU_EINVAL, what, "null argument");
+    uint64_t bad = 0;
+    if (const char *why = zk_tree::check_counts(t->plan, counts, m, &bad)) {
+        char msg[96];
+        if (std::strncmp(why, "count ", 6) == 0) std::snprintf(msg, sizeof msg, "entry %llu: %s", (unsigned long long)bad, why);
+        else std::snprintf(msg, sizeof msg, "%s", why);
+        return refuse(ctx, nullptr, QPGPU_EINVAL, what, msg);
+    }
+    Scratch cnt, snaps;
+    ZK_HIP(ctx, nullptr, cnt.alloc(m * sizeof(uint64_t)), what);
+    ZK_HIP(ctx, nullptr, snaps.alloc(m * sizeof(zk_tree::Snapshot)), what);
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(cnt.p, counts, m * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream), what);
+    ctx->prof_begin("zk_tree_snapshots_at");
+    const hipError_t e = zk_tree_derive_snapshots(t->d_nodes, t->plan, cnt.as<uint64_t>(), m, snaps.as<zk_tree::Snapshot>(), ctx->d_p2_app, ctx->stream);
+    ctx->prof_end();
+    ZK_HIP(ctx, nullptr, e, what);
+    return read_nodes(ctx, out, snaps.p, m * sizeof(zk_tree::Snapshot), what);      // the sync also ends the kernel's use of both buffers
+}
+
+int qpgpu_zk_tree_snapshot_check(const qpgpu_zk_tree *t, const qpgpu_zk_snapshot *snap) {
+    if (!t) return QPGPU_EINVAL;
+    qpgpu_ctx *ctx = t->ctx;
+    QP_DEV(ctx);
+    static const char *const what = "zk_tree_snapshot_check";
+    if (!snap) return refuse(ctx, nullptr, QPGPU_EINVAL, what, "null argument");
+    if (const char *why = zk_tree::check_open_at(t->plan, snap->count, snap->depth, nullptr, 0, nullptr)) return refuse(ctx, nullptr, QPGPU_EINVAL, what, why);
+    qpgpu_zk_snapshot own;
+    const uint64_t count = snap->count;
+    if (int rc = qpgpu_zk_tree_snapshots_at(t, &count, 1, &own)) return rc;
+    for (unsigned l = 1; l <= t->plan.depth; l++)
+        if (std::memcmp(own.last[l - 1], snap->last[l - 1], zk_tree::NODE_BYTES) != 0) {
+            char msg[96];
+            std::snprintf(msg, sizeof msg, "snapshot differs from the tree's at count %llu: the last node of level %u", (unsigned long long)count, l);
+            return refuse(ctx, nullptr, QPGPU_EINVAL, what, msg);
+        }
+    if (std::memcmp(&own, snap, sizeof own) != 0)
+        return refuse(ctx, nullptr, QPGPU_EINVAL, what, "snapshot differs from the tree's: the reserved word or an entry above the depth is not zero");
+    return QPGPU_OK;
+}
+
+int qpgpu_zk_tree_open_at_counts(const qpgpu_zk_tree *t, const uint64_t *counts, const uint64_t *indices, size_t n, uint8_t *siblings_out,
+                                 uint8_t *positions_out, uint8_t *roots_out) {
+    if (!t) return QPGPU_EINVAL;
+    qpgpu_ctx *ctx = t->ctx;
+    QP_DEV(ctx);
+    static const char *const what = "zk_tree_open_at_counts";
+    if (n == 0) return QPGPU_OK;
+    if (!counts || !indices || !siblings_out || !positions_out) return refuse(ctx, nullptr, QPGPU_EINVAL, what, "null argument");
+    uint64_t bad = 0;
+    if (const char *why = zk_tree::check_open_at_counts(t->plan, counts, indices, n, &bad)) {
+        char msg[96];
+        if (std::strncmp(why, "too many", 8) != 0) std::snprintf(msg, sizeof msg, "entry %llu: %s", (unsigned long long)bad, why);
+        else std::snprintf(msg, sizeof msg, "%s", why);
+        return refuse(ctx, nullptr, QPGPU_EINVAL, what, msg);
+    }
+    // one upload: the leaf indices, the distinct counts (sorted), and for every path the place of its count among them
+    std::vector<uint64_t> distinct;
+    std::vector<uint8_t> up;
+    size_t m = 0;
+    try {
+        distinct.assign(counts, counts + n);
+        std::sort(distinct.begin(), distinct.end());
+        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+        m = distinct.size();
+        up.resize((n + m) * sizeof(uint64_t) + n * sizeof(uint32_t));
+    } catch (const std::bad_alloc &) {
+        return refuse(ctx, nullptr, QPGPU_ENOMEM, what, "out of host memory");
+    }
+    const size_t off_counts = n * sizeof(uint64_t), off_snap_of = (n + m) * sizeof(uint64_t);
+    std::memcpy(up.data(), indices, n * sizeof(uint64_t));
+    std::memcpy(up.data() + off_counts, distinct.data(), m * sizeof(uint64_t));
+    uint32_t *snap_of = (uint32_t *)(up.data() + off_snap_of);
+    for (size_t i = 0; i < n; i++) snap_of[i] = (uint32_t)(std::lower_bound(distinct.begin(), distinct.end(), counts[i]) - distinct.begin());
+
+    const size_t rows = n * t->plan.depth;
+    Scratch in, snaps, sib, pos, roots;
+    ZK_HIP(ctx, nullptr, in.alloc(up.size()), what);
+    ZK_HIP(ctx, nullptr, snaps.alloc(m * sizeof(zk_tree::Snapshot)), what);
+    ZK_HIP(ctx, nullptr, sib.alloc(rows * zk_tree::PATH_LEVEL_BYTES), what);
+    ZK_HIP(ctx, nullptr, pos.alloc(rows), what);
+    if (roots_out) ZK_HIP(ctx, nullptr, roots.alloc(n * zk_tree::NODE_BYTES), what);
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(in.p, up.data(), up.size(), hipMemcpyHostToDevice, ctx->stream), what);
+    const uint8_t *d_in = in.as<uint8_t>();
+    ctx->prof_begin("zk_tree_open_at_counts");
+    hipError_t e = zk_tree_derive_snapshots(t->d_nodes, t->plan, (const uint64_t *)(d_in + off_counts), m, snaps.as<zk_tree::Snapshot>(), ctx->d_p2_app,
+                                            ctx->stream);
+    if (e == hipSuccess)
+        e = zk_tree_open_paths_at_many(t->d_nodes, t->plan, snaps.as<zk_tree::Snapshot>(), m, (const uint32_t *)(d_in + off_snap_of), (const uint64_t *)d_in,
+                                       n, sib.as<uint8_t>(), pos.as<uint8_t>(), roots.as<uint8_t>(), ctx->stream);
+    ctx->prof_end();
+    ZK_HIP(ctx, nullptr, e, what);
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(siblings_out, sib.p, rows * zk_tree::PATH_LEVEL_BYTES, hipMemcpyDeviceToHost, ctx->stream), what);
+    ZK_HIP(ctx, nullptr, hipMemcpyAsync(positions_out, pos.p, rows, hipMemcpyDeviceToHost, ctx->stream), what);
+    if (roots_out) ZK_HIP(ctx, nullptr, hipMemcpyAsync(roots_out, roots.p, n * zk_tree::NODE_BYTES, hipMemcpyDeviceToHost, ctx->stream), what);
+    ZK_HIP(ctx, nullptr, hipStreamSynchronize(ctx->stream), what);
+    return QPGPU_OK;
+}
+
+// The snapshot at n is derived from the nodes as they stand, then written over the last node of every level at the sizes of n: every
+// other node of those sizes is resident and unchanged since the tree had n leaves, so the tree is the one built from its first n leaves.
+// What lies beyond the new sizes stays in memory, unreachable: every read is bounded by the plan's sizes.
+int qpgpu_zk_tree_truncate(qpgpu_zk_tree *t, size_t n, qpgpu_zk_snapshot *snap_out, char *err) {
+    if (err) err[0] = 0;
+    if (!t) { if (err) std::snprintf(err, QPGPU_LEAF_ERR_CAP, "zk_tree_truncate: null tree"); return QPGPU_EINVAL; }
+    qpgpu_ctx *ctx = t->ctx;
+    QP_DEV(ctx);
+    static const char *const what = "zk_tree_truncate";
+    if (const char *why = zk_tree::check_truncate(t->plan, n)) return refuse(ctx, err, QPGPU_EINVAL, what, why);
+    zk_tree::Plan cut;
+    if (const char *why = zk_tree::make_plan_reserved(n, t->capacity, t->plan.depth, 0, cut)) return refuse(ctx, err, QPGPU_EINVAL, what, why);
+    const uint64_t count = n;
+    Scratch cnt, snap;
+    ZK_HIP(ctx, err, cnt.alloc(sizeof count), what);
+    ZK_HIP(ctx, err, snap.alloc(sizeof(zk_tree::Snapshot)), what);
+    ZK_HIP(ctx, err, hipMemcpyAsync(cnt.p, &count, sizeof count, hipMemcpyHostToDevice, ctx->stream), what);
+    ctx->prof_begin("zk_tree_truncate");
+    hipError_t e = zk_tree_derive_snapshots(t->d_nodes, t->plan, cnt.as<uint64_t>(), 1, snap.as<zk_tree::Snapshot>(), ctx->d_p2_app, ctx->stream);
+    if (e == hipSuccess) e = zk_tree_place_snapshot(t->d_nodes, cut, snap.as<zk_tree::Snapshot>(), t->d_aux() + offsetof(Aux, snap), ctx->stream);
+    ctx->prof_end();
+    ZK_HIP(ctx, err, e, what);
+    qpgpu_zk_snapshot at;
+    ZK_HIP(ctx, err, hipMemcpyAsync(&at, snap.p, sizeof at, hipMemcpyDeviceToHost, ctx->stream), what);
+    ZK_HIP(ctx, err, hipStreamSynchronize(ctx->stream), what);      // also ends the kernels' use of both buffers
+    t->plan = cut;
+    if (snap_out) *snap_out = at;
     return QPGPU_OK;
 }
 

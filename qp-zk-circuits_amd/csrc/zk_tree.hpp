@@ -1,11 +1,18 @@
 // zk_tree.hpp — the chain's 4-ary ZK Merkle tree on the device: level geometry and argument checks (host only, no HIP: also compiled
-// stand-alone under the sanitizers by tools/host_checks/zk_tree_plan_check.cpp) and the launch interface of zk_tree_kernels.hip.
+// stand-alone under the sanitizers by tools/host_checks/zk_tree_plan_check.cpp, zk_tree_append_check.cpp and zk_tree_reorg_check.cpp;
+// what the kernels share of it is marked ZK_TREE_HD) and the launch interface of zk_tree_kernels.hip.
 //
 // Storage: one array of 32-byte nodes, level 0 (the leaves) first, every level behind the one below it. Level l holds
 // ceil(count / 4^l) nodes; a child beyond a level's end is the empty hash (32 zero bytes) and is not stored.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+
+#ifdef __HIPCC__
+#define ZK_TREE_HD __host__ __device__       // the geometry that the kernels share with the host
+#else
+#define ZK_TREE_HD
+#endif
 
 namespace zk_tree {
 
@@ -24,7 +31,7 @@ struct Plan {
 };
 
 // ceil(count / 4^level); level <= 16, so 4^level fits 33 bits and the sum cannot wrap for count <= 2^24
-inline uint64_t level_size(uint64_t count, unsigned level) { return (count + ((1ull << (2 * level)) - 1)) >> (2 * level); }
+ZK_TREE_HD inline uint64_t level_size(uint64_t count, unsigned level) { return (count + ((1ull << (2 * level)) - 1)) >> (2 * level); }
 
 // the smallest depth with 4^depth >= count, at least 1 (a path always has a level); 0 when there is none up to MAX_DEPTH
 inline unsigned min_depth(uint64_t count) {
@@ -124,6 +131,54 @@ inline const char *check_open_at(const Plan &p, uint64_t snap_count, uint32_t sn
     return nullptr;
 }
 
+// ---- the tree as it stood at an earlier count, out of the tree alone (qpgpu_zk_tree_snapshots_at / _open_at_counts / _truncate) ----
+// At count n every node of level l >= 1 except the level's last is still resident and unchanged (above). The last one, index
+// level_size(n, l) - 1, is the hash of its children 4i .. 4i + 3 of level l - 1 as they stood at n: those at or beyond
+// level_size(n, l - 1) were empty, the last existing one is the last node of level l - 1 (for l - 1 >= 1 the node derived one step
+// earlier; a leaf is never rehashed), the others are resident. So the snapshot at n is a chain of `depth` node hashes over resident nodes.
+
+// the last node of level l >= 1 at count n >= 1
+struct LastNode {
+    uint64_t index;                  // its index in level l: level_size(n, l) - 1
+    uint32_t children;               // how many of its four children existed at n (1 .. 4): slots 0 .. children - 1 of level l - 1
+    int32_t computed;                // the child slot that takes the node derived at level l - 1 (children - 1), or -1 at l = 1
+};
+ZK_TREE_HD inline LastNode last_node(uint64_t n, unsigned l) {
+    LastNode r;
+    r.index = level_size(n, l) - 1;
+    r.children = (uint32_t)(level_size(n, l - 1) - 4 * r.index);
+    r.computed = l >= 2 ? (int32_t)r.children - 1 : -1;
+    return r;
+}
+
+// m counts, each 1 .. the live count. *bad: the first refused entry.
+inline const char *check_counts(const Plan &p, const uint64_t *counts, uint64_t m, uint64_t *bad) {
+    if (m > (uint64_t)SIZE_MAX / sizeof(Snapshot)) return "too many counts for one call";
+    for (uint64_t i = 0; i < m; i++) {
+        if (counts[i] == 0) { if (bad) *bad = i; return "count is 0"; }
+        if (counts[i] > p.count) { if (bad) *bad = i; return "count exceeds the tree's leaf count"; }
+    }
+    return nullptr;
+}
+
+// n paths, path i against the tree as it stood at counts[i]: check_open_at with a count per path
+inline const char *check_open_at_counts(const Plan &p, const uint64_t *counts, const uint64_t *indices, uint64_t n, uint64_t *bad) {
+    if (n > (uint64_t)SIZE_MAX / (PATH_LEVEL_BYTES * MAX_DEPTH)) return "too many paths for one call";
+    for (uint64_t i = 0; i < n; i++) {
+        if (counts[i] == 0) { if (bad) *bad = i; return "count is 0"; }
+        if (counts[i] > p.count) { if (bad) *bad = i; return "count exceeds the tree's leaf count"; }
+        if (indices[i] >= counts[i]) { if (bad) *bad = i; return "leaf index out of range"; }
+    }
+    return nullptr;
+}
+
+// back to the first n leaves
+inline const char *check_truncate(const Plan &p, uint64_t n) {
+    if (n == 0) return "n is 0";
+    if (n > p.count) return "n exceeds the tree's leaf count";
+    return nullptr;
+}
+
 }  // namespace zk_tree
 
 #ifndef ZK_TREE_PLAN_ONLY   // the stand-alone host check takes the geometry alone
@@ -150,4 +205,16 @@ hipError_t zk_tree_gather_snapshot(const uint8_t *d_nodes, const zk_tree::Plan &
 // zk_tree_open_paths on the tree as it stood at snap.count (checked against the plan on the host: zk_tree::check_open_at)
 hipError_t zk_tree_open_paths_at(const uint8_t *d_nodes, const zk_tree::Plan &plan, const zk_tree::Snapshot &snap, const uint64_t *d_indices,
                                  uint64_t n, uint8_t *d_siblings, uint8_t *d_positions, hipStream_t st);
+// d_out[j] = the snapshot of the tree as it stood at d_counts[j] leaves, j < m, derived from the resident nodes (counts checked on the
+// host: zk_tree::check_counts)
+hipError_t zk_tree_derive_snapshots(const uint8_t *d_nodes, const zk_tree::Plan &plan, const uint64_t *d_counts, uint64_t m, zk_tree::Snapshot *d_out,
+                                    const poseidon2::Params *p2, hipStream_t st);
+// zk_tree_open_paths_at with a snapshot per path: path q is opened at d_snaps[d_snap_of[q]] (m of them, from zk_tree_derive_snapshots
+// on this tree; zk_tree::check_open_at_counts on the host). d_roots (n x 32 bytes, may be null): the root each path leads to.
+hipError_t zk_tree_open_paths_at_many(const uint8_t *d_nodes, const zk_tree::Plan &plan, const zk_tree::Snapshot *d_snaps, uint64_t m,
+                                      const uint32_t *d_snap_of, const uint64_t *d_indices, uint64_t n, uint8_t *d_siblings, uint8_t *d_positions,
+                                      uint8_t *d_roots, hipStream_t st);
+// a truncate: `cut` is the plan at the new count, *d_snap the snapshot derived at that count. Its nodes go over the last node of every
+// level of `cut` and into d_snap_nodes (16 x 32 bytes).
+hipError_t zk_tree_place_snapshot(uint8_t *d_nodes, const zk_tree::Plan &cut, const zk_tree::Snapshot *d_snap, uint8_t *d_snap_nodes, hipStream_t st);
 #endif  // ZK_TREE_PLAN_ONLY

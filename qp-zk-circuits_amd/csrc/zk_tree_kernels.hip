@@ -11,6 +11,10 @@
 //   zk_append_top_kernel  zk_top_kernel over the dirty ranges of every remaining level, then the snapshot of the grown tree
 //   zk_snapshot_kernel    the snapshot alone
 //   zk_open_at_kernel     zk_open_kernel on the tree as it stood at a snapshot
+// and for the tree at earlier counts without a kept snapshot, and for a reorg (zk_tree.hpp: last_node):
+//   zk_snapshots_at_kernel    one thread per count: the snapshot at that count, `depth` node hashes over the resident nodes
+//   zk_open_at_many_kernel    zk_open_at_kernel with a snapshot per path, read from memory; the path's root too
+//   zk_place_snapshot_kernel  a derived snapshot written over the last node of every level: the tree truncated to that count
 //
 // The hash is the application hash of the Wormhole circuits: the pad `|| 1 || 0*` sponge with additive absorption over
 // poseidon2::permute_qp (qp-poseidon-core's set), the permutation behind p2_pad10_sponge_kernel<true>; the context's proof-system
@@ -72,16 +76,8 @@ __device__ __forceinline__ void load_group(const u8 *level, u64 n_in, u64 g, Key
     d = i + 3 < n_in ? load_key(level + 32 * (i + 3)) : zero;
 }
 
-// hash_node: parent g of a level. bad_leaf != nullptr (the pass over level 0 only): the lowest index of a child with a limb >= p is
-// recorded; inner nodes are permutation outputs, canonical by construction.
-__device__ __forceinline__ void hash_parent(const u8 *in, u64 n_in, u64 g, u8 *out, u32 *bad_leaf, const poseidon2::Params &p2) {
-    Key a, b, c, d;
-    load_group(in, n_in, g, a, b, c, d);
-    if (bad_leaf) {                              // wave-uniform; children are tested in index order, before the sort moves them
-        const u32 i = (u32)(4 * g);
-        const u32 bad = key_noncanonical(a) ? i : key_noncanonical(b) ? i + 1 : key_noncanonical(c) ? i + 2 : key_noncanonical(d) ? i + 3 : 0xFFFFFFFFu;
-        if (bad != 0xFFFFFFFFu) atomicMin(bad_leaf, bad);     // (a missing child is zero: canonical)
-    }
+// hash_node of four children in any order: sorted as 32-byte strings, sixteen limbs absorbed, three permutations. out: the node's limbs.
+__device__ __forceinline__ void hash_keys(Key a, Key b, Key c, Key d, u64 out[4], const poseidon2::Params &p2) {
     key_sort4(a, b, c, d);
     u64 s[12];
     s[0] = __builtin_bswap64(a.k0); s[1] = __builtin_bswap64(a.k1); s[2] = __builtin_bswap64(a.k2); s[3] = __builtin_bswap64(a.k3);
@@ -96,9 +92,24 @@ __device__ __forceinline__ void hash_parent(const u8 *in, u64 n_in, u64 g, u8 *o
     poseidon2::permute_qp(s, p2);
     s[0] = gl::add_canonical(s[0], 1);           // sixteen elements fill two rate blocks: the terminator opens a third
     poseidon2::permute_qp(s, p2);
+    out[0] = s[0]; out[1] = s[1]; out[2] = s[2]; out[3] = s[3];
+}
+
+// hash_node: parent g of a level. bad_leaf != nullptr (the pass over level 0 only): the lowest index of a child with a limb >= p is
+// recorded; inner nodes are permutation outputs, canonical by construction.
+__device__ __forceinline__ void hash_parent(const u8 *in, u64 n_in, u64 g, u8 *out, u32 *bad_leaf, const poseidon2::Params &p2) {
+    Key a, b, c, d;
+    load_group(in, n_in, g, a, b, c, d);
+    if (bad_leaf) {                              // wave-uniform; children are tested in index order, before the sort moves them
+        const u32 i = (u32)(4 * g);
+        const u32 bad = key_noncanonical(a) ? i : key_noncanonical(b) ? i + 1 : key_noncanonical(c) ? i + 2 : key_noncanonical(d) ? i + 3 : 0xFFFFFFFFu;
+        if (bad != 0xFFFFFFFFu) atomicMin(bad_leaf, bad);     // (a missing child is zero: canonical)
+    }
+    u64 h[4];
+    hash_keys(a, b, c, d, h, p2);
     ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out + 32 * g);
-    o[0] = make_ulonglong2(s[0], s[1]);
-    o[1] = make_ulonglong2(s[2], s[3]);
+    o[0] = make_ulonglong2(h[0], h[1]);
+    o[1] = make_ulonglong2(h[2], h[3]);
 }
 
 __global__ void __launch_bounds__(256) zk_node_kernel(const u8 *in, u64 n_in, u8 *out, u64 n_out, u32 *bad_leaf, const poseidon2::Params *p2) {
@@ -231,6 +242,82 @@ __global__ void __launch_bounds__(256) zk_open_at_kernel(const u8 *nodes, zk_tre
     positions[t] = (u8)pos;
 }
 
+// ---- the tree at earlier counts, out of the tree alone (zk_tree.hpp: last_node) ----
+
+// thread j: the snapshot of the tree as it stood at counts[j] leaves: the last node of level l = 1 .. depth is the hash of its children
+// of level l - 1 as they stood then: beyond the level's end the empty hash, the level's last node the one derived a step earlier (later
+// appends may have rehashed the resident copy; a leaf is never rehashed), every other child resident. A chain of `depth` dependent
+// node hashes on one thread, the latency class of the narrow levels of zk_append_top_kernel; a wave per workgroup spreads many counts
+// over the CUs. Counts are checked on the host (1 .. plan.count), so every read is below the live size of its level.
+__global__ void __launch_bounds__(64) zk_snapshots_at_kernel(const u8 *nodes, zk_tree::Plan plan, const u64 *counts, u64 m, zk_tree::Snapshot *out,
+                                                             const poseidon2::Params *p2) {
+    const u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const u64 n = counts[j];
+    zk_tree::Snapshot *o = out + j;
+    o->count = n; o->depth = plan.depth; o->reserved = 0;
+    const Key zero{0, 0, 0, 0};
+    Key cur = zero;
+#pragma unroll 1
+    for (u32 l = 1; l <= plan.depth; l++) {
+        const zk_tree::LastNode ln = zk_tree::last_node(n, l);
+        const u8 *group = nodes + 32 * (plan.off[l - 1] + 4 * ln.index);
+        const Key a = ln.computed == 0 ? cur : load_key(group);                          // (a last node has at least one child)
+        const Key b = ln.children < 2 ? zero : ln.computed == 1 ? cur : load_key(group + 32);
+        const Key c = ln.children < 3 ? zero : ln.computed == 2 ? cur : load_key(group + 64);
+        const Key d = ln.children < 4 ? zero : ln.computed == 3 ? cur : load_key(group + 96);
+        u64 h[4];
+        hash_keys(a, b, c, d, h, *p2);
+        o->last[l - 1][0] = h[0]; o->last[l - 1][1] = h[1]; o->last[l - 1][2] = h[2]; o->last[l - 1][3] = h[3];
+        cur = Key{__builtin_bswap64(h[0]), __builtin_bswap64(h[1]), __builtin_bswap64(h[2]), __builtin_bswap64(h[3])};
+    }
+    for (u32 l = plan.depth; l < zk_tree::MAX_DEPTH; l++) o->last[l][0] = o->last[l][1] = o->last[l][2] = o->last[l][3] = 0;
+}
+
+// zk_open_at_kernel with a snapshot per path, read from memory: path q is opened at snaps[snap_of[q]]. roots != nullptr: the thread of a
+// path's top level also writes the root the path leads to, the snapshot's last[depth - 1].
+__global__ void __launch_bounds__(256) zk_open_at_many_kernel(const u8 *nodes, zk_tree::Plan plan, const zk_tree::Snapshot *snaps, const u32 *snap_of,
+                                                              const u64 *indices, u64 n, u8 *siblings, u8 *positions, u8 *roots) {
+    const u64 t = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (t >= n * plan.depth) return;
+    const u64 q = t / plan.depth;
+    const u32 l = (u32)(t - q * plan.depth);
+    const zk_tree::Snapshot &snap = snaps[snap_of[q]];
+    const u64 idx = indices[q] >> (2 * l);       // checked against the path's count on the host
+    const u64 n_l = zk_tree::level_size(snap.count, l), g = idx & ~(u64)3;
+    const u8 *level = nodes + 32 * plan.off[l];
+    Key a = load_key_at(level, snap, l, n_l, g), b = load_key_at(level, snap, l, n_l, g + 1), c = load_key_at(level, snap, l, n_l, g + 2),
+        d = load_key_at(level, snap, l, n_l, g + 3);
+    const Key cur = load_key_at(level, snap, l, n_l, idx);
+    key_sort4(a, b, c, d);
+    const u32 pos = key_equal(a, cur) ? 0u : key_equal(b, cur) ? 1u : key_equal(c, cur) ? 2u : 3u;
+    u8 *o = siblings + 96 * t;
+    store_key(o, pos < 1 ? b : a);
+    store_key(o + 32, pos < 2 ? c : b);
+    store_key(o + 64, pos < 3 ? d : c);
+    positions[t] = (u8)pos;
+    if (roots && l == plan.depth - 1) {
+        const uint64_t *w = snap.last[l];
+        ulonglong2 *r = reinterpret_cast<ulonglong2 *>(roots + 32 * q);
+        r[0] = make_ulonglong2(w[0], w[1]);
+        r[1] = make_ulonglong2(w[2], w[3]);
+    }
+}
+
+// a truncate's last step, by the first 16 threads of a workgroup: the snapshot derived at the new count goes over the last node of every
+// level of `plan` (the tree at that count) and into snap_nodes, as gather_snapshot leaves them
+__global__ void __launch_bounds__(64) zk_place_snapshot_kernel(u8 *nodes, zk_tree::Plan plan, const zk_tree::Snapshot *snap, u8 *snap_nodes) {
+    if (threadIdx.x >= zk_tree::MAX_DEPTH) return;
+    const u32 l = threadIdx.x + 1;
+    const uint64_t *w = snap->last[l - 1];
+    const ulonglong2 lo = make_ulonglong2(w[0], w[1]), hi = make_ulonglong2(w[2], w[3]);      // (zero above the depth)
+    ulonglong2 *s = reinterpret_cast<ulonglong2 *>(snap_nodes + 32 * threadIdx.x);
+    s[0] = lo; s[1] = hi;
+    if (l > plan.depth) return;
+    ulonglong2 *o = reinterpret_cast<ulonglong2 *>(nodes + 32 * (plan.off[l] + plan.size[l] - 1));
+    o[0] = lo; o[1] = hi;
+}
+
 }  // namespace
 
 hipError_t zk_tree_leaf_hashes(const uint8_t *d_records, uint64_t count, uint8_t *d_out, const poseidon2::Params *p2, hipStream_t st) {
@@ -303,5 +390,31 @@ hipError_t zk_tree_open_paths_at(const uint8_t *d_nodes, const zk_tree::Plan &pl
     if ((threads + 255) / 256 > 0x7FFFFFFFull || snap.count == 0 || snap.count > plan.count || snap.depth != plan.depth) return hipErrorInvalidValue;
     hipLaunchKernelGGL(zk_open_at_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, d_nodes, plan, snap, d_indices, n, d_siblings,
                        d_positions);
+    return hipGetLastError();
+}
+
+hipError_t zk_tree_derive_snapshots(const uint8_t *d_nodes, const zk_tree::Plan &plan, const uint64_t *d_counts, uint64_t m, zk_tree::Snapshot *d_out,
+                                    const poseidon2::Params *p2, hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    if (plan.depth == 0 || plan.depth > zk_tree::MAX_DEPTH || plan.count == 0 || plan.count > zk_tree::MAX_LEAVES || (m + 63) / 64 > 0x7FFFFFFFull)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zk_snapshots_at_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, st, d_nodes, plan, d_counts, m, d_out, p2);
+    return hipGetLastError();
+}
+
+hipError_t zk_tree_open_paths_at_many(const uint8_t *d_nodes, const zk_tree::Plan &plan, const zk_tree::Snapshot *d_snaps, uint64_t m,
+                                      const uint32_t *d_snap_of, const uint64_t *d_indices, uint64_t n, uint8_t *d_siblings, uint8_t *d_positions,
+                                      uint8_t *d_roots, hipStream_t st) {
+    const u64 threads = n * plan.depth;
+    if (threads == 0) return hipSuccess;
+    if ((threads + 255) / 256 > 0x7FFFFFFFull || m == 0 || m > 0xFFFFFFFFull || plan.depth > zk_tree::MAX_DEPTH) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zk_open_at_many_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, d_nodes, plan, d_snaps, d_snap_of, d_indices,
+                       n, d_siblings, d_positions, d_roots);
+    return hipGetLastError();
+}
+
+hipError_t zk_tree_place_snapshot(uint8_t *d_nodes, const zk_tree::Plan &cut, const zk_tree::Snapshot *d_snap, uint8_t *d_snap_nodes, hipStream_t st) {
+    if (cut.depth == 0 || cut.depth > zk_tree::MAX_DEPTH || cut.count == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zk_place_snapshot_kernel, dim3(1), dim3(64), 0, st, d_nodes, cut, d_snap, d_snap_nodes);
     return hipGetLastError();
 }

@@ -53,14 +53,20 @@ class LeafInputs(ctypes.Structure):
 
     def set_zk_path(self, tree, index, at=None):
         """The Merkle path of leaf `index` of a ZkTree: zk_tree_root, zk_merkle_depth, the sorted siblings and the positions (levels past
-        the depth zeroed). at: a ZkSnapshot of the tree — the path and the root are those of the tree as it stood then."""
-        siblings, positions = tree.open([index], at=at)
+        the depth zeroed). at: a ZkSnapshot of the tree, or the leaf count it had then — the path and the root are those of the tree as
+        it stood then."""
+        root = None
+        if at is None or isinstance(at, ZkSnapshot):
+            siblings, positions = tree.open([index], at=at)
+        else:
+            siblings, positions, roots = tree.open([index], at=at, roots=True)
+            root = roots[0].tobytes()
         ctypes.memset(self.zk_merkle_siblings, 0, MAX_DEPTH * 96)
         ctypes.memset(self.zk_merkle_positions, 0, MAX_DEPTH)
         ctypes.memmove(self.zk_merkle_siblings, siblings.ctypes.data, tree.depth * 96)
         ctypes.memmove(self.zk_merkle_positions, positions.ctypes.data, tree.depth)
         self.zk_merkle_depth = tree.depth
-        return self.set32("zk_tree_root", tree.root if at is None else at.root)
+        return self.set32("zk_tree_root", root if root is not None else tree.root if at is None else at.root)
 
 
 def _lib():
@@ -191,7 +197,8 @@ class ZkTree:
     the transfers themselves (`transfers`, hashed on the device too). depth = 0 is the smallest depth that holds the leaves. Raises
     QpGpuError(QPGPU_EINVAL) for arguments the library refuses, a leaf hash with a non-canonical limb among them.
     capacity: room for that many leaves (qpgpu_zk_tree_build_reserved; depth = 0 is then the smallest depth that holds the capacity):
-    append() takes each later block's leaves, and open(indices, at=snapshot) opens paths at the root of an earlier block."""
+    append() takes each later block's leaves, and open(indices, at=snapshot) opens paths at the root of an earlier block; open(indices,
+    at=counts) does so with no snapshot kept, snapshots_at() and check() derive and check snapshots, truncate() follows a reorg."""
 
     def __init__(self, gpu, leaves=None, transfers=None, depth=0, flags=None, capacity=None):
         if (leaves is None) == (transfers is None):
@@ -256,15 +263,60 @@ class ZkTree:
         self.gpu._check(self.gpu.lib.qpgpu_zk_tree_read_level(self.h, level, first, n, out.ctypes.data))
         return out
 
-    def open(self, indices, at=None):
+    def snapshots_at(self, counts):
+        """The ZkSnapshots of the tree as it stood at each of `counts` leaves (1 .. leaf_count), derived on the device from the resident
+        nodes in one call (qpgpu_zk_tree_snapshots_at): what append() or snapshot() returned at that count."""
+        cnt = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        snaps = (ZkSnapshot * cnt.size)()
+        self.gpu._check(self.gpu.lib.qpgpu_zk_tree_snapshots_at(self.h, cnt.ctypes.data, cnt.size, ctypes.addressof(snaps)))
+        return [ZkSnapshot.from_buffer_copy(s) for s in snaps]
+
+    def check(self, snapshot):
+        """Whether `snapshot` is the one this tree gives at snapshot.count (qpgpu_zk_tree_snapshot_check): False for one kept from a fork
+        that truncate() has since abandoned. Raises QpGpuError(QPGPU_EINVAL) for a count of 0 or above leaf_count and for another depth."""
+        rc = self.gpu.lib.qpgpu_zk_tree_snapshot_check(self.h, ctypes.addressof(snapshot))
+        if rc == EINVAL and "snapshot differs" in self.gpu.last_error():
+            return False
+        self.gpu._check(rc)
+        return True
+
+    def truncate(self, n):
+        """A reorg: back to the first n leaves (qpgpu_zk_tree_truncate), the ZkSnapshot at n. Afterwards the tree is the one built from
+        those leaves, and appends continue from n. A refused truncate (QpGpuError(QPGPU_EINVAL): n = 0, n above leaf_count) leaves the
+        tree as it was."""
+        snap = ZkSnapshot(); err = ctypes.create_string_buffer(160)
+        rc = self.gpu.lib.qpgpu_zk_tree_truncate(self.h, n, ctypes.addressof(snap), err)
+        if rc != 0:
+            raise QpGpuError(rc, err.value.decode())
+        self.leaf_count = int(self.gpu.lib.qpgpu_zk_tree_leaf_count(self.h))
+        self._root = None
+        return snap
+
+    def open(self, indices, at=None, roots=False):
         """The paths of many leaves in one call: (siblings uint8 [n, depth, 3, 32] in sorted order, positions uint8 [n, depth]).
-        at: a ZkSnapshot of this tree — the paths of the tree as it stood then, leading to at.root (qpgpu_zk_tree_open_at)."""
+        at: a ZkSnapshot of this tree — the paths of the tree as it stood then, leading to at.root (qpgpu_zk_tree_open_at); or a leaf
+        count for all paths, or one per index — the paths of the tree as it stood at that count, no snapshot kept
+        (qpgpu_zk_tree_open_at_counts). roots=True: also the root each path leads to, uint8 [n, 32]."""
         idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
         sib = np.empty((idx.size, self.depth, 3, 32), dtype=np.uint8); pos = np.empty((idx.size, self.depth), dtype=np.uint8)
         if at is None:
             self.gpu._check(self.gpu.lib.qpgpu_zk_tree_open(self.h, idx.ctypes.data, idx.size, sib.ctypes.data, pos.ctypes.data))
-        else:
+            root = self.root if roots else None
+        elif isinstance(at, ZkSnapshot):
             self.gpu._check(self.gpu.lib.qpgpu_zk_tree_open_at(self.h, ctypes.addressof(at), idx.ctypes.data, idx.size, sib.ctypes.data, pos.ctypes.data))
+            root = at.root if roots else None
+        else:
+            cnt = np.ascontiguousarray(at, dtype=np.uint64).reshape(-1)
+            if np.ndim(at) == 0:
+                cnt = np.full(idx.size, cnt[0], dtype=np.uint64)
+            if cnt.size != idx.size:
+                raise ValueError("ZkTree.open: one count for all indices or one per index")
+            out = np.empty((idx.size, 32), dtype=np.uint8)
+            self.gpu._check(self.gpu.lib.qpgpu_zk_tree_open_at_counts(self.h, cnt.ctypes.data, idx.ctypes.data, idx.size, sib.ctypes.data, pos.ctypes.data,
+                                                                      out.ctypes.data if roots else None))
+            return (sib, pos, out) if roots else (sib, pos)
+        if roots:
+            return sib, pos, np.tile(np.frombuffer(root, dtype=np.uint8), (idx.size, 1))
         return sib, pos
 
     def close(self):
