@@ -29,15 +29,38 @@ __device__ uint4 g_table_p2[pmf::TABLE_BYTES / 16];     // qp-poseidon-core's Po
 
 #define MX_KERNEL __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4, 4)))
 
-// the two permutations of the build: the matrix table they need and the permutation itself
+// the two permutations of the build: the matrix table they need and the permutation itself, in two steps: body() is everything
+// up to the last linear layer, last_rows<FIRST, COUNT, CANON>() that layer for the rows the caller reads (canonical if they leave
+// the kernel); the other lanes of s mean nothing afterwards. The Poseidon2 plug keeps its whole permutation in body().
 struct PoseidonV1 {
     static __device__ __forceinline__ const uint4 *table() { return g_table; }
-    static __device__ __forceinline__ void permute(u64 (&s)[12], const poseidon2::Params *, const unsigned char *lds) { pmf::permute(s, c_poseidon_rc, lds); }
+    static __device__ __forceinline__ void body(u64 (&s)[12], const poseidon2::Params *, const unsigned char *lds) {
+        pmf::permute_head(s, c_poseidon_rc, lds);
+        pmf::permute_tail_rounds(s, c_poseidon_rc);
+    }
+    template <int FIRST, int COUNT, bool CANON>
+    static __device__ __forceinline__ void last_rows(u64 (&s)[12]) { pmf::last_layer_rows<FIRST, COUNT, CANON>(s); }
+    // Opaque to the optimiser, no instruction: a kernel with several endings calls it at the head of each, so that every ending
+    // starts from values of its own and the part the endings share (the forward transforms of the last linear layer) is not
+    // hoisted above the branch, where its results would have to live across it (counted in the leaf kernel: 164 to 188 bytes of
+    // scratch per lane with the hoist, against 44 without).
+    static __device__ __forceinline__ void own_copy(u64 (&s)[12]) {
+#pragma unroll
+        for (int i = 0; i < 12; i++) asm volatile("" : "+v"(s[i]));
+    }
 };
 struct Poseidon2QP {
     static __device__ __forceinline__ const uint4 *table() { return g_table_p2; }
-    static __device__ __forceinline__ void permute(u64 (&s)[12], const poseidon2::Params *p2, const unsigned char *lds) { pmf::permute_p2qp(s, *p2, lds); }
+    static __device__ __forceinline__ void body(u64 (&s)[12], const poseidon2::Params *p2, const unsigned char *lds) { pmf::permute_p2qp(s, *p2, lds); }
+    template <int FIRST, int COUNT, bool CANON>
+    static __device__ __forceinline__ void last_rows(u64 (&)[12]) {}
+    static __device__ __forceinline__ void own_copy(u64 (&)[12]) {}
 };
+template <class Perm, int FIRST, int COUNT, bool CANON>
+__device__ __forceinline__ void permute_rows(u64 (&s)[12], const poseidon2::Params *p2, const unsigned char *lds) {
+    Perm::body(s, p2, lds);
+    Perm::template last_rows<FIRST, COUNT, CANON>(s);
+}
 template <class Perm>
 __device__ __forceinline__ const unsigned char *table_to_lds() {
     extern __shared__ uint4 mx_lds[];
@@ -67,11 +90,19 @@ MX_KERNEL leaf_hash_kernel(MerkleLeafArgs a, const poseidon2::Params *p2) {
     u64 s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = 0;
+    // Three endings of a block's permutation, chosen per wave-uniform block position (one copy of the last linear layer each):
+    // the last block leaves the digest, rows 0..3; a block followed by a full one leaves the capacity, rows 8..11 (the sponge
+    // overwrites all eight rate lanes); the block before a ragged last one keeps every row, since the rate lanes that the last
+    // block does not fill stay in the state.
     for (u32 c = 0; c < W; c += 8) {
 #pragma unroll
         for (int i = 0; i < 8; i++)
             if (c + i < W) s[i] = elem(c + i);
-        Perm::permute(s, p2, lds);
+        Perm::body(s, p2, lds);
+        const u32 rest = W - c;                      // elements from this block on
+        if (rest <= 8) { Perm::own_copy(s); Perm::template last_rows<0, 4, true>(s); }
+        else if (rest >= 16) { Perm::own_copy(s); Perm::template last_rows<8, 4, false>(s); }
+        else { Perm::own_copy(s); Perm::template last_rows<0, 12, false>(s); }
     }
     if (live) {
         u64 *out = a.digests + j * 4;
@@ -96,7 +127,7 @@ MX_KERNEL node_kernel(const u64 *in, u64 *out, u64 n_out, u32 batch, u64 ps, u32
         u64 s[12];
         s[0] = a.x; s[1] = a.y; s[2] = b.x; s[3] = b.y; s[4] = c.x; s[5] = c.y; s[6] = d.x; s[7] = d.y;
         s[8] = s[9] = s[10] = s[11] = 0;
-        Perm::permute(s, p2, lds);
+        permute_rows<Perm, 0, 4, true>(s, p2, lds);
         if (live) {
             ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out + pr * ps + i * 4);
             o[0] = make_ulonglong2(s[0], s[1]);
@@ -128,7 +159,7 @@ MX_KERNEL pow_kernel(PowArgs a, const poseidon2::Params *p2) {
     u64 s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = (i == (int)a.pos) ? nonce : st[i];
-    Perm::permute(s, p2, lds);
+    permute_rows<Perm, 7, 1, true>(s, p2, lds);
     if (idx < a.count && (s[7] >> (64 - a.pow_bits)) == 0) atomicMin((unsigned long long *)&a.results[pr], (unsigned long long)nonce);
 }
 
@@ -140,7 +171,7 @@ MX_KERNEL selftest_kernel(u64 *states, const poseidon2::Params *p2) {
     u64 s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = states[t * 12 + i];
-    Perm::permute(s, p2, lds);
+    permute_rows<Perm, 0, 12, true>(s, p2, lds);
 #pragma unroll
     for (int i = 0; i < 12; i++) states[t * 12 + i] = s[i];
 }
@@ -189,12 +220,14 @@ static hipError_t device_selftest(HostPerm host_perm, const poseidon2::Params *h
             for (int i = 0; i < 12; i++) if (s[i] != out[(size_t)t * 12 + i]) e = hipErrorAssert;
         }
     // The hazard the test guards against depends on each kernel's own register allocation, so the kernels that SHIP run too,
-    // at the occupancy they ship at (1 024 workgroups: two per CU, four waves per SIMD): one leaf build (2^19 sponges of 5
-    // columns), one tree level over its digests (2^18 nodes) and one proof-of-work launch, each held against the host — for
+    // at the occupancy they ship at (1 024 workgroups: two per CU, four waves per SIMD): one leaf build (2^19 sponges of 17
+    // columns: three blocks, so that each of the leaf kernel's three endings runs: capacity rows before a full block, every row
+    // before the ragged last block, digest rows after it), one tree level over its digests (2^18 nodes) and one proof-of-work
+    // launch, each held against the host — for
     // the two hashing launches one lane of every wave (a mis-scheduled MFMA destination corrupts whole waves), for the proof of
     // work the minimum nonce itself.
     constexpr u64 NL = 1ull << 19, NN = NL / 2, POW_COUNT = 1ull << 18;
-    constexpr u32 WCOLS = 5, POW_BITS = 11, POW_BATCH = 2;
+    constexpr u32 WCOLS = 17, POW_BITS = 11, POW_BATCH = 2;
     u64 *d_cols = nullptr, *d_dig = nullptr, *d_pow = nullptr;
     std::vector<u64> cols((size_t)WCOLS * NL), dig(4 * (NL + NN)), powbuf(12 * POW_BATCH + 2 * POW_BATCH);
     if (e == hipSuccess) {
@@ -228,8 +261,10 @@ static hipError_t device_selftest(HostPerm host_perm, const poseidon2::Params *h
         for (u64 w = 0; w < NL / 64 && e == hipSuccess; w++) {           // one lane of every wave of the leaf build
             const u64 j = w * 64 + (w * 7) % 64;
             u64 s[12] = {0};
-            for (u32 c = 0; c < WCOLS; c++) s[c] = cols[(size_t)c * NL + j];
-            host_perm(s);
+            for (u32 c = 0; c < WCOLS; c += 8) {                         // overwrite absorption, a ragged last block
+                for (u32 i = 0; i < 8 && c + i < WCOLS; i++) s[i] = cols[(size_t)(c + i) * NL + j];
+                host_perm(s);
+            }
             for (int i = 0; i < 4; i++) if (s[i] != dig[4 * j + i]) e = hipErrorAssert;
         }
         for (u64 w = 0; w < NN / 64 && e == hipSuccess; w++) {           // one lane of every wave of the tree level

@@ -108,8 +108,12 @@ GL_HD void mds_circulant_half(const i64 (&x)[WIDTH], i64 (&o)[WIDTH]) {
     }
 }
 
-// s <- MDS * s
-GL_HD void mds_layer(u64 (&s)[WIDTH]) {
+// s[r] <- (MDS * s)[r] for the rows r in [FIRST, FIRST + COUNT) only; the other lanes of s keep their INPUT values and mean nothing
+// afterwards. Both half transforms are written out whole: what the named rows do not read is dead code to the compiler (a caller
+// that keeps rows 0..3 drops two of the three I terms, the eight other joins and reductions).
+template <int FIRST, int COUNT>
+GL_HD void mds_layer_rows(u64 (&s)[WIDTH]) {
+    static_assert(FIRST >= 0 && COUNT >= 1 && FIRST + COUNT <= WIDTH, "rows of the state");
     i64 lo[WIDTH], hi[WIDTH], ol[WIDTH], oh[WIDTH];
 #pragma unroll
     for (int i = 0; i < WIDTH; i++) { lo[i] = (i64)(u32)s[i]; hi[i] = (i64)(s[i] >> 32); }
@@ -117,13 +121,15 @@ GL_HD void mds_layer(u64 (&s)[WIDTH]) {
     mds_circulant_half(hi, oh);
     ol[0] += shl(lo[0], 3); oh[0] += shl(hi[0], 3);   // the diagonal term 8 * s[0]
 #pragma unroll
-    for (int r = 0; r < WIDTH; r++) {
+    for (int r = FIRST; r < FIRST + COUNT; r++) {
         const u64 al = (u64)ol[r], ah = (u64)oh[r];   // both in [0, 2^42)
         const u64 low = al + (ah << 32);
         const u32 top = (u32)(ah >> 32) + (low < al ? 1u : 0u);
         s[r] = gl::reduce96(low, top);
     }
 }
+// s <- MDS * s
+GL_HD void mds_layer(u64 (&s)[WIDTH]) { mds_layer_rows<0, WIDTH>(s); }
 
 // ---- the 22 partial rounds in the circulant's spectral domain ----
 // In a partial round only lane 0 goes through the S-box; lanes 1..11 see nothing but the MDS matrix, round after round. The

@@ -66,7 +66,7 @@ constexpr u64 small_g(int d) {
     return g;
 }
 constexpr u32 G0 = (u32)small_g(0), G1 = (u32)small_g(1), G2 = (u32)small_g(2);
-static_assert(small_g(0) == 25 && small_g(2) < (1ull << 32), "group coefficients fit one word");
+static_assert(small_g(0) == 25 && small_g(1) < small_g(2) && small_g(2) < (1ull << 21), "group coefficients: the bound of reduce96_terms");
 
 // ---- pieces shared by the device code and the host emulation ----
 // v -> eight signed digits d_b in [-128, 127] packed in a u64 with sum d_b 256^b = v (mod p): the integer v if v + BIAS does not
@@ -86,9 +86,10 @@ GL_HD u32 byte_perm(u32 s0, u32 s1, u32 sel) {
     return r;
 #endif
 }
-// sum_l z[l] 2^(8 l) mod p for 8 limbs in [0, 2^24): limbs l, l+3, l+6 do not overlap (three byte concatenations), then one
-// 96-bit add chain and one reduce96 (the top word stays below 2^18)
-GL_HD u64 recombine(const u32 (&z)[LIMBS]) {
+// sum_l z[l] 2^(8 l) as a 96-bit integer (lo + top 2^64) for 8 limbs in [0, 2^24): limbs l, l+3, l+6 do not overlap (three byte
+// concatenations), then one 96-bit add chain. The sum is below 2^24 (2^56 + 2^48 + ...) < 2^81 (so below 2^82): the
+// top word stays below 2^18.
+GL_HD void recombine_wide(const u32 (&z)[LIMBS], u64 &lo, u32 &top) {
     const u32 a0 = (z[3] << 24) | z[0], a1 = byte_perm(z[6], z[3], 0x05040201u), a2 = z[6] >> 16;
     const u32 b0 = z[1] << 8, b1 = (z[7] << 24) | z[4], b2 = z[7] >> 8;
     const u32 c0 = z[2] << 16, c1 = byte_perm(z[5], z[2], 0x06050402u);
@@ -97,12 +98,34 @@ GL_HD u64 recombine(const u32 (&z)[LIMBS]) {
     const u128 B = ((u128)b2 << 64) | ((u128)b1 << 32) | b0;
     const u128 Cc = ((u128)c1 << 32) | c0;
     const u128 S = A + B + Cc;
-    return gl::reduce96((u64)S, (u32)(S >> 64));
+    lo = (u64)S; top = (u32)(S >> 64);
 }
-GL_HD u64 mul_small(u64 y, u32 g) {
-    const u64 p0 = (u64)(u32)y * g;
-    const u64 p1 = (u64)(u32)(y >> 32) * g + (p0 >> 32);
-    return gl::reduce96((p1 << 32) | (u32)p0, (u32)(p1 >> 32));
+// the same mod p: one reduce96
+GL_HD u64 recombine(const u32 (&z)[LIMBS]) {
+    u64 lo; u32 top;
+    recombine_wide(z, lo, top);
+    return gl::reduce96(lo, top);
+}
+// (lo + top 2^64 + sum_{i<n} y[i] g[i]) mod p with ONE reduction: the S-box input of a round of the running group, from the
+// gemm's recombined sum and the group's earlier y with their small integer coefficients. Exact for any (loose) 64-bit y as long
+// as the integer stays below 2^96, which reduce96 needs (top word < 2^32): the recombined sum is below 2^82, each term below
+// 2^64 2^21 = 2^85 (G2 = 1 259 209 < 2^21), there are at most three terms: the total is below 2^82 + 3 2^85 < 2^87, top < 2^23.
+// (A term reduced on its own, two multiply-adds + reduce96 + gl::add, is 15 to 16 vector instructions; a term added here is two multiply-adds and
+// a carry.)
+constexpr int MAX_GROUP_TERMS = 3;
+// The terms go onto two 64-bit halves, one multiply-add each (v_mad_u64_u32 takes a 64-bit addend): al = the sum's low word + sum
+// of lo32(y) g < 2^32 + 3 2^53, ah = the sum's upper 64 bits + sum of hi32(y) g < 2^50 + 3 2^53; neither can wrap, and the join
+// is the MDS layer's (poseidon::join_halves). Counted in the gfx950 node kernel: 2 n + 3 vector instructions for n terms, where
+// adding 128-bit products with unsigned __int128 gave 6 n.
+GL_HD u64 reduce96_terms(u64 lo, u32 top, const u64 *y, const u32 *g, int n) {
+    if (n == 0) return gl::reduce96(lo, top);
+    u64 al = (u32)lo, ah = ((u64)top << 32) | (lo >> 32);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < n; i++) { al += (u64)(u32)y[i] * g[i]; ah += (y[i] >> 32) * g[i]; }
+    const u64 low = al + (ah << 32);
+    return gl::reduce96(low, (u32)(ah >> 32) + (low < al ? 1u : 0u));
 }
 // Tile rows. After the swaps a lane holds the 32 rows of its column in two register sets: X[i] = row (i&3) + 8 (i>>2), Y[i] = that
 // row + 4. Outputs 0, 1 of a tile are X[0..7], X[8..15]; outputs 2, 3 are Y[0..7], Y[8..15]; limb = i & 7.
@@ -273,14 +296,23 @@ inline bool emu_gemm(const unsigned char *tab, int tile0, int cidx, int steps, c
 inline bool emu_partial_rounds(u64 (&s)[12], const unsigned char *tab) {
     u64 D[N_ELEM] = {}, y[24], G[3];
     memcpy(G, tab + G_OFF, sizeof G);
+    const bool small = G[0] == G0 && G[1] == G1 && G[2] == G2;    // Poseidon's three small integers (the kernels have them as immediates)
     for (int e = 0; e < 12; e++) D[e] = to_digits(s[e]);
     for (int g = 0; g < N_GROUP; g++) {
         u32 Z[4][LIMBS];
         if (!emu_gemm(tab, group_base(g), g, group_steps(g), D, Z)) return false;
         for (int o = 0; o < 4 && 4 * g + o < 22; o++) {
             const int k = 4 * g + o;
-            u64 x = recombine(Z[o]);
-            for (int j = 4 * g; j < k; j++) x = gl::add(x, G[k - 1 - j] >> 32 ? gl::mul(y[j], G[k - 1 - j]) : mul_small(y[j], (u32)G[k - 1 - j]));
+            u64 x;
+            if (small) {                                      // the device's SMALL_G schedule: unreduced terms, one reduction
+                u64 lo; u32 top, gg[MAX_GROUP_TERMS];
+                recombine_wide(Z[o], lo, top);
+                for (int i = 0; i < o; i++) gg[i] = (u32)G[o - 1 - i];
+                x = reduce96_terms(lo, top, y + 4 * g, gg, o);
+            } else {
+                x = recombine(Z[o]);
+                for (int j = 4 * g; j < k; j++) x = gl::add(x, gl::mul(y[j], G[k - 1 - j]));
+            }
             y[k] = poseidon::sbox7_lane(x);
         }
         for (int o = 0; o < 4 && 4 * g + o < 22; o++) D[12 + 4 * g + o] = to_digits(y[4 * g + o]);
@@ -451,10 +483,20 @@ __device__ __forceinline__ void group_step(Run &st, F &f) {
 #pragma unroll
     for (int o = 0; o < n; o++) {
         const int k = 4 * G + o;
-        u64 x = recombine(Z[o]);
-        constexpr u32 Gc[3] = {G0, G1, G2};
+        u64 x;
+        if constexpr (SMALL_G) {
+            constexpr u32 Gc[3] = {G0, G1, G2};
+            u64 lo, yy[MAX_GROUP_TERMS] = {};
+            u32 top, gg[MAX_GROUP_TERMS] = {};
+            recombine_wide(Z[o], lo, top);
 #pragma unroll
-        for (int j = 4 * G; j < k; j++) x = gl::add(x, SMALL_G ? mul_small(st.y[j], Gc[k - 1 - j]) : gl::mul(st.y[j], st.Gd[k - 1 - j]));
+            for (int i = 0; i < o; i++) { yy[i] = st.y[4 * G + i]; gg[i] = Gc[o - 1 - i]; }
+            x = reduce96_terms(lo, top, yy, gg, o);
+        } else {
+            x = recombine(Z[o]);
+#pragma unroll
+            for (int j = 4 * G; j < k; j++) x = gl::add(x, gl::mul(st.y[j], st.Gd[k - 1 - j]));
+        }
         st.y[k] = f(k, x);
     }
 #pragma unroll
@@ -510,20 +552,37 @@ __device__ __forceinline__ void permute_head(u64 (&s)[12], const u64 *rc, const 
     SboxOfInput f;
     partial_rounds<true>(s, lds, f);
 }
-__device__ __forceinline__ void permute_tail(u64 (&s)[12], const u64 *rc) {
+// The four closing full rounds in two parts. permute_tail_rounds: three times [S-box layer, MDS layer, the next round's constants]
+// and the last round's S-box layer. The last linear layer is the caller's: a sponge reads only a few rows of it (plonky2 overwrites
+// the rate lanes with the next block, a digest is lanes 0..3, the proof of work reads lane 7), and mds_layer_rows joins and
+// reduces only the rows it is asked for. permute_tail_rows<FIRST, COUNT, CANON> ends in rows [FIRST, FIRST + COUNT), canonical if
+// they leave the kernel; the other lanes of s mean nothing afterwards. A loose row may feed the next permutation (its first
+// step is add_canonical, exact for any 64-bit left operand).
+__device__ __forceinline__ void permute_tail_rounds(u64 (&s)[12], const u64 *rc) {
     using namespace poseidon;
     int r = HALF_FULL + 1 + PARTIAL;
-    sbox7_layer(s);
-    mds_layer(s);
     for (int k = 1; k < HALF_FULL; k++, r++) {
-#pragma unroll
-        for (int i = 0; i < WIDTH; i++) s[i] = gl::add_canonical(s[i], rc[r * WIDTH + i]);
         sbox7_layer(s);
         mds_layer(s);
-    }
 #pragma unroll
-    for (int i = 0; i < WIDTH; i++) s[i] = gl::canon(s[i]);
+        for (int i = 0; i < WIDTH; i++) s[i] = gl::add_canonical(s[i], rc[r * WIDTH + i]);
+    }
+    sbox7_layer(s);
 }
+template <int FIRST, int COUNT, bool CANON>
+__device__ __forceinline__ void last_layer_rows(u64 (&s)[12]) {
+    poseidon::mds_layer_rows<FIRST, COUNT>(s);
+    if (CANON) {
+#pragma unroll
+        for (int i = FIRST; i < FIRST + COUNT; i++) s[i] = gl::canon(s[i]);
+    }
+}
+template <int FIRST, int COUNT, bool CANON>
+__device__ __forceinline__ void permute_tail_rows(u64 (&s)[12], const u64 *rc) {
+    permute_tail_rounds(s, rc);
+    last_layer_rows<FIRST, COUNT, CANON>(s);
+}
+__device__ __forceinline__ void permute_tail(u64 (&s)[12], const u64 *rc) { permute_tail_rows<0, 12, true>(s, rc); }
 __device__ __forceinline__ void permute(u64 (&s)[12], const u64 *rc, const unsigned char *lds) {
     permute_head(s, rc, lds);
     permute_tail(s, rc);
@@ -555,6 +614,9 @@ __device__ __forceinline__ void permute_p2qp(u64 (&s)[12], const poseidon2::Para
 __device__ void permute(u64 (&s)[12], const u64 *rc, const unsigned char *lds);   // host pass of a .hip unit: names only
 __device__ void permute_head(u64 (&s)[12], const u64 *rc, const unsigned char *lds);
 __device__ void permute_tail(u64 (&s)[12], const u64 *rc);
+__device__ void permute_tail_rounds(u64 (&s)[12], const u64 *rc);
+template <int FIRST, int COUNT, bool CANON> __device__ void last_layer_rows(u64 (&)[12]) {}
+template <int FIRST, int COUNT, bool CANON> __device__ void permute_tail_rows(u64 (&)[12], const u64 *) {}
 __device__ void permute_p2qp(u64 (&s)[12], const poseidon2::Params &p, const unsigned char *lds);
 template <bool SMALL_G, class F> __device__ void partial_rounds(u64 (&)[12], const unsigned char *, F &) {}   // body: device pass only
 #endif
