@@ -264,13 +264,17 @@ int qpgpu_generate_witness_partial_batch_blinded_dev(qpgpu_circuit *c, const uin
 int qpgpu_witness_public_inputs_dev(qpgpu_circuit *c, const uint64_t *d_wires, uint32_t batch, uint64_t *public_inputs_out);
 
 /* ---- stage-level entry points: the circuit-independent parts of prove() ---------------------------------------
- * For a patched `qp-plonky2::plonk::prover::prove` that keeps witness generation, partial products and the quotient
- * evaluation (which depend on the gate set) in Rust and moves everything else to the GPU — polynomial commitments
- * (s2/s3), opening evaluations (s7) and the whole FRI opening proof (s8..s11). Replaces, call for call:
+ * For a patched `qp-plonky2::plonk::prover::prove` that keeps witness generation in Rust and moves everything after it to
+ * the GPU — polynomial commitments (s2/s3), partial products (s5), the quotient (s6), opening evaluations (s7) and the whole
+ * FRI opening proof (s8..s11) — so that every polynomial stays on the device from the wire commitment to the proof bytes.
+ * Replaces, call for call:
  *   PolynomialBatch::from_values / from_coeffs  -> qpgpu_oracle_commit
  *   batch.merkle_tree.cap                       -> qpgpu_oracle_cap
+ *   all_wires_permutation_partial_products      -> qpgpu_stage_partial_products (on a qpgpu_stage_plan, below)
+ *   compute_quotient_polys                      -> qpgpu_stage_quotient
  *   batch.polynomials[i].to_extension().eval(z) -> qpgpu_oracle_eval           (OpeningSet::new)
- *   batch.get_lde_values(..)                    -> qpgpu_oracle_read / qpgpu_oracle_device_ptrs (quotient inputs)
+ *   batch.get_lde_values(..)                    -> qpgpu_oracle_read / qpgpu_oracle_device_ptrs (for a caller that evaluates
+ *                                                  gates of its own; the two stage entries read the LDEs in place)
  *   Challenger::{observe_*, get_*}              -> qpgpu_challenger_*         (host; optional, the Rust one works too)
  *   PolynomialBatch::prove_openings             -> qpgpu_fri_prove            (returns write_fri_proof bytes)
  * reached in the reference through wormhole/prover/src/lib.rs:171-175 and the aggregator call sites listed above. */
@@ -323,6 +327,54 @@ size_t qpgpu_fri_proof_size(qpgpu_oracle *const *oracles, uint32_t num_oracles, 
 int qpgpu_fri_prove(qpgpu_ctx *ctx, qpgpu_oracle *const *oracles, uint32_t num_oracles, const qpgpu_fri_batch *batches,
                     uint32_t num_batches, const qpgpu_fri_params *params, qpgpu_challenger *challenger,
                     uint8_t *out, size_t out_cap, size_t *out_len);
+
+/* ---- stages s5 and s6 of the stage flow: partial products and the quotient on the device ----------------------
+ * A qpgpu_stage_plan holds what the two gate-dependent stages need and what does not depend on a witness — what a circuit
+ * handle prepares at load: the sigma values on the subgroup (forward NTT of the constants/sigmas oracle's coefficients), the
+ * subgroup / coset / vanishing tables, the gate table and the folded hash-gate schedule. The launch sequences are the ones
+ * qpgpu_prove* runs, at a batch of one, so the stage flow's proof equals qpgpu_prove_dev's byte for byte.
+ *
+ * words: a full QPCP1 pack (qpgpu_circuit_load's input), or the same words with the constants/sigmas VALUE block left out:
+ * everything up to and including k_is and circuit_digest, then the trailers (the P2GL1 trailer is needed when gate type 14 is
+ * present; hint and PUBI1 trailers are accepted and ignored). The two forms are told apart by length; any other length is
+ * QPGPU_EINVAL. The header goes through the rules of qpgpu_circuit_load (a type-14 gate without its layout trailer is refused
+ * with the loader's message) BEFORE ctx and cs_oracle are looked at: a refusal of the words needs no device.
+ * cs_oracle: the caller's commitment of the constants/sigmas polynomials, qpgpu_oracle_commit(QPGPU_ORACLE_VALUES, no blinding)
+ * over num_selectors + num_constants + num_routed_wires columns; its column count, degree_bits and rate_bits are checked
+ * against the header (QPGPU_EINVAL names cs_oracle). The plan reads the oracle's LDE in place and does NOT own it: the oracle
+ * must outlive the plan; freeing it first is the caller's error.
+ * err (may be NULL): QPGPU_STAGE_ERR_CAP bytes for the reason; with a context it is qpgpu_last_error too. *out stays NULL on
+ * every error. A plan follows its context's threading rule: one thread at a time, on the ctx stream. */
+typedef struct qpgpu_stage_plan qpgpu_stage_plan;
+#define QPGPU_STAGE_ERR_CAP 256
+int qpgpu_stage_plan_create(qpgpu_ctx *ctx, const uint64_t *words, size_t n_words, const qpgpu_oracle *cs_oracle,
+                            qpgpu_stage_plan **out, char *err);
+/* Overwrites the workspace (everything that held witness-derived values) before releasing it. */
+void qpgpu_stage_plan_free(qpgpu_stage_plan *plan);
+/* Sizes for the caller's buffers, and whether the one-kernel quotient (qpgpu_circuit_set_quotient_fused) is what
+ * qpgpu_stage_quotient runs for this circuit. Any out-pointer may be NULL. */
+int qpgpu_stage_plan_info(const qpgpu_stage_plan *plan, unsigned *degree_bits, unsigned *num_challenges,
+                          unsigned *num_partial_products, unsigned *quotient_degree_factor, int *fused_selected);
+/* s5. wires: the num_wires x 2^degree_bits witness matrix, column-major — what the caller just committed — on the host or,
+ * with wires_on_device != 0, in HBM (left untouched). betas, gammas: num_challenges words each (host). d_out (device):
+ * num_challenges * (1 + num_partial_products) columns of 2^degree_bits values in the order the all-in-one prover commits them
+ * (Z_0 .. Z_{nch-1}, then the partial products of challenge 0, of challenge 1, ...), ready for
+ * qpgpu_oracle_commit(QPGPU_ORACLE_VALUES | QPGPU_ORACLE_DEVICE_INPUT [| QPGPU_ORACLE_BLINDING]). Synchronous on the ctx stream. */
+int qpgpu_stage_partial_products(qpgpu_stage_plan *plan, const uint64_t *wires, int wires_on_device, const uint64_t *betas,
+                                 const uint64_t *gammas, uint64_t *d_out);
+/* s6. Reads the resident LDEs of the wires oracle, the Z/partial-products oracle and the plan's constants/sigmas oracle in
+ * place (the salt columns of a blinded oracle are not polynomial columns: they lie outside the column stride and are not read).
+ * alphas: num_challenges words; public_inputs_hash: 4 words (host). d_out (device): num_challenges * quotient_degree_factor
+ * columns of 2^degree_bits COEFFICIENTS (the quotient chunks), for
+ * qpgpu_oracle_commit(QPGPU_ORACLE_COEFFS | QPGPU_ORACLE_DEVICE_INPUT [| QPGPU_ORACLE_BLINDING]). Synchronous on the ctx stream.
+ * The witness check of qpgpu_circuit_set_witness_check is part of this call (the stage flow has no later point at which an
+ * unsatisfied witness would show): QPGPU_EUNSAT, with the wording qpgpu_prove_dev uses under that check, for a trace that
+ * violates a gate constraint (the row is named) or whose permutation product does not close; d_out is then undefined. An
+ * oracle whose column count, degree_bits or rate_bits disagrees with the plan is QPGPU_EINVAL naming the argument. After any
+ * error the plan's workspace has been overwritten and the plan stays usable. */
+int qpgpu_stage_quotient(qpgpu_stage_plan *plan, const qpgpu_oracle *wires_oracle, const qpgpu_oracle *zs_pp_oracle,
+                         const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas, const uint64_t *public_inputs_hash,
+                         uint64_t *d_out);
 
 /* ---- proving pool: several proofs of one circuit in flight on one GPU ------------------------------------------
  * The native counterpart of the reference's dedicated proving worker (wormhole/aggregator/src/aggregator.rs:14-43):

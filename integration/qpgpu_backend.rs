@@ -35,10 +35,14 @@ use plonky2::plonk::config::GenericConfig;
 use plonky2::plonk::proof::ProofWithPublicInputs;
 
 // ---------------------------------------------------------------------------------------------------------------------
-// FFI: mirrors include/qpgpu.h (the subset the all-in-one path needs; the stage-level entry points are in INTEGRATION.md)
+// FFI: mirrors include/qpgpu.h (the subset the all-in-one path needs, and the two gate-dependent stages of the stage-level route;
+// its commitment / opening / FRI entry points are in INTEGRATION.md section 2a)
 // ---------------------------------------------------------------------------------------------------------------------
 #[repr(C)] pub struct QpgpuCtx { _p: [u8; 0] }
 #[repr(C)] pub struct QpgpuCircuit { _p: [u8; 0] }
+#[repr(C)] pub struct QpgpuOracle { _p: [u8; 0] }
+#[repr(C)] pub struct QpgpuStagePlan { _p: [u8; 0] }
+pub const QPGPU_STAGE_ERR_CAP: usize = 256;
 
 pub const QPGPU_OK: i32 = 0;
 pub const QPGPU_EUNSAT: i32 = -4;
@@ -66,6 +70,28 @@ extern "C" {
     pub fn qpgpu_prove_batch_dev(c: *mut QpgpuCircuit, d_wires: *const *const u64, batch: u32, public_inputs: *const *const u64,
                                  outs: *const *mut u8, out_cap: usize, out_lens: *mut usize) -> i32;
     pub fn qpgpu_pack_validate(pack: *const u64, n_words: usize, err: *mut c_char) -> i32;
+    // include/qpgpu.h — stages s5 / s6 of the stage-level route. `words`: the pack, or the pack without its
+    // constants/sigmas value block (header .. circuit_digest, then the trailers); `cs_oracle` must outlive the plan.
+    //
+    //   let plan = stage_plan_create(ctx, &pack_words[..header_end], o_cs)?;                  // once per circuit
+    //   let d_zs = qpgpu_malloc(nch * (1 + npp) * n * 8);  let d_q = qpgpu_malloc(nch * qdf * n * 8);
+    //   qpgpu_stage_partial_products(plan, wires.as_ptr(), 0, betas, gammas, d_zs)            // all_wires_permutation_partial_products
+    //   let o_zs = qpgpu_oracle_commit(ctx, d_zs, nch * (1 + npp), .., VALUES | DEVICE_INPUT [| BLINDING], seed, 2)
+    //   match qpgpu_stage_quotient(plan, o_wires, o_zs, betas, gammas, alphas, pi_hash, d_q)  // compute_quotient_polys
+    //       { QPGPU_EUNSAT => bail!("{}", last_error(ctx)), .. }                              // names the violated row
+    //   let o_q  = qpgpu_oracle_commit(ctx, d_q, nch * qdf, .., COEFFS | DEVICE_INPUT [| BLINDING], seed, 3)
+    //   .. qpgpu_free_scrubbed(ctx, d_zs, ..); qpgpu_free_scrubbed(ctx, d_q, ..);             // both held witness-derived values
+    //   qpgpu_stage_plan_free(plan) BEFORE qpgpu_oracle_free(o_cs)
+    pub fn qpgpu_stage_plan_create(ctx: *mut QpgpuCtx, words: *const u64, n_words: usize, cs_oracle: *const QpgpuOracle,
+                                   out: *mut *mut QpgpuStagePlan, err: *mut c_char) -> i32;
+    pub fn qpgpu_stage_plan_free(plan: *mut QpgpuStagePlan);
+    pub fn qpgpu_stage_plan_info(plan: *const QpgpuStagePlan, degree_bits: *mut u32, num_challenges: *mut u32, num_partial_products: *mut u32,
+                                 quotient_degree_factor: *mut u32, fused_selected: *mut i32) -> i32;
+    pub fn qpgpu_stage_partial_products(plan: *mut QpgpuStagePlan, wires: *const u64, wires_on_device: i32, betas: *const u64,
+                                        gammas: *const u64, d_out: *mut u64) -> i32;
+    pub fn qpgpu_stage_quotient(plan: *mut QpgpuStagePlan, wires_oracle: *const QpgpuOracle, zs_pp_oracle: *const QpgpuOracle,
+                                betas: *const u64, gammas: *const u64, alphas: *const u64, public_inputs_hash: *const u64,
+                                d_out: *mut u64) -> i32;
     pub fn qpgpu_circuit_constants_sigmas_cap(c: *const QpgpuCircuit, out: *mut u64, out_words: usize) -> i32;
     // include/qpgpu_verify.h — host-side verification of the bytes the GPU produced (debug self-check; production keeps
     // plonky2's own `VerifierCircuitData::verify`, which is what consumers of the proof run anyway)

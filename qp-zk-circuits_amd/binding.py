@@ -148,6 +148,12 @@ def load_library():
         "qpgpu_oracle_eval": (c.c_int, [vp, u64p, c.c_uint32, c.c_uint32, u64p]),
         "qpgpu_oracle_read": (c.c_int, [vp, c.c_uint, c.c_uint32, c.c_uint32, u64p]),
         "qpgpu_oracle_device_ptrs": (c.c_int, [vp, c.POINTER(vp), c.POINTER(vp), c.POINTER(vp)]),
+        "qpgpu_stage_plan_create": (c.c_int, [vp, u64p, c.c_size_t, vp, c.POINTER(vp), c.c_char_p]),
+        "qpgpu_stage_plan_free": (None, [vp]),
+        "qpgpu_stage_plan_info": (c.c_int, [vp, c.POINTER(c.c_uint), c.POINTER(c.c_uint), c.POINTER(c.c_uint), c.POINTER(c.c_uint),
+                                            c.POINTER(c.c_int)]),
+        "qpgpu_stage_partial_products": (c.c_int, [vp, u64p, c.c_int, u64p, u64p, u64p]),
+        "qpgpu_stage_quotient": (c.c_int, [vp, vp, vp, u64p, u64p, u64p, u64p, u64p]),
         "qpgpu_challenger_init": (None, [vp]),
         "qpgpu_challenger_observe": (None, [vp, u64p, c.c_size_t]),
         "qpgpu_challenger_get": (c.c_uint64, [vp]),
@@ -785,6 +791,85 @@ class PolyOracle:
         count = self.num_polys - first if count is None else count
         out = np.empty((count, self.n << (self.rate_bits if lde else 0)), dtype=np.uint64)
         self.gpu._check(self.gpu.lib.qpgpu_oracle_read(self.h, 1 if lde else 0, first, count, out.ctypes.data))
+        return out
+
+
+STAGE_ERR_CAP = 256
+
+
+def stage_header_words(pack_words):
+    """The pack without its constants/sigmas value block: header .. k_is, circuit_digest, then the trailers — the short form
+    of the words qpgpu_stage_plan_create takes (the values are in the caller's constants/sigmas oracle)."""
+    pw = np.ascontiguousarray(pack_words, dtype=np.uint64)
+    h = pack_header(pw)
+    end = 18 + h["num_arity_rounds"] + 8 * h["num_gates"] + h["num_routed_wires"] + 4
+    ncs = h["num_selectors"] + h["num_constants"] + h["num_routed_wires"]
+    return np.concatenate([pw[:end], pw[end + (ncs << h["degree_bits"]):]])
+
+
+class StagePlan:
+    """qpgpu_stage_plan: stages s5 (partial products) and s6 (quotient) of the stage flow on the device, for one circuit.
+    pack_words: the full pack or stage_header_words(pack); cs_oracle: the PolyOracle of the constants/sigmas values (no
+    blinding), which must stay open as long as the plan."""
+
+    def __init__(self, gpu, pack_words, cs_oracle):
+        self.gpu, self.cs_oracle = gpu, cs_oracle
+        pw = np.ascontiguousarray(pack_words, dtype=np.uint64)
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(STAGE_ERR_CAP)
+        rc = gpu.lib.qpgpu_stage_plan_create(gpu.ctx, pw.ctypes.data, pw.size, cs_oracle.h if cs_oracle is not None else None,
+                                             ctypes.byref(h), err)
+        if rc != 0:
+            raise QpGpuError(rc, err.value.decode())
+        self.h = h
+        v = [ctypes.c_uint() for _ in range(4)]
+        fused = ctypes.c_int()
+        gpu._check(gpu.lib.qpgpu_stage_plan_info(h, *[ctypes.byref(x) for x in v], ctypes.byref(fused)))
+        self.degree_bits, self.num_challenges, self.num_partial_products, self.quotient_degree_factor = [int(x.value) for x in v]
+        self.fused_selected = bool(fused.value)
+        self.n = 1 << self.degree_bits
+        self.num_zs_pp = self.num_challenges * (1 + self.num_partial_products)
+        self.num_quotient = self.num_challenges * self.quotient_degree_factor
+
+    def close(self):
+        if self.h:
+            self.gpu.lib.qpgpu_stage_plan_free(self.h)
+            self.h = None
+
+    def _challenges(self, xs):
+        a = np.ascontiguousarray(xs, dtype=np.uint64).ravel()
+        assert a.size == self.num_challenges
+        return a
+
+    def partial_products(self, wires, betas, gammas):
+        """wires: the witness matrix as a numpy array [num_wires, n] (host) or a DeviceBuffer / device pointer. Returns a
+        DeviceBuffer of num_zs_pp columns of n values: PolyOracle(gpu, (buf, plan.num_zs_pp, plan.n), ...) commits it."""
+        b, g = self._challenges(betas), self._challenges(gammas)
+        if isinstance(wires, np.ndarray):
+            w = np.ascontiguousarray(wires, dtype=np.uint64)
+            ptr, on_dev = w.ctypes.data, 0
+        else:
+            ptr, on_dev = _ptr(wires), 1
+        out = self.gpu.alloc(self.num_zs_pp * self.n * 8)
+        rc = self.gpu.lib.qpgpu_stage_partial_products(self.h, ptr, on_dev, b.ctypes.data, g.ctypes.data, out.ptr)
+        if rc != 0:
+            out.free(scrub=True)
+            self.gpu._check(rc)
+        return out
+
+    def quotient(self, wires_oracle, zs_pp_oracle, betas, gammas, alphas, public_inputs_hash):
+        """Returns a DeviceBuffer of num_quotient columns of n coefficients:
+        PolyOracle(gpu, (buf, plan.num_quotient, plan.n), coeffs=True, ...) commits it. QpGpuError -4 for a witness that does not
+        satisfy the circuit."""
+        b, g, a = self._challenges(betas), self._challenges(gammas), self._challenges(alphas)
+        pih = np.ascontiguousarray(public_inputs_hash, dtype=np.uint64).ravel()
+        assert pih.size == 4
+        out = self.gpu.alloc(self.num_quotient * self.n * 8)
+        rc = self.gpu.lib.qpgpu_stage_quotient(self.h, wires_oracle.h, zs_pp_oracle.h, b.ctypes.data, g.ctypes.data, a.ctypes.data,
+                                               pih.ctypes.data, out.ptr)
+        if rc != 0:
+            out.free(scrub=True)
+            self.gpu._check(rc)
         return out
 
 

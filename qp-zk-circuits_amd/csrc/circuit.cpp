@@ -36,7 +36,23 @@ std::vector<uint64_t> CircuitPack::serialize() const {
 }
 
 std::string CircuitPack::parse(const uint64_t *words, size_t n_words) {
+    const std::string err = walk(words, n_words, false);
+    return err.empty() ? validate() : err;
+}
+
+std::string CircuitPack::parse_stage(const uint64_t *words, size_t n_words) {
+    const std::string full = walk(words, n_words, false);
+    if (full.empty()) return validate();
+    const bool header_read = header_words != 0;
+    const std::string cut = walk(words, n_words, true);
+    if (cut.empty()) return validate();
+    if (!header_read) return cut;      // the words end (or go out of range) inside the header: both forms fail the same way
+    return "length fits neither a full pack nor a pack without its constants/sigmas values";
+}
+
+std::string CircuitPack::walk(const uint64_t *words, size_t n_words, bool without_values) {
     size_t pos = 0;
+    header_words = 0; header_only = without_values;
     // `k` words left from `pos`? written so that neither side can wrap
     auto need = [&](uint64_t k) { return k <= (uint64_t)(n_words - pos); };
     if (n_words < 18 || words[0] != QPCP_MAGIC) return "bad magic or truncated header";
@@ -70,7 +86,8 @@ std::string CircuitPack::parse(const uint64_t *words, size_t n_words) {
     if (!need(num_routed_wires + 4)) return "truncated k_is";
     k_is.assign(words + pos, words + pos + num_routed_wires); pos += num_routed_wires;
     for (int i = 0; i < 4; i++) circuit_digest[i] = words[pos++];
-    const uint64_t cs = num_cs_cols() << degree_bits;          // <= 3 * 4096 * 2^24: no overflow
+    header_words = pos;
+    const uint64_t cs = without_values ? 0 : num_cs_cols() << degree_bits;          // <= 3 * 4096 * 2^24: no overflow
     if (!need(cs)) return "truncated constants_sigmas";
     constants_sigmas.assign(words + pos, words + pos + cs); pos += cs;
     hints.clear(); pi_cells.clear();
@@ -100,7 +117,7 @@ std::string CircuitPack::parse(const uint64_t *words, size_t n_words) {
             pos += cnt;
         } else return "trailing data";
     }
-    return validate();
+    return "";
 }
 
 std::string CircuitPack::validate() const {
@@ -155,7 +172,7 @@ std::string CircuitPack::validate() const {
         }
         if (g.type == GATE_POSEIDON && (num_wires < 135 || num_routed_wires < 25 || g.num_constraints != 123)) return "bad poseidon gate";
     }
-    if (constants_sigmas.size() != (num_cs_cols() << degree_bits)) return "constants_sigmas has the wrong size";
+    if (!header_only && constants_sigmas.size() != (num_cs_cols() << degree_bits)) return "constants_sigmas has the wrong size";
     if (k_is.size() != num_routed_wires) return "k_is has the wrong size";
     const uint64_t n_cells = num_wires << degree_bits;
     if (!pi_cells.empty() && pi_cells.size() != num_public_inputs) return "public-input cell list does not match num_public_inputs";

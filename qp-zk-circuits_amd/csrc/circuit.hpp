@@ -98,6 +98,8 @@ struct CircuitPack {
     std::vector<uint64_t> pi_cells;          // optional: the wire cell (row * num_wires + column) of every public input
     P2GateLayout p2_layout;                  // wire layout of the Poseidon2 gate (default unless the pack carries "P2GL1")
     bool has_p2_layout = false;              // the trailer was present (serialize() writes it back)
+    bool header_only = false;                // parse_stage() took the form without the constants/sigmas values
+    size_t header_words = 0;                 // words up to and including circuit_digest (0: the last parse ended before them)
 
     uint64_t n() const { return 1ull << degree_bits; }
     uint64_t num_cs_cols() const { return num_selectors + num_constants + num_routed_wires; }
@@ -108,7 +110,12 @@ struct CircuitPack {
     std::vector<uint64_t> serialize() const;
     // returns empty string on success, otherwise the reason
     std::string parse(const uint64_t *words, size_t n_words);
+    // the stage plan's input (include/qpgpu.h: qpgpu_stage_plan_create): a full pack, or the same words with the constants/sigmas
+    // values left out (header .. circuit_digest, then the trailers); the two are told apart by length. Same validate() rules.
+    std::string parse_stage(const uint64_t *words, size_t n_words);
     std::string validate() const;
+private:
+    std::string walk(const uint64_t *words, size_t n_words, bool without_values);   // the words into the fields; no validate()
 };
 
 constexpr uint64_t QPCP_MAGIC = 0x0000003150435051ull;

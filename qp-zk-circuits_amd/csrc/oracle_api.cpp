@@ -4,20 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <string>
 #include "merkle.hpp"
+#include "oracle_handle.hpp"
 #include "prover_host.hpp"
 #include "prover_kernels.hpp"
 
 using gl::e2;
 using gl::u64;
-
-struct qpgpu_oracle {
-    qpgpu_ctx *ctx = nullptr;
-    PolyOracle o;
-    u64 *block = nullptr;     // one allocation: coeffs | lde | digests | salt | eval scratch | salt key
-    size_t block_words = 0;
-    e2 *d_point = nullptr, *d_eval = nullptr;
-    uint32_t *d_key = nullptr;
-};
 
 extern "C" {
 

@@ -27,18 +27,6 @@ using gl::u64;
 
 namespace {
 
-std::vector<u64> powers_table(u64 base, u64 count) {
-    std::vector<u64> t(count);
-    u64 a = 1;
-    for (u64 i = 0; i < count; i++) { t[i] = gl::canon(a); a = gl::mul(a, base); }
-    return t;
-}
-
-}  // namespace
-
-
-namespace {
-
 int alloc_batch(qpgpu_circuit *c, PolyOracle &b, uint32_t ncols, uint32_t nb, bool need_coeffs = true, uint32_t oracle_index = 0) {
     const CircuitPack &p = c->pack;
     const u64 n = p.n(), lde_n = n << p.rate_bits;
@@ -51,12 +39,6 @@ int alloc_batch(qpgpu_circuit *c, PolyOracle &b, uint32_t ncols, uint32_t nb, bo
     QP_TRY(c->alloc(&b.digests, (size_t)nb * digest_words((unsigned)(p.degree_bits + p.rate_bits), (unsigned)p.cap_height), secret));
     b.set_batch(nb, oracle_index == 0);
     b.cap.resize(b.cap_words() * b.nb);
-    return QPGPU_OK;
-}
-
-int h2d(qpgpu_ctx *ctx, void *dst, const void *src, size_t bytes) {
-    QP_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    QP_HIP(ctx, hipStreamSynchronize(ctx->stream));   // source is pageable and may go out of scope
     return QPGPU_OK;
 }
 
@@ -142,11 +124,9 @@ int qpgpu_circuit_load_batch(qpgpu_ctx *ctx, const uint64_t *pack_words, size_t 
     if (!err.empty()) { delete c; return ctx->fail(QPGPU_EINVAL, "circuit_load: " + err); }
     const CircuitPack &p = c->pack;
     c->layout = proof_layout::of(p);
-    if (p.num_chunks() > 16 || p.num_challenges > 4) { delete c; return ctx->fail(QPGPU_EINVAL, "circuit_load: too many chunks/challenges"); }
-    if (p.degree_bits + p.rate_bits > 23) { delete c; return ctx->fail(QPGPU_EINVAL, "circuit_load: LDE larger than 2^23 not supported"); }
-    if (p.degree_bits + p.rate_bits > 20 && p.rate_bits > 3) { delete c; return ctx->fail(QPGPU_EINVAL, "circuit_load: an LDE beyond 2^20 points needs rate_bits <= 3"); }
-    const u64 n = p.n(), lde_n = n << p.rate_bits, R = p.num_routed_wires, nch = p.num_challenges;
-    const unsigned d = (unsigned)p.degree_bits, L = (unsigned)(p.degree_bits + p.rate_bits);
+    { const std::string why = stage_limits(p); if (!why.empty()) { delete c; return ctx->fail(QPGPU_EINVAL, "circuit_load: " + why); } }
+    const u64 n = p.n(), nch = p.num_challenges;
+    const unsigned d = (unsigned)p.degree_bits;
     const uint32_t B = max_batch;
     int rc = QPGPU_OK;
     auto fail = [&](int code) { std::string keep = ctx->err; qpgpu_circuit_free(c); ctx->err = keep; return code; };
@@ -155,51 +135,15 @@ int qpgpu_circuit_load_batch(qpgpu_ctx *ctx, const uint64_t *pack_words, size_t 
     CK(merkle_ensure_constants(ctx));
     // constants / sigmas: values (for the sigma columns of s5) and the setup commitment, shared by all proofs
     CK(c->alloc(&c->d_cs_values, (size_t)p.num_cs_cols() * n));
-    CK(h2d(ctx, c->d_cs_values, p.constants_sigmas.data(), p.constants_sigmas.size() * 8));
+    CK(h2d_sync(ctx, c->d_cs_values, p.constants_sigmas.data(), p.constants_sigmas.size() * 8));
     CK(alloc_batch(c, c->cs, (uint32_t)p.num_cs_cols(), 1));
     CK(oracle_commit_values(ctx, c->d_cs_values, c->cs, nullptr));
-    // gates
-    std::vector<GateDev> gd(p.gates.size());
-    for (size_t i = 0; i < gd.size(); i++) {
-        const GateInfo &g = p.gates[i];
-        gd[i] = {(uint32_t)g.type, (uint32_t)g.param0, (uint32_t)g.param1, (uint32_t)g.selector_index, (uint32_t)g.group_start,
-                 (uint32_t)g.group_end, (uint32_t)g.num_constraints, (uint32_t)g.param2};
-    }
-    c->h_gates = gd;
-    for (const GateInfo &g : p.gates) c->has_p2_gate = c->has_p2_gate || g.type == GATE_POSEIDON2;
-    if (c->has_p2_gate) CK(ctx->ensure_p2_app());
-    CK(c->alloc(&c->d_gates, gd.size()));
-    CK(h2d(ctx, c->d_gates, gd.data(), gd.size() * sizeof(GateDev)));
-    CK(c->alloc(&c->d_poseidon_rc, 360));
-    CK(h2d(ctx, c->d_poseidon_rc, poseidon::host_round_constants(), 360 * 8));
+    // gate table, subgroup / coset / vanishing tables and the quotient switches: shared with the stage plan (prover_stages.cpp)
+    const StageAlloc take = [c](u64 **ptr, size_t count, bool secret) { return c->alloc(ptr, count, secret); };
+    c->tab.cs_values = c->d_cs_values; c->tab.cs_lde = c->cs.lde;
+    CK(stage_tables_build(ctx, p, take, c->tab));
     CK(c->alloc(&c->d_poseidon_fast, poseidon::FP_WORDS));
-    CK(h2d(ctx, c->d_poseidon_fast, poseidon::host_fast_partial(), poseidon::FP_WORDS * 8));
-    // subgroup, coset and vanishing tables
-    CK(c->alloc(&c->d_omega, n));
-    { auto t = powers_table(gl::root_of_unity(d), n); CK(h2d(ctx, c->d_omega, t.data(), n * 8)); }
-    const uint32_t rate = 1u << p.rate_bits;
-    std::vector<u64> zh(rate), zh_inv(rate);
-    { u64 gn = gl::pow(gl::MULT_GEN, n), wr = gl::root_of_unity((unsigned)p.rate_bits), a = 1;
-      for (uint32_t i = 0; i < rate; i++) { zh[i] = gl::canon(gl::sub(gl::mul(gn, a), 1)); zh_inv[i] = gl::inv(zh[i]); a = gl::mul(a, wr); } }
-    u64 *d_zh = nullptr;
-    CK(c->alloc(&d_zh, rate)); CK(c->alloc(&c->d_zh_inv, rate));
-    CK(h2d(ctx, d_zh, zh.data(), rate * 8)); CK(h2d(ctx, c->d_zh_inv, zh_inv.data(), rate * 8));
-    {
-        const uint32_t lo_bits = (L + 1) / 2;
-        u64 *d_lo = nullptr, *d_hi = nullptr;
-        const u64 wL = gl::root_of_unity(L);
-        auto lo = powers_table(wL, 1ull << lo_bits), hi = powers_table(gl::pow(wL, 1ull << lo_bits), 1ull << (L - lo_bits));
-        CK(c->alloc(&d_lo, lo.size())); CK(c->alloc(&d_hi, hi.size()));
-        CK(h2d(ctx, d_lo, lo.data(), lo.size() * 8)); CK(h2d(ctx, d_hi, hi.data(), hi.size() * 8));
-        CK(c->alloc(&c->d_x_coset, lde_n)); CK(c->alloc(&c->d_l0_coset, lde_n));
-        hipError_t e = pk_coset_tables(lde_n, L, d_lo, d_hi, lo_bits, d_zh, rate, gl::canon(n % gl::P), c->d_x_coset, c->d_l0_coset, ctx->stream);
-        if (e != hipSuccess) return fail(ctx->hip_fail(e, "coset_tables"));
-        const u64 ginv = gl::inv(gl::MULT_GEN);
-        c->ginv_lo_bits = lo_bits;
-        auto glo = powers_table(ginv, 1ull << lo_bits), ghi = powers_table(gl::pow(ginv, 1ull << lo_bits), 1ull << (L - lo_bits));
-        CK(c->alloc(&c->d_ginv_lo, glo.size())); CK(c->alloc(&c->d_ginv_hi, ghi.size()));
-        CK(h2d(ctx, c->d_ginv_lo, glo.data(), glo.size() * 8)); CK(h2d(ctx, c->d_ginv_hi, ghi.data(), ghi.size() * 8));
-    }
+    CK(h2d_sync(ctx, c->d_poseidon_fast, poseidon::host_fast_partial(), poseidon::FP_WORDS * 8));
     // per-proof workspace, B proofs
     unsigned qbits = 0; while ((1ull << qbits) < p.quotient_degree_factor) qbits++;
     const u64 q_n = n << qbits;
@@ -209,24 +153,9 @@ int qpgpu_circuit_load_batch(qpgpu_ctx *ctx, const uint64_t *pack_words, size_t 
     CK(alloc_batch(c, c->zs, (uint32_t)p.num_zs_pp_cols(), B, true, 2));
     CK(alloc_batch(c, c->quot, (uint32_t)p.num_quotient_cols(), B, false, 3));
     CK(c->alloc(&c->quot.coeffs, (size_t)B * nch * q_n, true));      // quotient values -> coefficients, = nq chunks of n, dense per proof
-    CK(c->alloc(&c->d_qacc, (size_t)B * nch * lde_n, true));
-    CK(c->alloc(&c->d_qcp, (size_t)B * nch * p.num_chunks() * n, true));
-    CK(c->alloc(&c->d_rowprod, (size_t)B * nch * n, true));
-    CK(c->alloc(&c->d_z, (size_t)B * nch * n, true));
     CK(c->alloc(&c->d_zs_vals, (size_t)B * p.num_zs_pp_cols() * n, true));
-    const size_t nterms = nch + nch * p.num_chunks() + p.num_gate_constraints;
-    c->small_words = (2 * nch + nch * R + nch * nterms + 4 + 3) & ~(size_t)3;
-    CK(c->alloc(&c->d_small, (size_t)B * c->small_words));
-    {
-        // The hash gates' quotient kernels run in the folded form (quotient_fold.hpp). QPGPU_QUOTIENT_FOLD=0, read here and nowhere
-        // else, keeps the round-by-round form for this circuit: the A/B measurement and the parity test.
-        const uint32_t n_hash = pk_count_hash_gates(gd.data(), (uint32_t)gd.size());
-        const char *e = getenv("QPGPU_QUOTIENT_FOLD");
-        if (n_hash > 0 && n_hash <= qfold::MAX_GATES && !(e && *e == '0')) {
-            c->fold_words = (size_t)n_hash * nch * qfold::WORDS;
-            CK(c->alloc(&c->d_fold, (size_t)B * c->fold_words));
-        }
-    }
+    c->work.stage = &c->stage;
+    CK(stage_work_alloc(p, c->tab, take, B, c->work));
     const size_t n_open = p.num_cs_cols() + p.num_wires + p.num_zs_pp_cols() + p.num_quotient_cols();
     CK(c->alloc(&c->d_points, (size_t)B * 2));
     CK(c->alloc(&c->d_open, (size_t)B * (n_open + nch), true));
@@ -239,10 +168,9 @@ int qpgpu_circuit_load_batch(qpgpu_ctx *ctx, const uint64_t *pack_words, size_t 
         u64 *base = nullptr;
         CK(c->alloc(&base, FriWork::words(c->fri, widths, n_open, B), true));
         c->fri_work.bind(base, c->fri, widths, n_open, B);
-        CK(c->alloc(&c->d_check, (size_t)B * 2));
     }
     {
-        c->stage.words = (size_t)B * (c->small_words + 8 + 4 + 8) + FriWork::stage_words(c->fri, n_open, B) + 64;
+        c->stage.words = (size_t)B * (c->tab.small_words + 8 + 4 + 8) + FriWork::stage_words(c->fri, n_open, B) + 64;
         // test hook: a staging ring too small for anything sends every table through the synchronous bounce path of Stager::put
         if (const char *e = getenv("QPGPU_STAGE_FALLBACK")) if (*e == '1') c->stage.words = 1;
         void *hp = nullptr;
@@ -250,11 +178,6 @@ int qpgpu_circuit_load_batch(qpgpu_ctx *ctx, const uint64_t *pack_words, size_t 
         if (e != hipSuccess) return fail(ctx->hip_fail(e, "hipHostMalloc(stage)"));
         c->stage.h = (u64 *)hp;
     }
-    // Stage s6 takes the permutation terms and the wire-local gates in one kernel where the gate list allows it
-    // (pk_quotient_fused_gates). QPGPU_QUOTIENT_FUSED=0 starts the circuit on the two launches instead (qpgpu_circuit_set_quotient_fused
-    // switches later); QPGPU_QUOTIENT_XCD_MAP=0 keeps the one kernel but drops its XCD-grouped workgroup order, for measurements.
-    if (const char *e = getenv("QPGPU_QUOTIENT_FUSED")) if (*e == '0') c->quotient_fused = false;
-    if (const char *e = getenv("QPGPU_QUOTIENT_XCD_MAP")) if (*e == '0') c->quotient_plain_map = true;
     // routing knob of stage s1, read here like the staging hook above: which generator form the hash-gate rows of a wide dependency
     // level get (witness_plan.cpp: generate_batch). 0: always the lane-cooperative one, 1: always a thread per row, unset: by width.
     if (const char *e = getenv("QPGPU_WITNESS_WIDE_ROWS")) if (*e == '0' || *e == '1') c->witness_wide_rows = *e - '0';
@@ -285,17 +208,14 @@ int qpgpu_circuit_set_witness_check(qpgpu_circuit *c, int on) {
 
 int qpgpu_circuit_set_quotient_fused(qpgpu_circuit *c, int on) {
     if (!c) return QPGPU_EINVAL;
-    c->quotient_fused = on != 0;
+    c->tab.quotient_fused = on != 0;
     return QPGPU_OK;
 }
 
 int qpgpu_circuit_quotient_info(const qpgpu_circuit *c, int *fused_enabled, int *fused_selected) {
     if (!c) return QPGPU_EINVAL;
-    const CircuitPack &p = c->pack;
-    const bool fits = pk_quotient_fused_gates(c->h_gates.data(), (uint32_t)c->h_gates.size(), (uint32_t)p.num_routed_wires,
-                                              (uint32_t)p.quotient_degree_factor, (uint32_t)p.num_partial_products + 1, nullptr);
-    if (fused_enabled) *fused_enabled = c->quotient_fused ? 1 : 0;
-    if (fused_selected) *fused_selected = c->quotient_fused && fits ? 1 : 0;
+    if (fused_enabled) *fused_enabled = c->tab.quotient_fused ? 1 : 0;
+    if (fused_selected) *fused_selected = c->tab.fused_selected(c->pack) ? 1 : 0;
     return QPGPU_OK;
 }
 
@@ -320,17 +240,13 @@ static int prove_batch_impl(qpgpu_circuit *c, uint32_t nb, const u64 *d_wires, c
     qpgpu_ctx *ctx = c->ctx;
     const CircuitPack &p = c->pack;
     hipStream_t st = ctx->stream;
-    const u64 n = p.n(), lde_n = n << p.rate_bits, R = p.num_routed_wires;
-    const uint32_t nch = (uint32_t)p.num_challenges, npp = (uint32_t)p.num_partial_products, nchunks = npp + 1;
-    const unsigned d = (unsigned)p.degree_bits, L = (unsigned)(p.degree_bits + p.rate_bits), cap_h = (unsigned)p.cap_height;
+    const u64 n = p.n();
+    const uint32_t nch = (uint32_t)p.num_challenges, npp = (uint32_t)p.num_partial_products;
+    const unsigned d = (unsigned)p.degree_bits, cap_h = (unsigned)p.cap_height;
     const size_t ncs = p.num_cs_cols(), NW = p.num_wires, nzp = p.num_zs_pp_cols(), nq = p.num_quotient_cols();
-    const size_t sig0 = p.num_selectors + p.num_constants, cap_words = (1ull << cap_h) * 4;
-    const size_t nterms = nch + nch * nchunks + p.num_gate_constraints;
-    // the quotient lives on the coset of size n * quotient_degree_factor: every 2^q_shift-th point of the LDE, i.e. its first q_n slots
-    unsigned qbits = 0; while ((1ull << qbits) < p.quotient_degree_factor) qbits++;
-    const unsigned Lq = d + qbits, q_shift = (unsigned)p.rate_bits - qbits;
-    const u64 q_n = 1ull << Lq;
-    const size_t SW = c->small_words;
+    const size_t cap_words = (1ull << cap_h) * 4;
+    const u64 q_n = n * p.quotient_degree_factor;      // the quotient's coset: n * quotient_degree_factor points (a power of two)
+    const size_t SW = c->tab.small_words;
 
     c->stage.pos = 0;
     u64 *ring_keys = nullptr; size_t ring_key_words = 0;
@@ -369,8 +285,7 @@ static int prove_batch_impl(qpgpu_circuit *c, uint32_t nb, const u64 *d_wires, c
     std::vector<Challenger> chs(nb, Challenger(ctx->hasher));
     std::vector<std::array<u64, 4>> betas(nb), gammas(nb), alphas(nb);
 
-    // small tables per proof: [betas nch][gammas nch][beta_k_is nch*R][alpha_pows nch*nterms][pi_hash 4]
-    u64 *d_betas = c->d_small, *d_gammas = d_betas + nch, *d_bk = d_gammas + nch, *d_apow = d_bk + (size_t)nch * R, *d_pih = d_apow + (size_t)nch * nterms;
+    // small tables per proof (prover_stages.cpp): betas, gammas, beta_k_is now; alpha powers and the public-input hash after the Z commitment
     std::vector<u64> small((size_t)nb * SW, 0);
     for (uint32_t b = 0; b < nb; b++) {
         Challenger &ch = chs[b];
@@ -379,23 +294,11 @@ static int prove_batch_impl(qpgpu_circuit *c, uint32_t nb, const u64 *d_wires, c
         ch.observe(c->wires.cap_of(b), cap_words);
         for (uint32_t k = 0; k < nch; k++) betas[b][k] = ch.get();
         for (uint32_t k = 0; k < nch; k++) gammas[b][k] = ch.get();
-        u64 *sm = small.data() + (size_t)b * SW;
-        for (uint32_t k = 0; k < nch; k++) { sm[k] = betas[b][k]; sm[nch + k] = gammas[b][k]; for (u64 j = 0; j < R; j++) sm[2 * nch + k * R + j] = gl::canon(gl::mul(betas[b][k], p.k_is[j])); }
+        stage_fill_betas(p, small.data() + (size_t)b * SW, betas[b].data(), gammas[b].data());
     }
-    // (the alpha part of the table is uploaded after the Z commitment; this upload covers betas .. beta_k_is)
-    QP_TRY(c->stage.put_rows(ctx, c->d_small, SW, small.data(), SW, 2 * nch + (size_t)nch * R, nb));
 
     // ---- s5 partial products ----
-    ctx->prof_begin("prove_partial_products");
-    PpArgs pa{};
-    pa.wires = d_wires; pa.sigmas = c->d_cs_values + sig0 * n; pa.omega_pows = c->d_omega; pa.beta_k_is = d_bk;
-    pa.betas = d_betas; pa.gammas = d_gammas; pa.qcp = c->d_qcp; pa.rowprod = c->d_rowprod; pa.n = n;
-    pa.num_routed = (uint32_t)R; pa.chunk = (uint32_t)p.quotient_degree_factor; pa.nchunks = nchunks; pa.nch = nch;
-    pa.batch = nb; pa.ps_wires = NW * n; pa.ps_small = SW; pa.ps_qcp = (u64)nch * nchunks * n; pa.ps_rowprod = (u64)nch * n;
-    QP_HIP(ctx, pk_pp_rows(pa, st));
-    QP_HIP(ctx, pk_pp_scan(c->d_rowprod, c->d_z, n, nch * nb, st));
-    QP_HIP(ctx, pk_pp_finish(pa, c->d_z, c->d_zs_vals, (u64)nch * n, (u64)nzp * n, st));
-    ctx->prof_end();
+    QP_TRY(stage_partial_products(ctx, p, c->tab, c->work, nb, small.data(), d_wires, NW * n, c->d_zs_vals));
     ctx->prof_begin("prove_commit_zs");
     QP_TRY(oracle_commit_values(ctx, c->d_zs_vals, c->zs, c->d_salt_keys));
     ctx->prof_end();
@@ -405,58 +308,12 @@ static int prove_batch_impl(qpgpu_circuit *c, uint32_t nb, const u64 *d_wires, c
         Challenger &ch = chs[b];
         ch.observe(c->zs.cap_of(b), cap_words);
         for (uint32_t k = 0; k < nch; k++) alphas[b][k] = ch.get();
-        u64 *ap = small.data() + (size_t)b * SW + 2 * nch + (size_t)nch * R;
-        for (uint32_t k = 0; k < nch; k++) { u64 a = 1; for (size_t t = 0; t < nterms; t++) { ap[k * nterms + t] = gl::canon(a); a = gl::mul(a, alphas[b][k]); } }
-        std::memcpy(ap + (size_t)nch * nterms, pih[b].data(), 32);
+        stage_fill_alphas(p, small.data() + (size_t)b * SW, alphas[b].data(), pih[b].data());
     }
-    QP_TRY(c->stage.put_rows(ctx, d_apow, SW, small.data() + 2 * nch + (size_t)nch * R, SW, (size_t)nch * nterms + 4, nb));
-    // the folded hash gates' weights for this batch's alphas: one small launch, read by the gate kernels of the witness check and of s6
-    QuotientArgs qa{};
-    qa.alpha_pows = d_apow; qa.poseidon_rc = c->d_poseidon_rc; qa.p2_gate = ctx->d_p2_app; qa.p2_layout = p.p2_layout;
-    qa.nch = nch; qa.nchunks = nchunks; qa.nterms = (uint32_t)nterms; qa.num_gates = (uint32_t)p.gates.size(); qa.batch = nb; qa.ps_small = SW;
-    qa.fold = c->d_fold; qa.ps_fold = c->fold_words;
-    QP_HIP(ctx, pk_quotient_fold_sweep(qa, c->h_gates.data(), st));
-    if (c->check_witness) {
-        // the analogue of plonky2's debug assertions: filtered gate constraints must vanish on every trace row and the
-        // permutation product must close; alpha-weighted sums are zero iff every constraint is (alpha is a transcript challenge)
-        QuotientArgs ta{};
-        ta.wires = d_wires; ta.cs = c->d_cs_values; ta.alpha_pows = d_apow; ta.pi_hash = d_pih; ta.gates = c->d_gates;
-        ta.acc = c->d_qacc; ta.out = c->d_qacc; ta.poseidon_rc = c->d_poseidon_rc;
-        ta.p2_gate = ctx->d_p2_app; ta.p2_layout = p.p2_layout;
-        ta.zh_inv = c->d_zh_inv; ta.lde_n = n; ta.q_n = n; ta.q_shift = 0; ta.log_lde = d; ta.rate = 1; ta.nch = nch; ta.num_routed = (uint32_t)R;
-        ta.chunk = (uint32_t)p.quotient_degree_factor; ta.nchunks = nchunks; ta.sig0 = (uint32_t)sig0;
-        ta.num_selectors = (uint32_t)p.num_selectors; ta.num_gates = (uint32_t)p.gates.size(); ta.nterms = (uint32_t)nterms;
-        ta.batch = nb; ta.ps_wires = NW * n; ta.ps_zs = 0; ta.ps_small = SW; ta.ps_acc = (u64)nch * n; ta.ps_out = (u64)nch * n;
-        ta.fold = c->d_fold; ta.ps_fold = c->fold_words;
-        QP_HIP(ctx, hipMemsetAsync(c->d_qacc, 0, (size_t)nb * nch * n * 8, st));
-        std::vector<u64> init(2 * (size_t)nb);
-        for (uint32_t b = 0; b < nb; b++) { init[2 * b] = ~0ull; init[2 * b + 1] = 0; }
-        QP_TRY(c->stage.put(ctx, c->d_check, init.data(), init.size() * 8));
-        QP_HIP(ctx, pk_gate_sums(ta, c->h_gates.data(), st));
-        QP_HIP(ctx, pk_witness_check(c->d_qacc, n, nch, c->d_z, c->d_rowprod, c->d_check, nb, st));
-        std::vector<u64> res(2 * (size_t)nb);
-        QP_TRY(ctx->read_back(res.data(), c->d_check, res.size() * 8));
-        for (uint32_t b = 0; b < nb; b++) {
-            const std::string who = nb > 1 ? " (proof " + std::to_string(b) + " of the batch)" : "";
-            if (res[2 * b] != ~0ull) return ctx->fail(QPGPU_EUNSAT, "witness does not satisfy the circuit: gate constraints fail at row " + std::to_string(res[2 * b]) + who);
-            if (res[2 * b + 1]) return ctx->fail(QPGPU_EUNSAT, "witness does not satisfy the circuit: a copy constraint is violated (permutation product != 1)" + who);
-        }
-    }
-    ctx->prof_begin("prove_quotient");
-    qa.wires = c->wires.lde; qa.cs = c->cs.lde; qa.zs_pp = c->zs.lde; qa.x_coset = c->d_x_coset; qa.l0_coset = c->d_l0_coset;
-    qa.zh_inv = c->d_zh_inv; qa.alpha_pows = d_apow; qa.beta_k_is = d_bk; qa.betas = d_betas; qa.gammas = d_gammas; qa.pi_hash = d_pih;
-    qa.gates = c->d_gates; qa.acc = c->d_qacc; qa.poseidon_rc = c->d_poseidon_rc; qa.out = c->quot.coeffs;
-    qa.p2_gate = ctx->d_p2_app; qa.p2_layout = p.p2_layout; qa.lde_n = lde_n; qa.q_n = q_n; qa.q_shift = q_shift; qa.log_lde = L; qa.rate = 1u << p.rate_bits; qa.nch = nch;
-    qa.num_routed = (uint32_t)R; qa.chunk = (uint32_t)p.quotient_degree_factor; qa.nchunks = nchunks; qa.sig0 = (uint32_t)sig0;
-    qa.num_selectors = (uint32_t)p.num_selectors; qa.num_gates = (uint32_t)p.gates.size(); qa.nterms = (uint32_t)nterms;
-    qa.batch = nb; qa.ps_wires = c->wires.ps_lde; qa.ps_zs = c->zs.ps_lde; qa.ps_small = SW; qa.ps_acc = (u64)nch * lde_n; qa.ps_out = (u64)nch * q_n;
-    qa.fused = c->quotient_fused ? 1 : 0; qa.fused_plain_map = c->quotient_plain_map ? 1 : 0;
-    QP_HIP(ctx, pk_quotient(qa, c->h_gates.data(), st));
-    // coset_ifft(g) on the quotient domain: ifft then scale coefficient i by g^-i; the qdf*n coefficients of a challenge
-    // are its qdf chunks of n, contiguous
-    QP_TRY(ntt_run(ctx, c->quot.coeffs, c->quot.coeffs, Lq, Lq, (size_t)nch * nb, true, false, 0));
-    QP_HIP(ctx, pk_scale_powers(c->quot.coeffs, q_n, (u64)nch * nb, c->d_ginv_lo, c->d_ginv_hi, c->ginv_lo_bits, st));
-    ctx->prof_end();
+    QuotientViews qv;
+    qv.wires_lde = c->wires.lde; qv.ps_wires_lde = c->wires.ps_lde; qv.zs_lde = c->zs.lde; qv.ps_zs_lde = c->zs.ps_lde; qv.out = c->quot.coeffs;
+    if (c->check_witness) { qv.check_wires = d_wires; qv.ps_check_wires = NW * n; }
+    QP_TRY(stage_quotient(ctx, p, c->tab, c->work, nb, small.data(), qv));
     ctx->prof_begin("prove_commit_quotient");
     QP_TRY(oracle_commit_coeffs(ctx, c->quot, c->d_salt_keys));
     ctx->prof_end();
@@ -564,7 +421,7 @@ int qpgpu_prove(qpgpu_circuit *c, const uint64_t *wires, const uint64_t *public_
     QP_DEV(c->ctx);
     if (!wires || (!public_inputs && c->pack.num_public_inputs) || !out) return c->ctx->fail(QPGPU_EINVAL, "prove: null argument");
     const size_t bytes = (size_t)c->pack.num_wires * c->pack.n() * 8;
-    QP_TRY(h2d(c->ctx, c->d_wires_vals, wires, bytes));
+    QP_TRY(h2d_sync(c->ctx, c->d_wires_vals, wires, bytes));
     int rc = prove_batch_impl(c, 1, c->d_wires_vals, &public_inputs, &out, out_cap, out_len);
     // the witness carries the spend secret (reference wormhole/circuit/src/sensitive.rs:36-44): scrub every device region
     // derived from it (witness, Z / quotient values, coefficients, LDEs, salts, FRI workspace), on success and on failure

@@ -682,9 +682,9 @@ int generate_batch(qpgpu_circuit *c, uint64_t *d_wires, uint32_t batch, const ui
     if (nc) QP_HIP(ctx, pk_copy(pp->d_check_val, ckv, ck_bytes, ctx->stream));
     if (pair_checks || val_checks || nz_checks) QP_HIP(ctx, hipMemsetAsync(plan.d_err, 0xFF, (size_t)batch * 16, ctx->stream));
     WitnessArgs a{};
-    a.wires = d_wires; a.src_of = plan.d_src_of; a.insts = plan.d_insts; a.gates = c->d_gates; a.cs = c->d_cs_values;
-    a.poseidon_rc = c->d_poseidon_rc; a.poseidon_fast = c->d_poseidon_fast; a.pi_hash = plan.d_pi_hash;
-    a.p2_gate = c->has_p2_gate ? ctx->d_p2_app : nullptr; a.p2_layout = c->pack.p2_layout;
+    a.wires = d_wires; a.src_of = plan.d_src_of; a.insts = plan.d_insts; a.gates = c->tab.d_gates; a.cs = c->d_cs_values;
+    a.poseidon_rc = c->tab.d_poseidon_rc; a.poseidon_fast = c->d_poseidon_fast; a.pi_hash = plan.d_pi_hash;
+    a.p2_gate = c->tab.has_p2_gate ? ctx->d_p2_app : nullptr; a.p2_layout = c->pack.p2_layout;
     a.hints = plan.d_hints; a.num_wires = (uint32_t)c->pack.num_wires;
     a.n = c->pack.n(); a.batch_stride = stride;
     a.num_routed = (uint32_t)c->pack.num_routed_wires; a.num_selectors = (uint32_t)c->pack.num_selectors;
