@@ -4,6 +4,8 @@
  * (qpgpu_oracle_commit), partial products and the quotient (qpgpu_stage_partial_products / qpgpu_stage_quotient on a
  * qpgpu_stage_plan made from the pack's header), openings (qpgpu_oracle_eval) and the FRI proof (qpgpu_fri_prove); the Z /
  * partial-product columns and the quotient chunks never leave the device. The assembled bytes are compared with qpgpu_prove's.
+ * With a second argument "steps" the FRI proof is built one step at a time instead (qpgpu_fri_begin .. qpgpu_fri_open and
+ * qpgpu_fri_grind, the transcript kept here): the route for a prover whose prove_openings differs from qpgpu_fri_prove's.
  *
  *   gcc -O2 -I include examples/stage_prove_example.c -L qp-zk-circuits_amd -lqpgpu -Wl,-rpath,$PWD/qp-zk-circuits_amd -o /tmp/stage_prove_example
  */
@@ -26,6 +28,7 @@ static size_t put(uint8_t *out, size_t at, const uint64_t *v, size_t n) { memcpy
 
 int main(int argc, char **argv) {
     unsigned degree_bits = argc > 1 ? (unsigned)atoi(argv[1]) : 10;
+    const int stepwise = argc > 2 && !strcmp(argv[2], "steps");
     const unsigned num_wires = 135, num_routed = 80, num_pis = 21, flags = 3; /* Poseidon + BaseSum rows */
     qpgpu_ctx *ctx = NULL;
     if (qpgpu_ctx_create(0, &ctx)) { fprintf(stderr, "no gfx950 device: the library has no CPU fallback\n"); return 2; }
@@ -121,7 +124,46 @@ int main(int argc, char **argv) {
     for (uint32_t i = 0; i < 4; i++) { fb[0].ranges[i].oracle = i; fb[0].ranges[i].first = 0; fb[0].ranges[i].count = counts[i]; }
     fb[1].point[0] = g_zeta[0]; fb[1].point[1] = g_zeta[1]; fb[1].num_ranges = 1;
     fb[1].ranges[0].oracle = 2; fb[1].ranges[0].first = 0; fb[1].ranges[0].count = nch;
-    CHECK(qpgpu_fri_prove(ctx, os, 4, fb, 2, &fp, &ch, mine + at, cap - at, &fri_len));
+    if (!stepwise) {
+        CHECK(qpgpu_fri_prove(ctx, os, 4, fb, 2, &fp, &ch, mine + at, cap - at, &fri_len));
+    } else {
+        /* prove_openings with the transcript on this side: caps, query rounds, final polynomial, nonce (write_fri_proof order) */
+        qpgpu_fri_session *fs = NULL;
+        uint64_t alpha[2], beta[2], nonce = 0, response, idx[64];
+        size_t n_final = 0, q_len = 0;
+        uint8_t *o = mine + at;
+        if (fp.num_query_rounds > 64) { fprintf(stderr, "num_query_rounds beyond this example's buffers\n"); return 3; }
+        CHECK(qpgpu_ctx_challenger_get(ctx, &ch, &alpha[0]));
+        CHECK(qpgpu_ctx_challenger_get(ctx, &ch, &alpha[1]));
+        CHECK(qpgpu_fri_begin(ctx, os, 4, fb, 2, &fp, alpha, &fs));
+        for (unsigned r = 0; r < narity; r++) {
+            CHECK(qpgpu_fri_round_commit(fs, (uint64_t *)o, cap_words));
+            CHECK(qpgpu_ctx_challenger_observe(ctx, &ch, (const uint64_t *)o, cap_words));
+            o += cap_words * 8;
+            CHECK(qpgpu_ctx_challenger_get(ctx, &ch, &beta[0]));
+            CHECK(qpgpu_ctx_challenger_get(ctx, &ch, &beta[1]));
+            CHECK(qpgpu_fri_round_fold(fs, beta));
+        }
+        unsigned folded = 0;
+        for (unsigned r = 0; r < narity; r++) folded += fp.reduction_arity_bits[r];
+        const size_t final_words = (size_t)2 << (degree_bits - folded), q_bytes = fp.num_query_rounds * qpgpu_fri_query_size(fs);
+        uint64_t *final_poly = malloc(final_words * 8);
+        CHECK(qpgpu_fri_final_poly(fs, final_poly, final_words, &n_final));
+        CHECK(qpgpu_ctx_challenger_observe(ctx, &ch, final_poly, 2 * n_final));
+        CHECK(qpgpu_fri_grind(ctx, &ch, fp.proof_of_work_bits, &nonce));
+        CHECK(qpgpu_ctx_challenger_observe(ctx, &ch, &nonce, 1));
+        CHECK(qpgpu_ctx_challenger_get(ctx, &ch, &response));
+        for (unsigned q = 0; q < fp.num_query_rounds; q++) {
+            CHECK(qpgpu_ctx_challenger_get(ctx, &ch, &idx[q]));
+            idx[q] %= (uint64_t)n << rate_bits;
+        }
+        CHECK(qpgpu_fri_open(fs, idx, fp.num_query_rounds, o, q_bytes, &q_len));
+        memcpy(o + q_len, final_poly, final_words * 8);                  /* query rounds hold one-byte path lengths: no alignment here */
+        memcpy(o + q_len + final_words * 8, &nonce, 8);
+        free(final_poly);
+        fri_len = (size_t)(o - (mine + at)) + q_len + final_words * 8 + 8;
+        qpgpu_fri_session_free(fs);
+    }
     at += fri_len;
     for (unsigned i = 0; i < num_pis; i++) { const uint64_t v = pis[i] % P; at = put(mine, at, &v, 1); }
     if (at != want_len || memcmp(mine, want, want_len)) { fprintf(stderr, "the staged proof differs from qpgpu_prove's\n"); return 4; }
@@ -136,7 +178,8 @@ int main(int argc, char **argv) {
 
     uint64_t h = 1469598103934665603ull;
     for (size_t i = 0; i < at; i++) h = (h ^ mine[i]) * 1099511628211ull;
-    printf("ok degree_bits=%u proof_bytes=%zu fnv1a=%016llx (staged flow == qpgpu_prove)\n", degree_bits, at, (unsigned long long)h);
+    printf("ok degree_bits=%u proof_bytes=%zu fnv1a=%016llx (staged flow%s == qpgpu_prove)\n", degree_bits, at, (unsigned long long)h,
+           stepwise ? ", FRI step by step," : "");
     qpgpu_oracle_free(o_bad); qpgpu_oracle_free(o_q); qpgpu_oracle_free(o_zs); qpgpu_oracle_free(o_w);
     qpgpu_stage_plan_free(plan);                                       /* before the oracle it reads */
     qpgpu_oracle_free(o_cs);

@@ -298,6 +298,12 @@ int qpgpu_oracle_eval(qpgpu_oracle *o, const uint64_t point[2], uint32_t first, 
 int qpgpu_oracle_read(qpgpu_oracle *o, unsigned what, uint32_t first, uint32_t count, uint64_t *out);
 /* device pointers of the resident data, same layouts as qpgpu_oracle_read (digests: leaf layer first, cap last) */
 int qpgpu_oracle_device_ptrs(const qpgpu_oracle *o, const uint64_t **d_coeffs, const uint64_t **d_lde, const uint64_t **d_digests);
+/* MerkleTree::prove + the leaf: rows_out n x leaf_width words (the num_polys columns at that slot, then the 4 salt words of a
+ * blinded oracle: the order the proof carries), paths_out n x (degree_bits + rate_bits - cap_height) x 4 words, siblings from the
+ * leaf layer upwards. indices are leaf indices (slot s = value at g*w^bitrev(s), as QPGPU_ORACLE_READ_LDE). Either out may be NULL.
+ * An index >= 2^(degree_bits + rate_bits) is QPGPU_EINVAL naming the entry; outputs untouched. n = 0 returns 0. */
+int qpgpu_oracle_open(qpgpu_oracle *o, const uint64_t *indices, size_t n, uint64_t *rows_out, uint64_t *paths_out);
+size_t qpgpu_oracle_leaf_width(const qpgpu_oracle *o);   /* num_polys, + 4 for a blinded oracle */
 
 /* plonky2::iop::challenger::Challenger as plain data: buffers are Vec<F> contents, lengths their len() */
 typedef struct {
@@ -327,6 +333,42 @@ size_t qpgpu_fri_proof_size(qpgpu_oracle *const *oracles, uint32_t num_oracles, 
 int qpgpu_fri_prove(qpgpu_ctx *ctx, qpgpu_oracle *const *oracles, uint32_t num_oracles, const qpgpu_fri_batch *batches,
                     uint32_t num_batches, const qpgpu_fri_params *params, qpgpu_challenger *challenger,
                     uint8_t *out, size_t out_cap, size_t *out_len);
+
+/* The same proof one step at a time, for a caller who keeps the transcript: the order of observations, the proof-of-work rule
+ * and the way query indices are drawn stay in the caller's code, the polynomials and trees stay on the device. qpgpu_fri_prove
+ * is, over these entries and a challenger: alpha = two draws; per round observe(cap), beta = two draws; observe(final
+ * polynomial); grind; observe(nonce); one draw; num_query_rounds draws taken mod 2^(degree_bits + rate_bits); its bytes are the
+ * caps, the query rounds, the final polynomial and the nonce. Use qpgpu_fri_prove unless the prover being replaced differs from
+ * that. One proof per session; a session follows its context's threading rule and works on the ctx stream;
+ * every entry that returns data has synchronised the stream when it returns. Errors are a code with the reason in
+ * qpgpu_last_error(ctx). A call out of order is QPGPU_EINVAL saying what was expected, and the session stays usable: a fold with
+ * no committed round waiting, a commit while a fold is pending or after the last round, the final polynomial or an opening before
+ * the last fold. */
+typedef struct qpgpu_fri_session qpgpu_fri_session;
+/* s8: validates exactly as qpgpu_fri_prove (same messages); builds the batched opening polynomial for `alpha` (the caller's
+ * FRI alpha, 2 words) and the first layer's values. Reads rate_bits, cap_height and the reduction schedule of params;
+ * proof_of_work_bits and num_query_rounds are not read. The oracles must outlive the session. *out stays NULL on error. */
+int qpgpu_fri_begin(qpgpu_ctx *ctx, qpgpu_oracle *const *oracles, uint32_t num_oracles, const qpgpu_fri_batch *batches,
+                    uint32_t num_batches, const qpgpu_fri_params *params, const uint64_t alpha[2], qpgpu_fri_session **out);
+/* s9, round r = 0, 1, ...: commit the current layer in leaves of 2^arity_bits[r] extension values -> its cap (4 << cap_height
+ * words; any other cap_words is QPGPU_EINVAL naming it, nothing written) */
+int qpgpu_fri_round_commit(qpgpu_fri_session *s, uint64_t *cap_out, size_t cap_words);
+/* ... then fold it with the caller's beta (2 words). The fold and the next layer's values are queued on the ctx stream. */
+int qpgpu_fri_round_fold(qpgpu_fri_session *s, const uint64_t beta[2]);
+/* after the last fold (at once for a schedule of zero rounds): 2^(degree_bits - sum arity_bits) coefficients, 2 words each;
+ * out_words must be exactly that many words (QPGPU_EINVAL naming it otherwise, nothing written). num_coeffs may be NULL. */
+int qpgpu_fri_final_poly(qpgpu_fri_session *s, uint64_t *out, size_t out_words, size_t *num_coeffs);
+/* s11, after the last fold, any number of times: for each index the FriQueryRound in write_fri_proof order (per oracle: row
+ * [+ salt], one-byte path length, path; per round: the 2^arity_bits evaluations of the coset, one-byte path length, path), i.e.
+ * the bytes qpgpu_fri_prove writes for a query round with that index. out_len = n * qpgpu_fri_query_size(s); a smaller out_cap
+ * is QPGPU_EINVAL naming it, an index >= 2^(degree_bits + rate_bits) is QPGPU_EINVAL naming the entry; nothing is written. */
+size_t qpgpu_fri_query_size(const qpgpu_fri_session *s);
+int qpgpu_fri_open(qpgpu_fri_session *s, const uint64_t *indices, size_t n, uint8_t *out, size_t out_cap, size_t *out_len);
+void qpgpu_fri_session_free(qpgpu_fri_session *s);   /* overwrites the workspace (witness-derived) before releasing it */
+/* s10: the minimum nonce w for which a COPY of *c, after observe(w), answers get() with proof_of_work_bits leading zero bits,
+ * the rule qpgpu_fri_prove applies. *c is not modified. 0 bits: *nonce_out = 0, no launch. Above 40 bits, or a state
+ * plonky2 cannot be in: QPGPU_EINVAL. */
+int qpgpu_fri_grind(qpgpu_ctx *ctx, const qpgpu_challenger *c, unsigned proof_of_work_bits, uint64_t *nonce_out);
 
 /* ---- stages s5 and s6 of the stage flow: partial products and the quotient on the device ----------------------
  * A qpgpu_stage_plan holds what the two gate-dependent stages need and what does not depend on a witness — what a circuit

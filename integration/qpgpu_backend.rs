@@ -42,6 +42,12 @@ use plonky2::plonk::proof::ProofWithPublicInputs;
 #[repr(C)] pub struct QpgpuCircuit { _p: [u8; 0] }
 #[repr(C)] pub struct QpgpuOracle { _p: [u8; 0] }
 #[repr(C)] pub struct QpgpuStagePlan { _p: [u8; 0] }
+#[repr(C)] pub struct QpgpuFriSession { _p: [u8; 0] }
+#[repr(C)] pub struct QpgpuChallenger { pub sponge_state: [u64; 12], pub input_buffer: [u64; 8], pub output_buffer: [u64; 8], pub input_len: u32, pub output_len: u32 }
+#[repr(C)] pub struct QpgpuFriRange { pub oracle: u32, pub first: u32, pub count: u32 }
+#[repr(C)] pub struct QpgpuFriBatch { pub point: [u64; 2], pub num_ranges: u32, pub ranges: [QpgpuFriRange; 8] }
+#[repr(C)] pub struct QpgpuFriParams { pub rate_bits: u32, pub cap_height: u32, pub proof_of_work_bits: u32, pub num_query_rounds: u32,
+                                       pub num_reduction_rounds: u32, pub reduction_arity_bits: [u32; 16] }
 pub const QPGPU_STAGE_ERR_CAP: usize = 256;
 
 pub const QPGPU_OK: i32 = 0;
@@ -92,6 +98,20 @@ extern "C" {
     pub fn qpgpu_stage_quotient(plan: *mut QpgpuStagePlan, wires_oracle: *const QpgpuOracle, zs_pp_oracle: *const QpgpuOracle,
                                 betas: *const u64, gammas: *const u64, alphas: *const u64, public_inputs_hash: *const u64,
                                 d_out: *mut u64) -> i32;
+    // include/qpgpu.h — stages s8..s11 one step at a time: PolynomialBatch::prove_openings with the
+    // challenger, the proof-of-work rule and the query indices kept in Rust. qpgpu_fri_prove is the one-call form; use it unless the
+    // fork's prove_openings differs from what DESIGN.md section 9 lists. `Oracle::open` and `FriSession` below wrap these.
+    pub fn qpgpu_oracle_leaf_width(o: *const QpgpuOracle) -> usize;
+    pub fn qpgpu_oracle_open(o: *mut QpgpuOracle, indices: *const u64, n: usize, rows_out: *mut u64, paths_out: *mut u64) -> i32;
+    pub fn qpgpu_fri_begin(ctx: *mut QpgpuCtx, oracles: *const *mut QpgpuOracle, n: u32, batches: *const QpgpuFriBatch, n_batches: u32,
+                           params: *const QpgpuFriParams, alpha: *const u64, out: *mut *mut QpgpuFriSession) -> i32;
+    pub fn qpgpu_fri_round_commit(s: *mut QpgpuFriSession, cap_out: *mut u64, cap_words: usize) -> i32;
+    pub fn qpgpu_fri_round_fold(s: *mut QpgpuFriSession, beta: *const u64) -> i32;
+    pub fn qpgpu_fri_final_poly(s: *mut QpgpuFriSession, out: *mut u64, out_words: usize, num_coeffs: *mut usize) -> i32;
+    pub fn qpgpu_fri_query_size(s: *const QpgpuFriSession) -> usize;
+    pub fn qpgpu_fri_open(s: *mut QpgpuFriSession, indices: *const u64, n: usize, out: *mut u8, out_cap: usize, out_len: *mut usize) -> i32;
+    pub fn qpgpu_fri_session_free(s: *mut QpgpuFriSession);
+    pub fn qpgpu_fri_grind(ctx: *mut QpgpuCtx, c: *const QpgpuChallenger, proof_of_work_bits: u32, nonce_out: *mut u64) -> i32;
     pub fn qpgpu_circuit_constants_sigmas_cap(c: *const QpgpuCircuit, out: *mut u64, out_words: usize) -> i32;
     // include/qpgpu_verify.h — host-side verification of the bytes the GPU produced (debug self-check; production keeps
     // plonky2's own `VerifierCircuitData::verify`, which is what consumers of the proof run anyway)
@@ -572,4 +592,77 @@ impl GpuCircuit {
 
 impl Drop for GpuCircuit {
     fn drop(&mut self) { unsafe { qpgpu_circuit_free(self.circuit); qpgpu_ctx_destroy(self.ctx); } }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Stage-level route, s8..s11 step by step. `Oracle` borrows a committed batch made elsewhere
+// (qpgpu_oracle_commit); `FriSession` is PolynomialBatch::prove_openings with the transcript on the Rust side:
+//
+//   let mut fs = FriSession::begin(ctx, &[o_cs, o_wires, o_zs, o_q], &batches, &fri_params, degree_bits, challenger.get_extension_challenge())?;
+//   for _ in 0..fri_params.num_reduction_rounds {
+//       let cap = fs.round_commit()?;  challenger.observe_cap(&cap);
+//       fs.round_fold(challenger.get_extension_challenge())?;
+//   }
+//   let final_poly = fs.final_poly()?;  challenger.observe_extension_elements(&final_poly);
+//   let nonce = fri_grind(ctx, &challenger.to_qpgpu(), pow_bits)?;          // or the fork's own rule
+//   challenger.observe_element(nonce);  let _response = challenger.get_challenge();
+//   let indices: Vec<u64> = (0..num_query_rounds).map(|_| challenger.get_challenge().to_canonical_u64() % lde_size).collect();
+//   let query_rounds = fs.open(&indices)?;                                  // FriQueryRound bytes, write_fri_proof order
+// ---------------------------------------------------------------------------------------------------------------------
+pub struct Oracle { pub ctx: *mut QpgpuCtx, pub raw: *mut QpgpuOracle, pub path_len: usize }
+
+impl Oracle {
+    /// MerkleTree::prove at leaf indices: (rows, n x leaf_width words; paths, n x path_len x 4 words, leaf layer upwards)
+    pub fn open(&self, indices: &[u64]) -> Result<(Vec<u64>, Vec<u64>)> {
+        let width = unsafe { qpgpu_oracle_leaf_width(self.raw) };
+        let (mut rows, mut paths) = (vec![0u64; indices.len() * width], vec![0u64; indices.len() * self.path_len * 4]);
+        if unsafe { qpgpu_oracle_open(self.raw, indices.as_ptr(), indices.len(), rows.as_mut_ptr(), paths.as_mut_ptr()) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
+        Ok((rows, paths))
+    }
+}
+
+pub struct FriSession { ctx: *mut QpgpuCtx, raw: *mut QpgpuFriSession, cap_words: usize, final_words: usize }
+
+impl FriSession {
+    /// degree_bits: of the oracles. The oracles must outlive the session.
+    pub fn begin(ctx: *mut QpgpuCtx, oracles: &[*mut QpgpuOracle], batches: &[QpgpuFriBatch], params: &QpgpuFriParams, degree_bits: u32,
+                 alpha: [u64; 2]) -> Result<Self> {
+        let mut raw: *mut QpgpuFriSession = core::ptr::null_mut();
+        if unsafe { qpgpu_fri_begin(ctx, oracles.as_ptr(), oracles.len() as u32, batches.as_ptr(), batches.len() as u32, params, alpha.as_ptr(), &mut raw) } != QPGPU_OK {
+            bail!("{}", last_error(ctx))
+        }
+        let folded: u32 = params.reduction_arity_bits[..params.num_reduction_rounds as usize].iter().sum();
+        Ok(Self { ctx, raw, cap_words: 4usize << params.cap_height, final_words: 2usize << (degree_bits - folded) })
+    }
+    pub fn round_commit(&mut self) -> Result<Vec<u64>> {
+        let mut cap = vec![0u64; self.cap_words];
+        if unsafe { qpgpu_fri_round_commit(self.raw, cap.as_mut_ptr(), cap.len()) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
+        Ok(cap)
+    }
+    pub fn round_fold(&mut self, beta: [u64; 2]) -> Result<()> {
+        if unsafe { qpgpu_fri_round_fold(self.raw, beta.as_ptr()) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
+        Ok(())
+    }
+    /// coefficients as word pairs
+    pub fn final_poly(&mut self) -> Result<Vec<u64>> {
+        let (mut out, mut n) = (vec![0u64; self.final_words], 0usize);
+        if unsafe { qpgpu_fri_final_poly(self.raw, out.as_mut_ptr(), out.len(), &mut n) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
+        Ok(out)
+    }
+    /// the FriQueryRound bytes of each index, back to back
+    pub fn open(&mut self, indices: &[u64]) -> Result<Vec<u8>> {
+        let (mut out, mut len) = (vec![0u8; indices.len() * unsafe { qpgpu_fri_query_size(self.raw) }], 0usize);
+        if unsafe { qpgpu_fri_open(self.raw, indices.as_ptr(), indices.len(), out.as_mut_ptr(), out.len(), &mut len) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
+        out.truncate(len);
+        Ok(out)
+    }
+}
+
+impl Drop for FriSession { fn drop(&mut self) { unsafe { qpgpu_fri_session_free(self.raw) } } }
+
+/// the minimum nonce under qpgpu_fri_prove's proof-of-work rule; the challenger is not advanced
+pub fn fri_grind(ctx: *mut QpgpuCtx, challenger: &QpgpuChallenger, proof_of_work_bits: u32) -> Result<u64> {
+    let mut nonce = 0u64;
+    if unsafe { qpgpu_fri_grind(ctx, challenger, proof_of_work_bits, &mut nonce) } != QPGPU_OK { bail!("{}", last_error(ctx)) }
+    Ok(nonce)
 }

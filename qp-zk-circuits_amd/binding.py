@@ -148,6 +148,8 @@ def load_library():
         "qpgpu_oracle_eval": (c.c_int, [vp, u64p, c.c_uint32, c.c_uint32, u64p]),
         "qpgpu_oracle_read": (c.c_int, [vp, c.c_uint, c.c_uint32, c.c_uint32, u64p]),
         "qpgpu_oracle_device_ptrs": (c.c_int, [vp, c.POINTER(vp), c.POINTER(vp), c.POINTER(vp)]),
+        "qpgpu_oracle_open": (c.c_int, [vp, u64p, c.c_size_t, u64p, u64p]),
+        "qpgpu_oracle_leaf_width": (c.c_size_t, [vp]),
         "qpgpu_stage_plan_create": (c.c_int, [vp, u64p, c.c_size_t, vp, c.POINTER(vp), c.c_char_p]),
         "qpgpu_stage_plan_free": (None, [vp]),
         "qpgpu_stage_plan_info": (c.c_int, [vp, c.POINTER(c.c_uint), c.POINTER(c.c_uint), c.POINTER(c.c_uint), c.POINTER(c.c_uint),
@@ -160,6 +162,14 @@ def load_library():
         "qpgpu_fri_proof_size": (c.c_size_t, [c.POINTER(vp), c.c_uint32, vp]),
         "qpgpu_fri_prove": (c.c_int, [vp, c.POINTER(vp), c.c_uint32, vp, c.c_uint32, vp, vp, vp, c.c_size_t,
                                       c.POINTER(c.c_size_t)]),
+        "qpgpu_fri_begin": (c.c_int, [vp, c.POINTER(vp), c.c_uint32, vp, c.c_uint32, vp, u64p, c.POINTER(vp)]),
+        "qpgpu_fri_round_commit": (c.c_int, [vp, u64p, c.c_size_t]),
+        "qpgpu_fri_round_fold": (c.c_int, [vp, u64p]),
+        "qpgpu_fri_final_poly": (c.c_int, [vp, u64p, c.c_size_t, c.POINTER(c.c_size_t)]),
+        "qpgpu_fri_query_size": (c.c_size_t, [vp]),
+        "qpgpu_fri_open": (c.c_int, [vp, u64p, c.c_size_t, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
+        "qpgpu_fri_session_free": (None, [vp]),
+        "qpgpu_fri_grind": (c.c_int, [vp, vp, c.c_uint, c.POINTER(c.c_uint64)]),
         "qpgpu_field_probe": (c.c_int, [vp, c.c_uint, c.c_uint, u64p, u64p, c.c_size_t, u64p, c.c_size_t, c.c_int]),
         "qpgpu_synth_pack_words": (c.c_size_t, [c.c_uint, c.c_uint, c.c_uint]),
         "qpgpu_synth_pack_words_ex": (c.c_size_t, [c.c_uint, c.c_uint, c.c_uint, c.c_uint]),
@@ -793,6 +803,22 @@ class PolyOracle:
         self.gpu._check(self.gpu.lib.qpgpu_oracle_read(self.h, 1 if lde else 0, first, count, out.ctypes.data))
         return out
 
+    @property
+    def leaf_width(self):
+        """Words of a Merkle leaf: num_polys, + 4 salt words for a blinded oracle."""
+        return int(self.gpu.lib.qpgpu_oracle_leaf_width(self.h))
+
+    def open(self, indices, rows=True, paths=True):
+        """MerkleTree::prove at leaf indices: (rows [n, leaf_width], paths [n, degree_bits + rate_bits - cap_height, 4]); an
+        output that is not asked for comes back as None."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).ravel()
+        plen = self.degree_bits + self.rate_bits - self.cap_height
+        r = np.empty((idx.size, self.leaf_width), dtype=np.uint64) if rows else None
+        p = np.empty((idx.size, plen, 4), dtype=np.uint64) if paths else None
+        self.gpu._check(self.gpu.lib.qpgpu_oracle_open(self.h, idx.ctypes.data if idx.size else None, idx.size,
+                                                       r.ctypes.data if rows else None, p.ctypes.data if paths else None))
+        return r, p
+
 
 STAGE_ERR_CAP = 256
 
@@ -873,10 +899,7 @@ class StagePlan:
         return out
 
 
-def fri_prove(gpu, oracles, batches, challenger, reduction_arity_bits, rate_bits=3, cap_height=4, proof_of_work_bits=16,
-              num_query_rounds=28):
-    """PolynomialBatch::prove_openings. batches: [(point(a, b), [(oracle, first, count), ...]), ...]; challenger is
-    advanced in place. Returns the FriProof bytes."""
+def _fri_args(oracles, batches, reduction_arity_bits, rate_bits, cap_height, proof_of_work_bits, num_query_rounds):
     hs = (ctypes.c_void_p * len(oracles))(*[o.h for o in oracles])
     bs = (_FriBatch * len(batches))()
     for b, (point, ranges) in zip(bs, batches):
@@ -887,6 +910,14 @@ def fri_prove(gpu, oracles, batches, challenger, reduction_arity_bits, rate_bits
     prm = _FriParams(rate_bits, cap_height, proof_of_work_bits, num_query_rounds, len(reduction_arity_bits))
     for i, a in enumerate(reduction_arity_bits):
         prm.reduction_arity_bits[i] = a
+    return hs, bs, prm
+
+
+def fri_prove(gpu, oracles, batches, challenger, reduction_arity_bits, rate_bits=3, cap_height=4, proof_of_work_bits=16,
+              num_query_rounds=28):
+    """PolynomialBatch::prove_openings. batches: [(point(a, b), [(oracle, first, count), ...]), ...]; challenger is
+    advanced in place. Returns the FriProof bytes."""
+    hs, bs, prm = _fri_args(oracles, batches, reduction_arity_bits, rate_bits, cap_height, proof_of_work_bits, num_query_rounds)
     size = gpu.lib.qpgpu_fri_proof_size(hs, len(oracles), ctypes.byref(prm))
     if size == 0:
         raise QpGpuError(-1, "fri_prove: bad oracles or FRI parameters")
@@ -895,6 +926,76 @@ def fri_prove(gpu, oracles, batches, challenger, reduction_arity_bits, rate_bits
     gpu._check(gpu.lib.qpgpu_fri_prove(gpu.ctx, hs, len(oracles), ctypes.byref(bs), len(batches), ctypes.byref(prm),
                                        ctypes.byref(challenger.state), out.ctypes.data, out.size, ctypes.byref(ln)))
     return out[:ln.value].tobytes()
+
+
+def fri_grind(gpu, challenger, proof_of_work_bits):
+    """The minimum proof-of-work nonce for a transcript in `challenger`'s state (qpgpu_fri_grind); the challenger is not advanced."""
+    nonce = ctypes.c_uint64()
+    gpu._check(gpu.lib.qpgpu_fri_grind(gpu.ctx, ctypes.byref(challenger.state), proof_of_work_bits, ctypes.byref(nonce)))
+    return int(nonce.value)
+
+
+class FriSession:
+    """qpgpu_fri_session: the FRI opening proof one step at a time; the caller keeps the transcript. Arguments as fri_prove's, with
+    the FRI alpha in place of the challenger. A context manager; the oracles must stay open as long as the session.
+
+        with FriSession(gpu, oracles, batches, ch.get_n(2), arity_bits, rate_bits=3, cap_height=4) as fs:
+            for _ in arity_bits:
+                ch.observe(fs.round_commit()); fs.round_fold(ch.get_n(2))
+            final = fs.final_poly(); ch.observe(final)
+            nonce = fri_grind(gpu, ch, pow_bits); ch.observe([nonce]); ch.get()
+            queries = fs.open([ch.get() % fs.lde_size for _ in range(num_query_rounds)])"""
+
+    def __init__(self, gpu, oracles, batches, alpha, reduction_arity_bits, rate_bits=3, cap_height=4):
+        self.gpu, self.oracles = gpu, list(oracles)
+        hs, bs, prm = _fri_args(oracles, batches, reduction_arity_bits, rate_bits, cap_height, 0, 0)
+        a = np.array([int(alpha[0]), int(alpha[1])], dtype=np.uint64)
+        h = ctypes.c_void_p()
+        gpu._check(gpu.lib.qpgpu_fri_begin(gpu.ctx, hs, len(oracles), ctypes.byref(bs), len(batches), ctypes.byref(prm), a.ctypes.data,
+                                           ctypes.byref(h)))
+        self.h = h
+        self.cap_height, self.arity_bits = cap_height, list(reduction_arity_bits)
+        self.lde_size = 1 << (oracles[0].degree_bits + rate_bits)
+        self.final_len = 1 << (oracles[0].degree_bits - sum(self.arity_bits))
+        self.query_size = int(gpu.lib.qpgpu_fri_query_size(h))
+
+    def close(self):
+        if self.h:
+            self.gpu.lib.qpgpu_fri_session_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def round_commit(self):
+        """Commit the current layer: its cap, [2^cap_height, 4]."""
+        cap = np.empty((1 << self.cap_height, 4), dtype=np.uint64)
+        self.gpu._check(self.gpu.lib.qpgpu_fri_round_commit(self.h, cap.ctypes.data, cap.size))
+        return cap
+
+    def round_fold(self, beta):
+        b = np.array([int(beta[0]), int(beta[1])], dtype=np.uint64)
+        self.gpu._check(self.gpu.lib.qpgpu_fri_round_fold(self.h, b.ctypes.data))
+
+    def final_poly(self):
+        """The final polynomial's coefficients, [final_len, 2]."""
+        out = np.empty((self.final_len, 2), dtype=np.uint64)
+        n = ctypes.c_size_t()
+        self.gpu._check(self.gpu.lib.qpgpu_fri_final_poly(self.h, out.ctypes.data, out.size, ctypes.byref(n)))
+        assert n.value == self.final_len
+        return out
+
+    def open(self, indices):
+        """The FriQueryRound bytes of each index, back to back (query_size bytes each)."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).ravel()
+        out = np.empty(max(1, idx.size * self.query_size), dtype=np.uint8)
+        ln = ctypes.c_size_t()
+        self.gpu._check(self.gpu.lib.qpgpu_fri_open(self.h, idx.ctypes.data if idx.size else None, idx.size, out.ctypes.data,
+                                                    idx.size * self.query_size, ctypes.byref(ln)))
+        return out[:ln.value].tobytes()
 
 
 class ProvingPool:

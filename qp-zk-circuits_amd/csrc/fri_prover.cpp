@@ -1,6 +1,7 @@
 // fri_prover.cpp — committed polynomial batches and the FRI opening prover (stages s2/s3 and s8..s11 of
 // SURVEY.md §8a), independent of any circuit: used by the all-in-one prover (prover.cpp) and exported stage by stage
-// through the C ABI (oracle_api.cpp). Follows qp-plonky2 1.5.5 `fri::oracle::PolynomialBatch::{from_values,
+// through the C ABI (oracle_api.cpp, fri_api.cpp). The opening prover is the step functions of fri_prover.hpp and fri_prove, the loop
+// over them. Follows qp-plonky2 1.5.5 `fri::oracle::PolynomialBatch::{from_values,
 // from_coeffs, prove_openings}` and `fri::prover::{fri_proof, fri_committed_trees, fri_proof_of_work,
 // fri_prover_query_rounds}` as reached from the reference's `prove()` call (wormhole/prover/src/lib.rs:171-175).
 //
@@ -9,8 +10,8 @@
 #include <sys/random.h>
 #include <algorithm>
 #include <string>
+#include "fri_prover.hpp"
 #include "merkle.hpp"
-#include "prover_host.hpp"
 #include "prover_kernels.hpp"
 
 using gl::e2;
@@ -145,13 +146,11 @@ void FriWork::bind(u64 *base, const FriParams &p, const std::vector<size_t> &lea
 
 size_t fri_proof_bytes(const FriParams &p, const std::vector<size_t> &leaf_widths) { return proof_part(p, leaf_widths).total; }
 
-int fri_prove(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracles, size_t n_oracles,
-              const std::vector<FriBatch> &batches, uint32_t nb, Challenger *chs, FriWork &w, Stager &stage, ByteWriter *outs) {
+int fri_begin(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracles, size_t n_oracles, const std::vector<FriBatch> &batches,
+              uint32_t nb, const e2 *alphas, FriWork &w, Stager &stage, bool one_call, FriState &s) {
     hipStream_t st = ctx->stream;
-    const HasherDev hd = ctx->hasher_dev();
     const unsigned d = p.degree_bits, L = d + p.rate_bits, cap_h = p.cap_h;
-    const u64 n = 1ull << d, lde_n = n << p.rate_bits;
-    const size_t cap_words = (1ull << cap_h) * 4;
+    const u64 n = 1ull << d;
     if (nb == 0 || nb > w.nb_cap) return ctx->fail(QPGPU_EINVAL, "fri_prove: batch larger than the workspace");
     if (w.proof.op.size() != n_oracles + p.arity_bits.size()) return ctx->fail(QPGPU_EINVAL, "fri_prove: workspace bound for other oracles or FRI rounds");
     for (size_t i = 0; i < n_oracles; i++) {
@@ -161,10 +160,6 @@ int fri_prove(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracl
     }
     { unsigned tot = 0; for (unsigned a : p.arity_bits) { tot += a; if (a == 0 || a > 8) return ctx->fail(QPGPU_EINVAL, "fri_prove: bad reduction arity"); }
       if (tot > d || L - tot < cap_h) return ctx->fail(QPGPU_EINVAL, "fri_prove: reduction schedule does not fit the degree / cap height"); }
-    if (p.pow_bits > 40) return ctx->fail(QPGPU_EINVAL, "fri_prove: proof_of_work_bits above 40");
-
-    std::vector<e2> fri_alpha(nb);
-    for (uint32_t b = 0; b < nb; b++) fri_alpha[b] = chs[b].get_ext();
 
     // ---- s8 batched opening polynomial: final = sum over batches, each shifted by alpha^(#polys of the later ones) ----
     size_t max_count = 0;
@@ -185,7 +180,7 @@ int fri_prove(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracl
         std::vector<e2> apw((size_t)nb * max_count);
         for (uint32_t b = 0; b < nb; b++) {
             e2 a = gl::e2_from(1);
-            for (size_t i = 0; i < max_count; i++) { apw[(size_t)b * max_count + i] = gl::e2_canon(a); a = gl::e2_mul(a, fri_alpha[b]); }
+            for (size_t i = 0; i < max_count; i++) { apw[(size_t)b * max_count + i] = gl::e2_canon(a); a = gl::e2_mul(a, alphas[b]); }
         }
         QP_TRY(stage.put_rows(ctx, (u64 *)w.alpha_ext, w.ws, (const u64 *)apw.data(), 2 * max_count, 2 * max_count, nb));
     }
@@ -207,7 +202,7 @@ int fri_prove(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracl
         std::vector<e2> pts(nb), shifts(nb);
         for (uint32_t b = 0; b < nb; b++) {
             pts[b] = gl::e2_canon(fb.points[b]);
-            shifts[b] = bi == 0 ? gl::e2_from(1) : gl::e2_canon(gl::e2_pow(fri_alpha[b], count));
+            shifts[b] = bi == 0 ? gl::e2_from(1) : gl::e2_canon(gl::e2_pow(alphas[b], count));
         }
         QP_TRY(stage.put(ctx, w.t_points, pts.data(), nb * sizeof(e2)));
         QP_TRY(stage.put(ctx, w.t_shifts, shifts.data(), nb * sizeof(e2)));
@@ -215,74 +210,95 @@ int fri_prove(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracl
     }
     ctx->prof_end();
 
-    // ---- s9 FRI commit phase ----
+    // ---- s9 FRI commit phase begins: values of the first layer = LDE of the two component columns, leaf order ----
+    s = FriState();
+    s.ctx = ctx; s.p = p; s.oracles.assign(oracles, oracles + n_oracles); s.nb = nb; s.w = &w; s.stage = &stage; s.one_call = one_call;
+    s.steps = FriSteps((unsigned)p.arity_bits.size());
+    s.shift = gl::MULT_GEN;
+    s.coef = w.fin; s.valid = n; s.log_len = L; s.slot = 0;
     ctx->prof_begin("prove_fri_commit");
-    std::vector<std::vector<u64>> fri_caps;     // per round: [nb][cap_words]
-    std::vector<unsigned> tree_log_leaves;
-    u64 shift = gl::MULT_GEN;
-    u64 *coef = w.fin;           // [2][valid] per proof
-    u64 valid = n; unsigned log_len = L;
-    size_t slot = 0;
     NttProofs np; np.nproofs = nb; np.in_ps = w.ws; np.out_ps = w.ws;
-    // values of the first layer: LDE of the two component columns, leaf order
-    QP_TRY(ntt_run(ctx, coef, w.vals, d, L, 2, false, true, shift, np));
-    for (size_t r = 0; r < p.arity_bits.size(); r++) {
-        const unsigned ab = p.arity_bits[r];
-        const u64 len = 1ull << log_len, arity = 1ull << ab;
-        const unsigned log_leaves = log_len - ab;
-        u64 *rows = w.leafrows[r];
-        QP_HIP(ctx, pk_interleave_ext(w.vals, w.vals + len, len, rows, nb, w.ws, w.ws, st));
-        // leaves = chunks of `arity` extension values = 2*arity consecutive felts
-        QP_HIP(ctx, merkle_leaf_hash_rows(rows, 1ull << log_leaves, (uint32_t)(2 * arity), w.digests[r], nb, w.ws, w.ws, hd, st));
-        {
-            u64 cnt = 1ull << log_leaves; u64 *lvl = w.digests[r];
-            QP_HIP(ctx, merkle_reduce_to_cap(lvl, cnt, 1ull << cap_h, nb, w.ws, hd, st));
-            while (cnt > (1ull << cap_h)) { lvl += cnt * 4; cnt >>= 1; }
-            std::vector<u64> capv(cap_words * nb);
-            QP_TRY(ctx->read_back_2d(capv.data(), lvl, w.ws * 8, cap_words * 8, nb));
-            fri_caps.push_back(capv);
-        }
-        tree_log_leaves.push_back(log_leaves);
-        std::vector<e2> betas(nb);
-        for (uint32_t b = 0; b < nb; b++) {
-            chs[b].observe(fri_caps.back().data() + (size_t)b * cap_words, cap_words);
-            betas[b] = gl::e2_canon(chs[b].get_ext());
-        }
-        QP_TRY(stage.put(ctx, w.t_betas, betas.data(), nb * sizeof(e2)));
-        const u64 new_valid = valid >> ab;
-        u64 *ncoef = w.coeffs[slot]; slot ^= 1;
-        QP_HIP(ctx, pk_fri_fold(coef, coef + valid, new_valid, (uint32_t)arity, w.t_betas, ncoef, ncoef + new_valid, nb, w.ws, w.ws, st));
-        coef = ncoef; valid = new_valid; log_len -= ab;
-        shift = gl::pow(shift, arity);
-        if (r + 1 < p.arity_bits.size()) {
-            unsigned lv = 0; while ((1ull << lv) < valid) lv++;
-            QP_TRY(ntt_run(ctx, coef, w.vals, lv, log_len, 2, false, true, shift, np));
-        }
-    }
-    std::vector<u64> final_coeffs(2 * valid * nb);   // per proof: component arrays [a...][b...]
-    QP_TRY(ctx->read_back_2d(final_coeffs.data(), coef, w.ws * 8, 2 * valid * 8, nb));
-    ctx->prof_end();
-    std::vector<std::vector<e2>> final_poly(nb, std::vector<e2>(valid));
-    for (uint32_t b = 0; b < nb; b++) {
-        const u64 *fc = final_coeffs.data() + (size_t)b * 2 * valid;
-        for (u64 i = 0; i < valid; i++) final_poly[b][i] = gl::e2_make(fc[i], fc[valid + i]);
-        chs[b].observe((const u64 *)final_poly[b].data(), 2 * valid);
-    }
+    QP_TRY(ntt_run(ctx, s.coef, w.vals, d, L, 2, false, true, s.shift, np));
+    if (!one_call) ctx->prof_end();
+    return QPGPU_OK;
+}
 
-    // ---- s10 proof of work: minimum nonce per proof ----
+int fri_round_commit(FriState &s) {
+    qpgpu_ctx *ctx = s.ctx; hipStream_t st = ctx->stream; FriWork &w = *s.w;
+    const HasherDev hd = ctx->hasher_dev();
+    const size_t r = s.steps.round;
+    const uint32_t nb = s.nb;
+    const unsigned ab = s.p.arity_bits[r], cap_h = s.p.cap_h;
+    const u64 len = 1ull << s.log_len, arity = 1ull << ab;
+    const unsigned log_leaves = s.log_len - ab;
+    const size_t cap_words = s.cap_words();
+    if (!s.one_call) ctx->prof_begin("prove_fri_commit");
+    u64 *rows = w.leafrows[r];
+    QP_HIP(ctx, pk_interleave_ext(w.vals, w.vals + len, len, rows, nb, w.ws, w.ws, st));
+    // leaves = chunks of `arity` extension values = 2*arity consecutive felts
+    QP_HIP(ctx, merkle_leaf_hash_rows(rows, 1ull << log_leaves, (uint32_t)(2 * arity), w.digests[r], nb, w.ws, w.ws, hd, st));
+    {
+        u64 cnt = 1ull << log_leaves; u64 *lvl = w.digests[r];
+        QP_HIP(ctx, merkle_reduce_to_cap(lvl, cnt, 1ull << cap_h, nb, w.ws, hd, st));
+        while (cnt > (1ull << cap_h)) { lvl += cnt * 4; cnt >>= 1; }
+        std::vector<u64> capv(cap_words * nb);
+        QP_TRY(ctx->read_back_2d(capv.data(), lvl, w.ws * 8, cap_words * 8, nb));
+        s.caps.push_back(capv);
+    }
+    if (!s.one_call) ctx->prof_end();
+    s.tree_log_leaves.push_back(log_leaves);
+    s.steps.done(FriSteps::COMMIT);
+    return QPGPU_OK;
+}
+
+int fri_round_fold(FriState &s, const e2 *betas) {
+    qpgpu_ctx *ctx = s.ctx; hipStream_t st = ctx->stream; FriWork &w = *s.w;
+    const size_t r = s.steps.round;
+    const uint32_t nb = s.nb;
+    const unsigned ab = s.p.arity_bits[r];
+    const u64 arity = 1ull << ab;
+    if (!s.one_call) ctx->prof_begin("prove_fri_commit");
+    QP_TRY(s.stage->put(ctx, w.t_betas, betas, nb * sizeof(e2)));
+    const u64 new_valid = s.valid >> ab;
+    u64 *ncoef = w.coeffs[s.slot]; s.slot ^= 1;
+    QP_HIP(ctx, pk_fri_fold(s.coef, s.coef + s.valid, new_valid, (uint32_t)arity, w.t_betas, ncoef, ncoef + new_valid, nb, w.ws, w.ws, st));
+    s.coef = ncoef; s.valid = new_valid; s.log_len -= ab;
+    s.shift = gl::pow(s.shift, arity);
+    s.steps.done(FriSteps::FOLD);
+    if (r + 1 < s.p.arity_bits.size()) {
+        unsigned lv = 0; while ((1ull << lv) < s.valid) lv++;
+        NttProofs np; np.nproofs = nb; np.in_ps = w.ws; np.out_ps = w.ws;
+        QP_TRY(ntt_run(ctx, s.coef, w.vals, lv, s.log_len, 2, false, true, s.shift, np));
+    }
+    if (!s.one_call) ctx->prof_end();
+    return QPGPU_OK;
+}
+
+int fri_final_poly(FriState &s, std::vector<u64> &out) {
+    qpgpu_ctx *ctx = s.ctx;
+    if (!s.one_call) ctx->prof_begin("prove_fri_commit");
+    out.resize(2 * s.valid * s.nb);   // per proof: component arrays [a...][b...]
+    QP_TRY(ctx->read_back_2d(out.data(), s.coef, s.w->ws * 8, 2 * s.valid * 8, s.nb));
+    ctx->prof_end();
+    return QPGPU_OK;
+}
+
+int fri_grind(qpgpu_ctx *ctx, const Challenger *chs, uint32_t nb, unsigned pow_bits, const PowTables &t, Stager &stage, u64 *witness) {
+    hipStream_t st = ctx->stream;
     ctx->prof_begin("prove_pow");
-    std::vector<u64> pow_witness(nb, 0);
-    if (p.pow_bits > 0) {
+    for (uint32_t b = 0; b < nb; b++) witness[b] = 0;
+    if (pow_bits > 0) {
+        const HasherDev hd = ctx->hasher_dev();
         std::vector<u64> states(12 * (size_t)nb);
         for (uint32_t b = 0; b < nb; b++) {
             std::memcpy(states.data() + 12 * (size_t)b, chs[b].state, 12 * 8);
             for (int i = 0; i < chs[b].n_in; i++) states[12 * (size_t)b + i] = chs[b].in[i];
             if (chs[b].n_in != chs[0].n_in) return ctx->fail(QPGPU_EDEVICE, "prove: transcripts of a batch diverged in length");
         }
-        QP_TRY(stage.put(ctx, w.pow_states, states.data(), states.size() * 8));
+        QP_TRY(stage.put(ctx, t.states, states.data(), states.size() * 8));
         PowArgs pw{};
-        pw.states = w.pow_states; pw.bases = w.pow_bases; pw.results = w.pow_results;
-        pw.pos = (uint32_t)chs[0].n_in; pw.pow_bits = p.pow_bits; pw.batch = nb;
+        pw.states = t.states; pw.bases = t.bases; pw.results = t.results;
+        pw.pos = (uint32_t)chs[0].n_in; pw.pow_bits = pow_bits; pw.batch = nb;
         // expected 2^pow_bits candidates per proof; a span of 4x that finds a proof's nonce 98 % of the time (all 32 of a batch
         // in a little over half of the batches; the rest take a second, nearly empty launch), and the kernel drops the candidates
         // above a nonce already found, so the span costs little beyond the expected work
@@ -291,74 +307,120 @@ int fri_prove(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracl
         std::vector<u64> bases(nb, 0), res(nb);
         std::vector<char> found(nb, 0);
         uint32_t n_found = 0;
-        QP_HIP(ctx, hipMemsetAsync(w.pow_results, 0xFF, 8 * (size_t)nb, st));
+        QP_HIP(ctx, hipMemsetAsync(t.results, 0xFF, 8 * (size_t)nb, st));
         const size_t stage_pos = stage.pos;
         for (u64 round = 0; n_found < nb; round++) {
             stage.pos = stage_pos;   // the previous round's upload has completed (read_back below syncs): its slot is free again
             for (uint32_t b = 0; b < nb; b++) bases[b] = found[b] ? ~0ull : round * span;
-            QP_TRY(stage.put(ctx, w.pow_bases, bases.data(), 8 * (size_t)nb));
+            QP_TRY(stage.put(ctx, t.bases, bases.data(), 8 * (size_t)nb));
             QP_HIP(ctx, pk_pow(pw, hd, st));
-            QP_TRY(ctx->read_back(res.data(), w.pow_results, 8 * (size_t)nb));
+            QP_TRY(ctx->read_back(res.data(), t.results, 8 * (size_t)nb));
             for (uint32_t b = 0; b < nb; b++)
-                if (!found[b] && res[b] != ~0ull) { pow_witness[b] = res[b]; found[b] = 1; n_found++; }
+                if (!found[b] && res[b] != ~0ull) { witness[b] = res[b]; found[b] = 1; n_found++; }
             if (round * span > (1ull << 41)) return ctx->fail(QPGPU_EDEVICE, "prove: proof of work not found");
         }
     }
     ctx->prof_end();
-    for (uint32_t b = 0; b < nb; b++) {
-        chs[b].observe(&pow_witness[b], 1);
-        (void)chs[b].get();   // the response, re-derived by the verifier
-    }
+    return QPGPU_OK;
+}
 
-    // ---- s11 queries ----
+int fri_gather(FriState &s, const u64 *qidx, uint32_t nq, ByteWriter *outs) {
+    qpgpu_ctx *ctx = s.ctx; hipStream_t st = ctx->stream; FriWork &w = *s.w;
+    const uint32_t nb = s.nb;
+    const size_t n_oracles = s.oracles.size();
+    const u64 lde_n = s.lde_n();
+    if (nq > s.p.num_queries) return ctx->fail(QPGPU_EINVAL, "fri_gather: more query indices than the workspace holds");
     ctx->prof_begin("prove_queries");
-    const uint32_t nqr = p.num_queries;
-    std::vector<u64> qidx((size_t)nqr * nb);
-    for (uint32_t b = 0; b < nb; b++)
-        for (uint32_t q = 0; q < nqr; q++) qidx[(size_t)b * nqr + q] = chs[b].get() % lde_n;
-    QP_TRY(stage.put(ctx, w.qidx, qidx.data(), qidx.size() * 8));
+    QP_TRY(s.stage->put(ctx, w.qidx, qidx, (size_t)nq * nb * 8));
     // gather layout (per section, all queries contiguous): for each oracle rows then paths; for each FRI round evals then paths
     struct Sec { size_t off, words; bool is_path; };
     std::vector<Sec> secs;
     size_t goff = 0;
     for (size_t i = 0; i < n_oracles; i++) {
-        const PolyOracle *o = oracles[i];
+        const PolyOracle *o = s.oracles[i];
         const uint32_t plen0 = (uint32_t)w.proof.op[i].path_len;
-        QP_HIP(ctx, pk_gather_rows(o->lde, lde_n, o->ncols, w.qidx, nqr, w.gather + goff, nb, o->ps_lde, w.ws, st));
-        secs.push_back({goff, o->ncols, false}); goff += (size_t)o->ncols * nqr;
+        QP_HIP(ctx, pk_gather_rows(o->lde, lde_n, o->ncols, w.qidx, nq, w.gather + goff, nb, o->ps_lde, w.ws, st));
+        secs.push_back({goff, o->ncols, false}); goff += (size_t)o->ncols * nq;
         if (o->salt) {
-            QP_HIP(ctx, pk_gather_rows(o->salt, lde_n, 4, w.qidx, nqr, w.gather + goff, nb, o->ps_salt, w.ws, st));
-            secs.push_back({goff, 4, false}); goff += (size_t)4 * nqr;
+            QP_HIP(ctx, pk_gather_rows(o->salt, lde_n, 4, w.qidx, nq, w.gather + goff, nb, o->ps_salt, w.ws, st));
+            secs.push_back({goff, 4, false}); goff += (size_t)4 * nq;
         }
-        QP_HIP(ctx, pk_gather_paths(o->digests, lde_n, plen0, w.qidx, 0, nqr, w.gather + goff, nb, o->ps_digests, w.ws, st));
-        secs.push_back({goff, (size_t)plen0 * 4, true}); goff += (size_t)plen0 * 4 * nqr;
+        QP_HIP(ctx, pk_gather_paths(o->digests, lde_n, plen0, w.qidx, 0, nq, w.gather + goff, nb, o->ps_digests, w.ws, st));
+        secs.push_back({goff, (size_t)plen0 * 4, true}); goff += (size_t)plen0 * 4 * nq;
     }
-    for (size_t r = 0; r < p.arity_bits.size(); r++) {
+    for (size_t r = 0; r < s.p.arity_bits.size(); r++) {
         const proof_layout::Opening &op = w.proof.op[n_oracles + r];
         const uint32_t width = (uint32_t)op.row_words, pl = (uint32_t)op.path_len, sh = (uint32_t)op.shift;
-        QP_HIP(ctx, pk_gather_leaf_rows(w.leafrows[r], width, w.qidx, sh, nqr, w.gather + goff, nb, w.ws, w.ws, st));
-        secs.push_back({goff, width, false}); goff += (size_t)width * nqr;
-        QP_HIP(ctx, pk_gather_paths(w.digests[r], 1ull << tree_log_leaves[r], pl, w.qidx, sh, nqr, w.gather + goff, nb, w.ws, w.ws, st));
-        secs.push_back({goff, (size_t)pl * 4, true}); goff += (size_t)pl * 4 * nqr;
+        QP_HIP(ctx, pk_gather_leaf_rows(w.leafrows[r], width, w.qidx, sh, nq, w.gather + goff, nb, w.ws, w.ws, st));
+        secs.push_back({goff, width, false}); goff += (size_t)width * nq;
+        QP_HIP(ctx, pk_gather_paths(w.digests[r], 1ull << s.tree_log_leaves[r], pl, w.qidx, sh, nq, w.gather + goff, nb, w.ws, w.ws, st));
+        secs.push_back({goff, (size_t)pl * 4, true}); goff += (size_t)pl * 4 * nq;
     }
-    if (goff != w.gather_words) return ctx->fail(QPGPU_EDEVICE, "prove: internal gather size mismatch");
+    if (goff * s.p.num_queries != w.gather_words * nq) return ctx->fail(QPGPU_EDEVICE, "prove: internal gather size mismatch");
     std::vector<u64> gathered(goff * nb);
     QP_TRY(ctx->read_back_2d(gathered.data(), w.gather, w.ws * 8, goff * 8, nb));
     ctx->prof_end();
-
-    // ---- FriProof bytes (util::serialization write_fri_proof): caps, query rounds, final poly, pow witness ----
+    // FriQueryRound bytes (util::serialization write_fri_query_rounds)
     for (uint32_t b = 0; b < nb; b++) {
-        ByteWriter &out = outs[b];
         const u64 *g = gathered.data() + (size_t)b * goff;
-        for (auto &cp : fri_caps) out.vec(cp.data() + (size_t)b * cap_words, cap_words);
-        for (uint32_t q = 0; q < nqr; q++) {
+        for (uint32_t q = 0; q < nq; q++) {
             for (const Sec &sc : secs) {
-                if (sc.is_path) out.u8((uint8_t)(sc.words / 4));   // write_merkle_proof: one-byte sibling count
-                out.vec(g + sc.off + (size_t)q * sc.words, sc.words);
+                if (sc.is_path) outs[b].u8((uint8_t)(sc.words / 4));   // write_merkle_proof: one-byte sibling count
+                outs[b].vec(g + sc.off + (size_t)q * sc.words, sc.words);
             }
         }
-        for (u64 i = 0; i < valid; i++) out.ext(final_poly[b][i]);
-        out.u64le(pow_witness[b]);
+    }
+    return QPGPU_OK;
+}
+
+int fri_prove(qpgpu_ctx *ctx, const FriParams &p, const PolyOracle *const *oracles, size_t n_oracles,
+              const std::vector<FriBatch> &batches, uint32_t nb, Challenger *chs, FriWork &w, Stager &stage, ByteWriter *outs) {
+    if (p.pow_bits > 40) return ctx->fail(QPGPU_EINVAL, "fri_prove: proof_of_work_bits above 40");
+    if (nb == 0 || nb > w.nb_cap) return ctx->fail(QPGPU_EINVAL, "fri_prove: batch larger than the workspace");
+    const u64 lde_n = 1ull << (p.degree_bits + p.rate_bits);
+    std::vector<e2> fri_alpha(nb);
+    for (uint32_t b = 0; b < nb; b++) fri_alpha[b] = chs[b].get_ext();
+
+    FriState s;
+    QP_TRY(fri_begin(ctx, p, oracles, n_oracles, batches, nb, fri_alpha.data(), w, stage, true, s));   // s8, first layer of s9
+    const size_t cap_words = s.cap_words();
+    std::vector<e2> betas(nb);
+    for (size_t r = 0; r < p.arity_bits.size(); r++) {                                                  // s9
+        QP_TRY(fri_round_commit(s));
+        for (uint32_t b = 0; b < nb; b++) {
+            chs[b].observe(s.caps.back().data() + (size_t)b * cap_words, cap_words);
+            betas[b] = gl::e2_canon(chs[b].get_ext());
+        }
+        QP_TRY(fri_round_fold(s, betas.data()));
+    }
+    std::vector<u64> final_coeffs;
+    QP_TRY(fri_final_poly(s, final_coeffs));
+    const u64 valid = s.valid;
+    std::vector<std::vector<e2>> final_poly(nb, std::vector<e2>(valid));
+    for (uint32_t b = 0; b < nb; b++) {
+        const u64 *fc = final_coeffs.data() + (size_t)b * 2 * valid;
+        for (u64 i = 0; i < valid; i++) final_poly[b][i] = gl::e2_make(fc[i], fc[valid + i]);
+        chs[b].observe((const u64 *)final_poly[b].data(), 2 * valid);
+    }
+
+    std::vector<u64> pow_witness(nb, 0);                                                                // s10: minimum nonce per proof
+    QP_TRY(fri_grind(ctx, chs, nb, p.pow_bits, PowTables{w.pow_states, w.pow_bases, w.pow_results}, stage, pow_witness.data()));
+    for (uint32_t b = 0; b < nb; b++) {
+        chs[b].observe(&pow_witness[b], 1);
+        (void)chs[b].get();   // the response, re-derived by the verifier
+    }
+
+    const uint32_t nqr = p.num_queries;                                                                 // s11
+    std::vector<u64> qidx((size_t)nqr * nb);
+    for (uint32_t b = 0; b < nb; b++)
+        for (uint32_t q = 0; q < nqr; q++) qidx[(size_t)b * nqr + q] = chs[b].get() % lde_n;
+    // FriProof bytes (util::serialization write_fri_proof): caps, query rounds, final poly, pow witness
+    for (uint32_t b = 0; b < nb; b++)
+        for (auto &cp : s.caps) outs[b].vec(cp.data() + (size_t)b * cap_words, cap_words);
+    QP_TRY(fri_gather(s, qidx.data(), nqr, outs));
+    for (uint32_t b = 0; b < nb; b++) {
+        for (u64 i = 0; i < valid; i++) outs[b].ext(final_poly[b][i]);
+        outs[b].u64le(pow_witness[b]);
     }
     return QPGPU_OK;
 }

@@ -1,7 +1,8 @@
-// oracle_api.cpp — stage-level C ABI: polynomial-batch commitments, opening evaluations, the challenger and the FRI
-// opening proof as separate calls (include/qpgpu.h, "stage-level entry points"). These are the circuit-independent
-// parts of qp-plonky2's prove(); a patched prover can keep its gate evaluation in Rust and use these for the rest.
+// oracle_api.cpp — stage-level C ABI: polynomial-batch commitments, their opening evaluations and Merkle openings, and the
+// challenger as separate calls (include/qpgpu.h, "stage-level entry points"; the FRI opening proof is fri_api.cpp). These are the
+// circuit-independent parts of qp-plonky2's prove(); a patched prover can keep its gate evaluation in Rust and use these for the rest.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <string>
 #include "merkle.hpp"
 #include "oracle_handle.hpp"
@@ -128,39 +129,63 @@ int qpgpu_oracle_device_ptrs(const qpgpu_oracle *h, const uint64_t **d_coeffs, c
     return QPGPU_OK;
 }
 
+size_t qpgpu_oracle_leaf_width(const qpgpu_oracle *h) { return h ? (size_t)h->o.ncols + (h->o.salt ? 4 : 0) : 0; }
+
+int qpgpu_oracle_open(qpgpu_oracle *h, const uint64_t *indices, size_t n, uint64_t *rows_out, uint64_t *paths_out) {
+    if (!h) return QPGPU_EINVAL;
+    qpgpu_ctx *ctx = h->ctx;
+    QP_DEV(ctx);
+    if (n == 0) return QPGPU_OK;
+    if (!indices) return ctx->fail(QPGPU_EINVAL, "oracle_open: indices is NULL");
+    const PolyOracle &o = h->o;
+    const u64 lde_n = o.lde_n();
+    for (size_t i = 0; i < n; i++)
+        if (indices[i] >= lde_n)
+            return ctx->fail(QPGPU_EINVAL, "oracle_open: indices[" + std::to_string(i) + "] = " + std::to_string(indices[i]) + " is not below 2^" + std::to_string(o.log_lde()));
+    const uint32_t plen = o.log_lde() - o.cap_h;
+    const size_t width = qpgpu_oracle_leaf_width(h), per = 1 + (rows_out ? width : 0) + (paths_out ? (size_t)plen * 4 : 0);
+    if (per == 1) return QPGPU_OK;
+    const size_t chunk = 256;                       // indices per pass: the gathers go through the context's scratch buffer
+    QP_TRY(ctx->ensure_scratch(std::min(n, chunk) * per * 8));
+    std::vector<u64> got;
+    for (size_t at = 0; at < n; at += chunk) {
+        const uint32_t m = (uint32_t)std::min(chunk, n - at);
+        u64 *d_idx = ctx->scratch, *d_rows = d_idx + m, *d_salt = d_rows + (rows_out ? (size_t)o.ncols * m : 0),
+            *d_paths = d_idx + m + (rows_out ? width * m : 0);
+        QP_HIP(ctx, hipMemcpyAsync(d_idx, indices + at, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (rows_out) {
+            QP_HIP(ctx, pk_gather_rows(o.lde, lde_n, o.ncols, d_idx, m, d_rows, 1, 0, 0, ctx->stream));
+            if (o.salt) QP_HIP(ctx, pk_gather_rows(o.salt, lde_n, 4, d_idx, m, d_salt, 1, 0, 0, ctx->stream));
+        }
+        if (paths_out) QP_HIP(ctx, pk_gather_paths(o.digests, lde_n, plen, d_idx, 0, m, d_paths, 1, 0, 0, ctx->stream));
+        got.resize((size_t)m * (per - 1));
+        QP_TRY(ctx->read_back(got.data(), d_rows, got.size() * 8));
+        if (rows_out)
+            for (uint32_t q = 0; q < m; q++) {      // the leaf as the proof carries it: the columns, then the salt
+                std::memcpy(rows_out + (at + q) * width, got.data() + (size_t)q * o.ncols, (size_t)o.ncols * 8);
+                if (o.salt) std::memcpy(rows_out + (at + q) * width + o.ncols, got.data() + (size_t)o.ncols * m + (size_t)q * 4, 32);
+            }
+        if (paths_out && plen) std::memcpy(paths_out + at * plen * 4, got.data() + (rows_out ? width * m : 0), (size_t)m * plen * 32);
+    }
+    return QPGPU_OK;
+}
+
 // ---- challenger (host only) ----
-// plonky2 never holds a full input buffer (a duplex runs when the eighth element arrives) nor more than eight outputs: a
-// state that says otherwise is invalid input
-static bool to_host(const qpgpu_challenger *c, Challenger &ch) {
-    if (c->input_len >= 8 || c->output_len > 8) return false;
-    std::memcpy(ch.state, c->sponge_state, sizeof ch.state);
-    ch.n_in = (int)c->input_len; ch.n_out = (int)c->output_len;
-    std::memcpy(ch.in, c->input_buffer, sizeof ch.in);
-    std::memcpy(ch.out, c->output_buffer, sizeof ch.out);
-    return true;
-}
-static void from_host(const Challenger &ch, qpgpu_challenger *c) {
-    std::memcpy(c->sponge_state, ch.state, sizeof ch.state);
-    std::memset(c->input_buffer, 0, sizeof c->input_buffer); std::memset(c->output_buffer, 0, sizeof c->output_buffer);
-    for (int i = 0; i < ch.n_in; i++) c->input_buffer[i] = ch.in[i];
-    for (int i = 0; i < ch.n_out; i++) c->output_buffer[i] = ch.out[i];
-    c->input_len = (uint32_t)ch.n_in; c->output_len = (uint32_t)ch.n_out;
-}
 void qpgpu_challenger_init(qpgpu_challenger *c) { if (c) std::memset(c, 0, sizeof *c); }
 static int challenger_observe(const hasher::Config &h, qpgpu_challenger *c, const uint64_t *elements, size_t n) {
     if (!c || (!elements && n)) return QPGPU_EINVAL;
     Challenger ch(h);
-    if (!to_host(c, ch)) return QPGPU_EINVAL;
+    if (!challenger_to_host(c, ch)) return QPGPU_EINVAL;
     ch.observe(elements, n);
-    from_host(ch, c);
+    challenger_from_host(ch, c);
     return QPGPU_OK;
 }
 static int challenger_get(const hasher::Config &h, qpgpu_challenger *c, uint64_t *out) {
     if (!c || !out) return QPGPU_EINVAL;
     Challenger ch(h);
-    if (!to_host(c, ch)) return QPGPU_EINVAL;
+    if (!challenger_to_host(c, ch)) return QPGPU_EINVAL;
     *out = ch.get();
-    from_host(ch, c);
+    challenger_from_host(ch, c);
     return QPGPU_OK;
 }
 // under the context's hasher
@@ -176,77 +201,6 @@ uint64_t qpgpu_challenger_get(qpgpu_challenger *c) {
     uint64_t v = 0;
     (void)challenger_get(hasher::process_default(), c, &v);
     return v;
-}
-
-// ---- FRI ----
-static int fri_setup(qpgpu_oracle *const *oracles, uint32_t n, const qpgpu_fri_params *params, FriParams &fp, std::vector<size_t> &widths, size_t &total_polys) {
-    if (!oracles || n == 0 || !params || params->num_reduction_rounds > 16) return QPGPU_EINVAL;
-    for (uint32_t i = 0; i < n; i++) if (!oracles[i] || oracles[i]->ctx != oracles[0]->ctx) return QPGPU_EINVAL;
-    fp.degree_bits = oracles[0]->o.log_n; fp.rate_bits = params->rate_bits; fp.cap_h = params->cap_height;
-    fp.pow_bits = params->proof_of_work_bits; fp.num_queries = params->num_query_rounds;
-    fp.arity_bits.assign(params->reduction_arity_bits, params->reduction_arity_bits + params->num_reduction_rounds);
-    unsigned tot = 0;
-    for (unsigned a : fp.arity_bits) { if (a == 0 || a > 8) return QPGPU_EINVAL; tot += a; }
-    if (tot > fp.degree_bits || fp.degree_bits + fp.rate_bits < tot + fp.cap_h || fp.pow_bits > 40 || fp.num_queries == 0 || fp.num_queries > 4096) return QPGPU_EINVAL;
-    widths.clear(); total_polys = 0;
-    for (uint32_t i = 0; i < n; i++) { widths.push_back(oracles[i]->o.ncols + (oracles[i]->o.salt ? 4 : 0)); total_polys += oracles[i]->o.ncols; }
-    return QPGPU_OK;
-}
-
-size_t qpgpu_fri_proof_size(qpgpu_oracle *const *oracles, uint32_t num_oracles, const qpgpu_fri_params *params) {
-    FriParams fp; std::vector<size_t> widths; size_t total = 0;
-    if (fri_setup(oracles, num_oracles, params, fp, widths, total) != QPGPU_OK) return 0;
-    return fri_proof_bytes(fp, widths);
-}
-
-int qpgpu_fri_prove(qpgpu_ctx *ctx, qpgpu_oracle *const *oracles, uint32_t num_oracles, const qpgpu_fri_batch *batches,
-                    uint32_t num_batches, const qpgpu_fri_params *params, qpgpu_challenger *challenger,
-                    uint8_t *out, size_t out_cap, size_t *out_len) {
-    if (!ctx) return QPGPU_EINVAL;
-    QP_DEV(ctx);
-    if (!batches || num_batches == 0 || !challenger || !out) return ctx->fail(QPGPU_EINVAL, "fri_prove: null argument");
-    FriParams fp; std::vector<size_t> widths; size_t total_polys = 0;
-    if (fri_setup(oracles, num_oracles, params, fp, widths, total_polys) != QPGPU_OK || oracles[0]->ctx != ctx)
-        return ctx->fail(QPGPU_EINVAL, "fri_prove: bad oracles or FRI parameters");
-    if (challenger->input_len >= 8 || challenger->output_len > 8) return ctx->fail(QPGPU_EINVAL, "fri_prove: invalid challenger state (input_len must be < 8, output_len <= 8)");
-    std::vector<FriBatch> bs(num_batches);
-    size_t max_count = 0;
-    for (uint32_t b = 0; b < num_batches; b++) {
-        if (batches[b].num_ranges == 0 || batches[b].num_ranges > 8) return ctx->fail(QPGPU_EINVAL, "fri_prove: a batch needs 1..8 polynomial ranges");
-        bs[b].points = {gl::e2_make(gl::canon(batches[b].point[0]), gl::canon(batches[b].point[1]))};
-        size_t cnt = 0;
-        for (uint32_t r = 0; r < batches[b].num_ranges; r++) {
-            const qpgpu_fri_range &rg = batches[b].ranges[r];
-            bs[b].ranges.push_back({rg.oracle, rg.first, rg.count});
-            cnt += rg.count;
-        }
-        max_count = std::max(max_count, cnt);
-    }
-    std::vector<const PolyOracle *> os;
-    for (uint32_t i = 0; i < num_oracles; i++) os.push_back(&oracles[i]->o);
-    // workspace: one device allocation and one pinned staging block per call
-    void *dv = nullptr, *hv = nullptr;
-    const size_t work_words = FriWork::words(fp, widths, max_count, 1);
-    QP_HIP(ctx, hipMalloc(&dv, work_words * 8));
-    Stager stage;
-    stage.words = FriWork::stage_words(fp, max_count, 1);
-    hipError_t e = hipHostMalloc(&hv, stage.words * 8, hipHostMallocDefault);
-    if (e != hipSuccess) { (void)hipFree(dv); return ctx->hip_fail(e, "hipHostMalloc(fri stage)"); }
-    stage.h = (u64 *)hv;
-    FriWork work;
-    work.bind((u64 *)dv, fp, widths, max_count, 1);
-    Challenger ch(ctx->hasher); (void)to_host(challenger, ch);
-    ByteWriter w{out, out_cap};
-    int rc = fri_prove(ctx, fp, os.data(), os.size(), bs, 1, &ch, work, stage, &w);
-    // the workspace holds alpha-combinations of the committed (possibly secret) polynomials: clear it before release
-    (void)hipMemsetAsync(dv, 0, work_words * 8, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(dv); (void)hipHostFree(hv);
-    if (rc != QPGPU_OK) return rc;
-    from_host(ch, challenger);
-    if (out_len) *out_len = w.len;
-    if (w.overflow) return ctx->fail(QPGPU_EBUFSIZE, "fri_prove: output buffer too small");
-    return QPGPU_OK;
 }
 
 }  // extern "C"
