@@ -305,6 +305,35 @@ int qpgpu_oracle_device_ptrs(const qpgpu_oracle *o, const uint64_t **d_coeffs, c
 int qpgpu_oracle_open(qpgpu_oracle *o, const uint64_t *indices, size_t n, uint64_t *rows_out, uint64_t *paths_out);
 size_t qpgpu_oracle_leaf_width(const qpgpu_oracle *o);   /* num_polys, + 4 for a blinded oracle */
 
+/* ---- lockstep batches of the stage flow: one call per stage for `batch` proofs of one circuit ------------------
+ * qpgpu_prove_batch_dev launches every stage once for up to max_batch proofs; the entries below give the stage route the same
+ * batch dimension, on the same launch sequences (proof = grid.z or a folded leading dimension), so a patched prove() that keeps its
+ * own transcript can prove a level of leaves in lockstep. batch is 1..1024 everywhere. The transcripts stay with the caller, one per
+ * proof; arrays are [batch][...], dense, proof b first. A batch of one through these entries gives what the single-proof entries give.
+ *
+ * One qpgpu_oracle may hold the committed batches of `batch` proofs. polys[b]: proof b's num_polys x 2^degree_bits matrix, on the
+ * host or (QPGPU_ORACLE_DEVICE_INPUT) on the device, where the matrices may lie back to back (used in place) or be separate
+ * allocations (gathered; same result). Flags, limits and messages are qpgpu_oracle_commit's. With QPGPU_ORACLE_BLINDING proof b's
+ * key is derived from blinding_seed + b when the seed is non-zero (qpgpu_circuit_set_blinding_seed's rule for a batch); seed 0
+ * draws 256 fresh bits per proof. The host copy of the keys is overwritten as soon as the device has them. */
+int qpgpu_oracle_commit_batch(qpgpu_ctx *ctx, const uint64_t *const *polys, uint32_t batch, uint32_t num_polys, unsigned degree_bits,
+                              unsigned rate_bits, unsigned cap_height, unsigned flags, uint64_t blinding_seed, uint32_t blinding_stream,
+                              qpgpu_oracle **out);
+uint32_t qpgpu_oracle_batch(const qpgpu_oracle *o);   /* proofs the oracle holds; 1 for qpgpu_oracle_commit's */
+/* words between two proofs' coefficients, LDEs and digests (qpgpu_oracle_device_ptrs gives proof 0's base); 0, 0, 0 at batch 1.
+ * Any out-pointer may be NULL. */
+int qpgpu_oracle_strides(const qpgpu_oracle *o, uint64_t *coeffs, uint64_t *lde, uint64_t *digests);
+/* On a batched oracle qpgpu_oracle_cap returns batch x (4 << cap_height) words (a smaller out_words is QPGPU_EINVAL),
+ * qpgpu_oracle_leaf_width, _device_ptrs and _free work as for any oracle, and qpgpu_oracle_eval, _read and _open are QPGPU_EINVAL
+ * naming the entry to use: they do not silently serve proof 0.
+ * qpgpu_oracle_eval_batch: proof b's polynomials [first, first + count) at proof b's point; points [batch][2], out
+ * [batch][count][2]. One upload, one launch, one read-back for the whole batch. */
+int qpgpu_oracle_eval_batch(qpgpu_oracle *o, const uint64_t *points, uint32_t first, uint32_t count, uint64_t *out);
+/* qpgpu_oracle_open for every proof: indices [batch][n] (each proof its own), rows_out [batch][n][leaf_width], paths_out
+ * [batch][n][path][4]; either out may be NULL. One gather per 256 indices for all proofs together. An index out of range is
+ * QPGPU_EINVAL naming indices[b][i]; outputs untouched. */
+int qpgpu_oracle_open_batch(qpgpu_oracle *o, const uint64_t *indices, size_t n, uint64_t *rows_out, uint64_t *paths_out);
+
 /* plonky2::iop::challenger::Challenger as plain data: buffers are Vec<F> contents, lengths their len() */
 typedef struct {
     uint64_t sponge_state[12];
@@ -370,6 +399,31 @@ void qpgpu_fri_session_free(qpgpu_fri_session *s);   /* overwrites the workspace
  * plonky2 cannot be in: QPGPU_EINVAL. */
 int qpgpu_fri_grind(qpgpu_ctx *ctx, const qpgpu_challenger *c, unsigned proof_of_work_bits, uint64_t *nonce_out);
 
+/* The FRI opening proof for a lockstep batch. Every oracle holds `batch` proofs (qpgpu_oracle_batch == batch) or one proof shared
+ * by all of them (== 1: the constants/sigmas oracle); anything else is QPGPU_EINVAL naming the oracle. The `point` field of each
+ * qpgpu_fri_batch is NOT read: proof b's point for opening batch k is points[k][b] (points: [num_batches][batch][2]).
+ * qpgpu_fri_prove_batch: challengers [batch], advanced in place; outs[b] receives proof b's FriProof bytes (out_cap each),
+ * out_lens[b] its length (out_lens may be NULL). The transcripts advance together: the bytes are those of `batch` calls of
+ * qpgpu_fri_prove. */
+int qpgpu_fri_prove_batch(qpgpu_ctx *ctx, qpgpu_oracle *const *oracles, uint32_t num_oracles, const qpgpu_fri_batch *batches,
+                          uint32_t num_batches, const uint64_t *points, uint32_t batch, const qpgpu_fri_params *params,
+                          qpgpu_challenger *challengers, uint8_t *const *outs, size_t out_cap, size_t *out_lens);
+/* A session of `batch` proofs; alphas [batch][2]. The step entries above keep their prototypes and read the session's batch
+ * count; their arrays hold the proofs back to back:
+ *   qpgpu_fri_round_commit   cap_words  exactly batch * (4 << cap_height)
+ *   qpgpu_fri_round_fold     beta       [batch][2]
+ *   qpgpu_fri_final_poly     out_words  exactly batch x the single-proof count (*num_coeffs stays per proof)
+ *   qpgpu_fri_open           indices    [batch][n]; out [batch][n * qpgpu_fri_query_size(s)]; out_cap, out_len: the total
+ * A wrong size is QPGPU_EINVAL naming the expected number; nothing is written and the session stays usable. The order rules are
+ * unchanged; qpgpu_fri_round_fold still only queues work. */
+int qpgpu_fri_begin_batch(qpgpu_ctx *ctx, qpgpu_oracle *const *oracles, uint32_t num_oracles, const qpgpu_fri_batch *batches,
+                          uint32_t num_batches, const uint64_t *points, uint32_t batch, const qpgpu_fri_params *params,
+                          const uint64_t *alphas, qpgpu_fri_session **out);
+uint32_t qpgpu_fri_session_batch(const qpgpu_fri_session *s);   /* 1 for qpgpu_fri_begin's */
+/* qpgpu_fri_grind for `batch` transcripts in one search: cs [batch] (not modified; all at the same point of the transcript, i.e.
+ * with the same number of pending inputs, QPGPU_EINVAL otherwise), nonces_out [batch]. */
+int qpgpu_fri_grind_batch(qpgpu_ctx *ctx, const qpgpu_challenger *cs, uint32_t batch, unsigned proof_of_work_bits, uint64_t *nonces_out);
+
 /* ---- stages s5 and s6 of the stage flow: partial products and the quotient on the device ----------------------
  * A qpgpu_stage_plan holds what the two gate-dependent stages need and what does not depend on a witness — what a circuit
  * handle prepares at load: the sigma values on the subgroup (forward NTT of the constants/sigmas oracle's coefficients), the
@@ -417,6 +471,28 @@ int qpgpu_stage_partial_products(qpgpu_stage_plan *plan, const uint64_t *wires, 
 int qpgpu_stage_quotient(qpgpu_stage_plan *plan, const qpgpu_oracle *wires_oracle, const qpgpu_oracle *zs_pp_oracle,
                          const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas, const uint64_t *public_inputs_hash,
                          uint64_t *d_out);
+
+/* The two stages for a lockstep batch. qpgpu_stage_plan_create_batch: a plan whose workspace holds max_batch proofs (1..1024,
+ * checked together with the header, before ctx or cs_oracle is looked at: the refusal needs no device); qpgpu_stage_plan_create is
+ * max_batch = 1. cs_oracle is the constants/sigmas commitment shared by all proofs: it must hold one proof (QPGPU_EINVAL names it
+ * otherwise). */
+int qpgpu_stage_plan_create_batch(qpgpu_ctx *ctx, const uint64_t *words, size_t n_words, const qpgpu_oracle *cs_oracle,
+                                  uint32_t max_batch, qpgpu_stage_plan **out, char *err);
+uint32_t qpgpu_stage_plan_max_batch(const qpgpu_stage_plan *plan);
+/* s5 for `batch` witnesses (batch > max_batch is QPGPU_EINVAL naming it): wires[b] is proof b's matrix, on the host or, with
+ * wires_on_device != 0, in HBM, back to back (read in place) or as separate allocations (gathered into the plan). betas, gammas:
+ * [batch][num_challenges]. d_out (device): [batch][num_challenges * (1 + num_partial_products)][2^degree_bits] values, dense, so
+ * qpgpu_oracle_commit_batch(QPGPU_ORACLE_DEVICE_INPUT) with polys[b] = d_out + b * cols * n uses them in place. */
+int qpgpu_stage_partial_products_batch(qpgpu_stage_plan *plan, const uint64_t *const *wires, uint32_t batch, int wires_on_device,
+                                       const uint64_t *betas, const uint64_t *gammas, uint64_t *d_out);
+/* s6 for a batch: both oracles must hold exactly `batch` proofs (QPGPU_EINVAL naming the argument otherwise). betas, gammas,
+ * alphas: [batch][num_challenges]; public_inputs_hashes: [batch][4]. d_out (device): [batch][num_challenges *
+ * quotient_degree_factor][2^degree_bits] coefficients, dense. The witness check is part of the call, with the semantics of
+ * qpgpu_prove_batch_dev: QPGPU_EUNSAT concerns the whole batch, and the message names the proof ("(proof b of the batch)").
+ * After any error the workspace has been overwritten and the plan stays usable. */
+int qpgpu_stage_quotient_batch(qpgpu_stage_plan *plan, const qpgpu_oracle *wires_oracle, const qpgpu_oracle *zs_pp_oracle, uint32_t batch,
+                               const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
+                               const uint64_t *public_inputs_hashes, uint64_t *d_out);
 
 /* ---- proving pool: several proofs of one circuit in flight on one GPU ------------------------------------------
  * The native counterpart of the reference's dedicated proving worker (wormhole/aggregator/src/aggregator.rs:14-43):

@@ -112,6 +112,32 @@ extern "C" {
     pub fn qpgpu_fri_open(s: *mut QpgpuFriSession, indices: *const u64, n: usize, out: *mut u8, out_cap: usize, out_len: *mut usize) -> i32;
     pub fn qpgpu_fri_session_free(s: *mut QpgpuFriSession);
     pub fn qpgpu_fri_grind(ctx: *mut QpgpuCtx, c: *const QpgpuChallenger, proof_of_work_bits: u32, nonce_out: *mut u64) -> i32;
+    // include/qpgpu.h — the stage route for a lockstep batch: one call per stage for `batch` proofs of one circuit (a level of
+    // leaves), `batch` transcripts kept in Rust; arrays are [batch][..], proof b first ("a level of
+    // leaves"). An oracle made by qpgpu_oracle_commit_batch holds all the proofs' columns; the constants/sigmas oracle holds one proof
+    // and is shared. `Oracle::{eval_batch, open_batch}`, `FriSession::begin_batch` and `fri_grind_batch` below wrap these.
+    pub fn qpgpu_oracle_commit_batch(ctx: *mut QpgpuCtx, polys: *const *const u64, batch: u32, num_polys: u32, degree_bits: u32, rate_bits: u32,
+                                     cap_height: u32, flags: u32, blinding_seed: u64, blinding_stream: u32, out: *mut *mut QpgpuOracle) -> i32;
+    pub fn qpgpu_oracle_batch(o: *const QpgpuOracle) -> u32;
+    pub fn qpgpu_oracle_strides(o: *const QpgpuOracle, coeffs: *mut u64, lde: *mut u64, digests: *mut u64) -> i32;
+    pub fn qpgpu_oracle_eval_batch(o: *mut QpgpuOracle, points: *const u64, first: u32, count: u32, out: *mut u64) -> i32;
+    pub fn qpgpu_oracle_open_batch(o: *mut QpgpuOracle, indices: *const u64, n: usize, rows_out: *mut u64, paths_out: *mut u64) -> i32;
+    pub fn qpgpu_stage_plan_create_batch(ctx: *mut QpgpuCtx, words: *const u64, n_words: usize, cs_oracle: *const QpgpuOracle, max_batch: u32,
+                                         out: *mut *mut QpgpuStagePlan, err: *mut c_char) -> i32;
+    pub fn qpgpu_stage_plan_max_batch(plan: *const QpgpuStagePlan) -> u32;
+    pub fn qpgpu_stage_partial_products_batch(plan: *mut QpgpuStagePlan, wires: *const *const u64, batch: u32, wires_on_device: i32,
+                                              betas: *const u64, gammas: *const u64, d_out: *mut u64) -> i32;
+    pub fn qpgpu_stage_quotient_batch(plan: *mut QpgpuStagePlan, wires_oracle: *const QpgpuOracle, zs_pp_oracle: *const QpgpuOracle, batch: u32,
+                                      betas: *const u64, gammas: *const u64, alphas: *const u64, public_inputs_hashes: *const u64,
+                                      d_out: *mut u64) -> i32;
+    pub fn qpgpu_fri_prove_batch(ctx: *mut QpgpuCtx, oracles: *const *mut QpgpuOracle, n: u32, batches: *const QpgpuFriBatch, n_batches: u32,
+                                 points: *const u64, batch: u32, params: *const QpgpuFriParams, challengers: *mut QpgpuChallenger,
+                                 outs: *const *mut u8, out_cap: usize, out_lens: *mut usize) -> i32;
+    pub fn qpgpu_fri_begin_batch(ctx: *mut QpgpuCtx, oracles: *const *mut QpgpuOracle, n: u32, batches: *const QpgpuFriBatch, n_batches: u32,
+                                 points: *const u64, batch: u32, params: *const QpgpuFriParams, alphas: *const u64,
+                                 out: *mut *mut QpgpuFriSession) -> i32;
+    pub fn qpgpu_fri_session_batch(s: *const QpgpuFriSession) -> u32;
+    pub fn qpgpu_fri_grind_batch(ctx: *mut QpgpuCtx, cs: *const QpgpuChallenger, batch: u32, proof_of_work_bits: u32, nonces_out: *mut u64) -> i32;
     pub fn qpgpu_circuit_constants_sigmas_cap(c: *const QpgpuCircuit, out: *mut u64, out_words: usize) -> i32;
     // include/qpgpu_verify.h — host-side verification of the bytes the GPU produced (debug self-check; production keeps
     // plonky2's own `VerifierCircuitData::verify`, which is what consumers of the proof run anyway)
@@ -619,9 +645,27 @@ impl Oracle {
         if unsafe { qpgpu_oracle_open(self.raw, indices.as_ptr(), indices.len(), rows.as_mut_ptr(), paths.as_mut_ptr()) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
         Ok((rows, paths))
     }
+    /// proofs the oracle holds (qpgpu_oracle_commit_batch); 1 for qpgpu_oracle_commit's
+    pub fn batch(&self) -> usize { unsafe { qpgpu_oracle_batch(self.raw) as usize } }
+    /// proof b's polynomials [first, first + count) at points[b]: batch x count word pairs, one launch for the whole batch
+    pub fn eval_batch(&self, points: &[[u64; 2]], first: u32, count: u32) -> Result<Vec<u64>> {
+        if points.len() != self.batch() { bail!("eval_batch: one point per proof of the oracle") }
+        let mut out = vec![0u64; points.len() * count as usize * 2];
+        if unsafe { qpgpu_oracle_eval_batch(self.raw, points.as_ptr() as *const u64, first, count, out.as_mut_ptr()) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
+        Ok(out)
+    }
+    /// `open` for every proof: indices [batch][n], each proof its own; (rows [batch][n][leaf_width], paths [batch][n][path_len][4])
+    pub fn open_batch(&self, indices: &[u64]) -> Result<(Vec<u64>, Vec<u64>)> {
+        let (batch, width) = (self.batch(), unsafe { qpgpu_oracle_leaf_width(self.raw) });
+        if indices.len() % batch != 0 { bail!("open_batch: the same number of indices for every proof") }
+        let (mut rows, mut paths) = (vec![0u64; indices.len() * width], vec![0u64; indices.len() * self.path_len * 4]);
+        if unsafe { qpgpu_oracle_open_batch(self.raw, indices.as_ptr(), indices.len() / batch, rows.as_mut_ptr(), paths.as_mut_ptr()) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
+        Ok((rows, paths))
+    }
 }
 
-pub struct FriSession { ctx: *mut QpgpuCtx, raw: *mut QpgpuFriSession, cap_words: usize, final_words: usize }
+/// cap_words and final_words are the session's totals: `batch` proofs back to back for a session made by begin_batch
+pub struct FriSession { ctx: *mut QpgpuCtx, raw: *mut QpgpuFriSession, cap_words: usize, final_words: usize, batch: usize }
 
 impl FriSession {
     /// degree_bits: of the oracles. The oracles must outlive the session.
@@ -632,7 +676,29 @@ impl FriSession {
             bail!("{}", last_error(ctx))
         }
         let folded: u32 = params.reduction_arity_bits[..params.num_reduction_rounds as usize].iter().sum();
-        Ok(Self { ctx, raw, cap_words: 4usize << params.cap_height, final_words: 2usize << (degree_bits - folded) })
+        Ok(Self { ctx, raw, cap_words: 4usize << params.cap_height, final_words: 2usize << (degree_bits - folded), batch: 1 })
+    }
+    /// A lockstep batch: points[k][b] is proof b's point of opening batch k (the `point` fields of `batches` are not read), alphas one
+    /// per proof. round_commit then returns the proofs' caps back to back, round_fold_batch takes one beta per proof, final_poly
+    /// returns the proofs' coefficients back to back, open takes [batch][n] indices and returns [batch][n] query rounds.
+    pub fn begin_batch(ctx: *mut QpgpuCtx, oracles: &[*mut QpgpuOracle], batches: &[QpgpuFriBatch], points: &[Vec<[u64; 2]>],
+                       params: &QpgpuFriParams, degree_bits: u32, alphas: &[[u64; 2]]) -> Result<Self> {
+        let batch = alphas.len();
+        if points.len() != batches.len() || points.iter().any(|p| p.len() != batch) { bail!("begin_batch: one point per opening batch and proof") }
+        let flat: Vec<u64> = points.iter().flatten().flatten().copied().collect();
+        let mut raw: *mut QpgpuFriSession = core::ptr::null_mut();
+        if unsafe { qpgpu_fri_begin_batch(ctx, oracles.as_ptr(), oracles.len() as u32, batches.as_ptr(), batches.len() as u32, flat.as_ptr(), batch as u32,
+                                          params, alphas.as_ptr() as *const u64, &mut raw) } != QPGPU_OK {
+            bail!("{}", last_error(ctx))
+        }
+        let folded: u32 = params.reduction_arity_bits[..params.num_reduction_rounds as usize].iter().sum();
+        Ok(Self { ctx, raw, cap_words: batch * (4usize << params.cap_height), final_words: batch * (2usize << (degree_bits - folded)), batch })
+    }
+    pub fn batch(&self) -> usize { self.batch }
+    pub fn round_fold_batch(&mut self, betas: &[[u64; 2]]) -> Result<()> {
+        if betas.len() != self.batch { bail!("round_fold_batch: one beta per proof") }
+        if unsafe { qpgpu_fri_round_fold(self.raw, betas.as_ptr() as *const u64) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
+        Ok(())
     }
     pub fn round_commit(&mut self) -> Result<Vec<u64>> {
         let mut cap = vec![0u64; self.cap_words];
@@ -640,6 +706,7 @@ impl FriSession {
         Ok(cap)
     }
     pub fn round_fold(&mut self, beta: [u64; 2]) -> Result<()> {
+        if self.batch != 1 { bail!("round_fold: a session of {} proofs takes round_fold_batch", self.batch) }
         if unsafe { qpgpu_fri_round_fold(self.raw, beta.as_ptr()) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
         Ok(())
     }
@@ -651,8 +718,9 @@ impl FriSession {
     }
     /// the FriQueryRound bytes of each index, back to back
     pub fn open(&mut self, indices: &[u64]) -> Result<Vec<u8>> {
+        if indices.len() % self.batch != 0 { bail!("open: the same number of indices for every proof") }
         let (mut out, mut len) = (vec![0u8; indices.len() * unsafe { qpgpu_fri_query_size(self.raw) }], 0usize);
-        if unsafe { qpgpu_fri_open(self.raw, indices.as_ptr(), indices.len(), out.as_mut_ptr(), out.len(), &mut len) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
+        if unsafe { qpgpu_fri_open(self.raw, indices.as_ptr(), indices.len() / self.batch, out.as_mut_ptr(), out.len(), &mut len) } != QPGPU_OK { bail!("{}", last_error(self.ctx)) }
         out.truncate(len);
         Ok(out)
     }
@@ -666,3 +734,41 @@ pub fn fri_grind(ctx: *mut QpgpuCtx, challenger: &QpgpuChallenger, proof_of_work
     if unsafe { qpgpu_fri_grind(ctx, challenger, proof_of_work_bits, &mut nonce) } != QPGPU_OK { bail!("{}", last_error(ctx)) }
     Ok(nonce)
 }
+
+/// fri_grind for the transcripts of a lockstep batch in one search; none is advanced
+pub fn fri_grind_batch(ctx: *mut QpgpuCtx, challengers: &[QpgpuChallenger], proof_of_work_bits: u32) -> Result<Vec<u64>> {
+    let mut nonces = vec![0u64; challengers.len()];
+    if unsafe { qpgpu_fri_grind_batch(ctx, challengers.as_ptr(), challengers.len() as u32, proof_of_work_bits, nonces.as_mut_ptr()) } != QPGPU_OK { bail!("{}", last_error(ctx)) }
+    Ok(nonces)
+}
+
+/// A stage plan for up to max_batch proofs in lockstep (qpgpu_stage_plan_create_batch); `cs_oracle` holds one proof and must outlive it
+pub struct StagePlan { pub ctx: *mut QpgpuCtx, pub raw: *mut QpgpuStagePlan }
+
+impl StagePlan {
+    pub fn create_batch(ctx: *mut QpgpuCtx, words: &[u64], cs_oracle: *const QpgpuOracle, max_batch: u32) -> Result<Self> {
+        let (mut raw, mut err) = (core::ptr::null_mut(), [0 as c_char; 256]);
+        if unsafe { qpgpu_stage_plan_create_batch(ctx, words.as_ptr(), words.len(), cs_oracle, max_batch, &mut raw, err.as_mut_ptr()) } != QPGPU_OK {
+            bail!("{}", unsafe { std::ffi::CStr::from_ptr(err.as_ptr()) }.to_string_lossy())
+        }
+        Ok(Self { ctx, raw })
+    }
+    pub fn max_batch(&self) -> u32 { unsafe { qpgpu_stage_plan_max_batch(self.raw) } }
+    /// s5 for wires.len() witnesses (device pointers when on_device): d_out receives [batch][nch * (1 + npp)][n] values
+    pub fn partial_products_batch(&mut self, wires: &[*const u64], on_device: bool, betas: &[u64], gammas: &[u64], d_out: *mut u64) -> Result<()> {
+        if unsafe { qpgpu_stage_partial_products_batch(self.raw, wires.as_ptr(), wires.len() as u32, on_device as i32, betas.as_ptr(), gammas.as_ptr(), d_out) } != QPGPU_OK {
+            bail!("{}", last_error(self.ctx))
+        }
+        Ok(())
+    }
+    /// s6 for `batch` proofs: d_out receives [batch][nch * qdf][n] coefficients; an unsatisfied witness fails the whole batch and the message names the proof
+    pub fn quotient_batch(&mut self, wires: &Oracle, zs_pp: &Oracle, batch: u32, betas: &[u64], gammas: &[u64], alphas: &[u64], pi_hashes: &[u64],
+                          d_out: *mut u64) -> Result<()> {
+        if unsafe { qpgpu_stage_quotient_batch(self.raw, wires.raw, zs_pp.raw, batch, betas.as_ptr(), gammas.as_ptr(), alphas.as_ptr(), pi_hashes.as_ptr(), d_out) } != QPGPU_OK {
+            bail!("{}", last_error(self.ctx))
+        }
+        Ok(())
+    }
+}
+
+impl Drop for StagePlan { fn drop(&mut self) { unsafe { qpgpu_stage_plan_free(self.raw) } } }

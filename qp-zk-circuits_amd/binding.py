@@ -170,6 +170,22 @@ def load_library():
         "qpgpu_fri_open": (c.c_int, [vp, u64p, c.c_size_t, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "qpgpu_fri_session_free": (None, [vp]),
         "qpgpu_fri_grind": (c.c_int, [vp, vp, c.c_uint, c.POINTER(c.c_uint64)]),
+        # lockstep batches of the stage flow
+        "qpgpu_oracle_commit_batch": (c.c_int, [vp, c.POINTER(vp), c.c_uint32, c.c_uint32, c.c_uint, c.c_uint, c.c_uint, c.c_uint,
+                                                c.c_uint64, c.c_uint32, c.POINTER(vp)]),
+        "qpgpu_oracle_batch": (c.c_uint32, [vp]),
+        "qpgpu_oracle_strides": (c.c_int, [vp, c.POINTER(c.c_uint64), c.POINTER(c.c_uint64), c.POINTER(c.c_uint64)]),
+        "qpgpu_oracle_eval_batch": (c.c_int, [vp, u64p, c.c_uint32, c.c_uint32, u64p]),
+        "qpgpu_oracle_open_batch": (c.c_int, [vp, u64p, c.c_size_t, u64p, u64p]),
+        "qpgpu_stage_plan_create_batch": (c.c_int, [vp, u64p, c.c_size_t, vp, c.c_uint32, c.POINTER(vp), c.c_char_p]),
+        "qpgpu_stage_plan_max_batch": (c.c_uint32, [vp]),
+        "qpgpu_stage_partial_products_batch": (c.c_int, [vp, c.POINTER(vp), c.c_uint32, c.c_int, u64p, u64p, u64p]),
+        "qpgpu_stage_quotient_batch": (c.c_int, [vp, vp, vp, c.c_uint32, u64p, u64p, u64p, u64p, u64p]),
+        "qpgpu_fri_prove_batch": (c.c_int, [vp, c.POINTER(vp), c.c_uint32, vp, c.c_uint32, u64p, c.c_uint32, vp, vp, c.POINTER(vp),
+                                            c.c_size_t, c.POINTER(c.c_size_t)]),
+        "qpgpu_fri_begin_batch": (c.c_int, [vp, c.POINTER(vp), c.c_uint32, vp, c.c_uint32, u64p, c.c_uint32, vp, u64p, c.POINTER(vp)]),
+        "qpgpu_fri_session_batch": (c.c_uint32, [vp]),
+        "qpgpu_fri_grind_batch": (c.c_int, [vp, vp, c.c_uint32, c.c_uint, c.POINTER(c.c_uint64)]),
         "qpgpu_field_probe": (c.c_int, [vp, c.c_uint, c.c_uint, u64p, u64p, c.c_size_t, u64p, c.c_size_t, c.c_int]),
         "qpgpu_synth_pack_words": (c.c_size_t, [c.c_uint, c.c_uint, c.c_uint]),
         "qpgpu_synth_pack_words_ex": (c.c_size_t, [c.c_uint, c.c_uint, c.c_uint, c.c_uint]),
@@ -778,6 +794,43 @@ class PolyOracle:
         gpu._check(gpu.lib.qpgpu_oracle_commit(gpu.ctx, ptr, num_polys, self.degree_bits, rate_bits, cap_height, flags,
                                                blinding_seed, blinding_stream, ctypes.byref(h)))
         self.h = h
+        self.batch = None           # set by commit_batch: the oracle then answers through the batch entries
+
+    @classmethod
+    def commit_batch(cls, gpu, polys, rate_bits=3, cap_height=4, coeffs=False, blinding=False, blinding_seed=0, blinding_stream=0):
+        """qpgpu_oracle_commit_batch: one oracle over the matrices of `batch` proofs. polys: a list of numpy arrays [num_polys, n]
+        (or one array [batch, num_polys, n]), or a list of (device pointer, num_polys, n), back to back or separate allocations.
+        With blinding, proof b's key is derived from blinding_seed + b (seed 0: fresh keys). cap / eval / open then take and return
+        [batch, ...] arrays."""
+        self = cls.__new__(cls)
+        self.gpu = gpu
+        if isinstance(polys, np.ndarray) or isinstance(polys[0], np.ndarray):
+            keep = [np.ascontiguousarray(a, dtype=np.uint64) for a in polys]
+            num_polys, n = keep[0].shape
+            assert all(a.shape == (num_polys, n) for a in keep)
+            ptrs, flags = [a.ctypes.data for a in keep], 0
+        else:
+            num_polys, n = polys[0][1], polys[0][2]
+            assert all((q[1], q[2]) == (num_polys, n) for q in polys)
+            ptrs, flags = [_ptr(q[0]) for q in polys], ORACLE_DEVICE_INPUT
+        self.num_polys, self.n, self.batch = num_polys, n, len(ptrs)
+        self.degree_bits, self.rate_bits, self.cap_height = n.bit_length() - 1, rate_bits, cap_height
+        assert 1 << self.degree_bits == n
+        flags |= (ORACLE_COEFFS if coeffs else ORACLE_VALUES) | (ORACLE_BLINDING if blinding else 0)
+        h = ctypes.c_void_p()
+        arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
+        self.h = None
+        gpu._check(gpu.lib.qpgpu_oracle_commit_batch(gpu.ctx, arr, len(ptrs), num_polys, self.degree_bits, rate_bits, cap_height, flags,
+                                                     blinding_seed, blinding_stream, ctypes.byref(h)))
+        self.h = h
+        assert int(gpu.lib.qpgpu_oracle_batch(h)) == self.batch
+        return self
+
+    def strides(self):
+        """Words between two proofs' (coefficients, LDEs, digests); (0, 0, 0) for an oracle of one proof."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        self.gpu._check(self.gpu.lib.qpgpu_oracle_strides(self.h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
 
     def close(self):
         if self.h:
@@ -785,6 +838,10 @@ class PolyOracle:
             self.h = None
 
     def cap(self):
+        if self.batch is not None:
+            out = np.empty((self.batch, 4 << self.cap_height), dtype=np.uint64)
+            self.gpu._check(self.gpu.lib.qpgpu_oracle_cap(self.h, out.ctypes.data, out.size))
+            return out
         out = np.empty((1 << self.cap_height, 4), dtype=np.uint64)
         self.gpu._check(self.gpu.lib.qpgpu_oracle_cap(self.h, out.ctypes.data, out.size))
         return out
@@ -792,6 +849,11 @@ class PolyOracle:
     def eval(self, point, first=0, count=None):
         """Evaluations at an extension point (a, b): array [count, 2]."""
         count = self.num_polys - first if count is None else count
+        if self.batch is not None:              # points [batch, 2] -> [batch, count, 2]
+            pt = np.ascontiguousarray(np.array(point, dtype=np.uint64).reshape(self.batch, 2))
+            out = np.empty((self.batch, count, 2), dtype=np.uint64)
+            self.gpu._check(self.gpu.lib.qpgpu_oracle_eval_batch(self.h, pt.ctypes.data, first, count, out.ctypes.data))
+            return out
         pt = np.array(point, dtype=np.uint64)
         out = np.empty((count, 2), dtype=np.uint64)
         self.gpu._check(self.gpu.lib.qpgpu_oracle_eval(self.h, pt.ctypes.data, first, count, out.ctypes.data))
@@ -811,8 +873,16 @@ class PolyOracle:
     def open(self, indices, rows=True, paths=True):
         """MerkleTree::prove at leaf indices: (rows [n, leaf_width], paths [n, degree_bits + rate_bits - cap_height, 4]); an
         output that is not asked for comes back as None."""
-        idx = np.ascontiguousarray(indices, dtype=np.uint64).ravel()
         plen = self.degree_bits + self.rate_bits - self.cap_height
+        if self.batch is not None:              # indices [batch, n] -> rows [batch, n, leaf_width], paths [batch, n, plen, 4]
+            idx = np.ascontiguousarray(np.array(indices, dtype=np.uint64).reshape(self.batch, -1))
+            n = idx.shape[1]
+            r = np.zeros((self.batch, n, self.leaf_width), dtype=np.uint64) if rows else None
+            p = np.zeros((self.batch, n, plen, 4), dtype=np.uint64) if paths else None
+            self.gpu._check(self.gpu.lib.qpgpu_oracle_open_batch(self.h, idx.ctypes.data if n else None, n,
+                                                                 r.ctypes.data if rows else None, p.ctypes.data if paths else None))
+            return r, p
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).ravel()
         r = np.empty((idx.size, self.leaf_width), dtype=np.uint64) if rows else None
         p = np.empty((idx.size, plen, 4), dtype=np.uint64) if paths else None
         self.gpu._check(self.gpu.lib.qpgpu_oracle_open(self.h, idx.ctypes.data if idx.size else None, idx.size,
@@ -838,16 +908,22 @@ class StagePlan:
     pack_words: the full pack or stage_header_words(pack); cs_oracle: the PolyOracle of the constants/sigmas values (no
     blinding), which must stay open as long as the plan."""
 
-    def __init__(self, gpu, pack_words, cs_oracle):
+    def __init__(self, gpu, pack_words, cs_oracle, max_batch=None):
+        """max_batch: None = qpgpu_stage_plan_create (one proof); a number = qpgpu_stage_plan_create_batch, a workspace for that
+        many proofs in lockstep (partial_products_batch, quotient_batch)."""
         self.gpu, self.cs_oracle = gpu, cs_oracle
         pw = np.ascontiguousarray(pack_words, dtype=np.uint64)
         h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(STAGE_ERR_CAP)
-        rc = gpu.lib.qpgpu_stage_plan_create(gpu.ctx, pw.ctypes.data, pw.size, cs_oracle.h if cs_oracle is not None else None,
-                                             ctypes.byref(h), err)
+        cs = cs_oracle.h if cs_oracle is not None else None
+        if max_batch is None:
+            rc = gpu.lib.qpgpu_stage_plan_create(gpu.ctx, pw.ctypes.data, pw.size, cs, ctypes.byref(h), err)
+        else:
+            rc = gpu.lib.qpgpu_stage_plan_create_batch(gpu.ctx, pw.ctypes.data, pw.size, cs, max_batch, ctypes.byref(h), err)
         if rc != 0:
             raise QpGpuError(rc, err.value.decode())
         self.h = h
+        self.max_batch = int(gpu.lib.qpgpu_stage_plan_max_batch(h))
         v = [ctypes.c_uint() for _ in range(4)]
         fused = ctypes.c_int()
         gpu._check(gpu.lib.qpgpu_stage_plan_info(h, *[ctypes.byref(x) for x in v], ctypes.byref(fused)))
@@ -899,11 +975,50 @@ class StagePlan:
         return out
 
 
+    def _challenges_batch(self, xs, batch, width=None):
+        a = np.ascontiguousarray(xs, dtype=np.uint64)
+        assert a.size == batch * (self.num_challenges if width is None else width)
+        return a
+
+    def partial_products_batch(self, wires, betas, gammas):
+        """s5 for a lockstep batch. wires: a list of numpy arrays [num_wires, n] (host) or of DeviceBuffers / device pointers (back
+        to back or separate). betas, gammas: [batch, num_challenges]. Returns a DeviceBuffer [batch][num_zs_pp][n], dense."""
+        batch = len(wires)
+        b, g = self._challenges_batch(betas, batch), self._challenges_batch(gammas, batch)
+        if isinstance(wires[0], np.ndarray):
+            keep = [np.ascontiguousarray(w, dtype=np.uint64) for w in wires]
+            ptrs, on_dev = [w.ctypes.data for w in keep], 0
+        else:
+            ptrs, on_dev = [_ptr(w) for w in wires], 1
+        arr = (ctypes.c_void_p * batch)(*ptrs)
+        out = self.gpu.alloc(batch * self.num_zs_pp * self.n * 8)
+        rc = self.gpu.lib.qpgpu_stage_partial_products_batch(self.h, arr, batch, on_dev, b.ctypes.data, g.ctypes.data, out.ptr)
+        if rc != 0:
+            out.free(scrub=True)
+            self.gpu._check(rc)
+        return out
+
+    def quotient_batch(self, wires_oracle, zs_pp_oracle, batch, betas, gammas, alphas, public_inputs_hashes):
+        """s6 for a lockstep batch: the two oracles hold `batch` proofs each (PolyOracle.commit_batch). betas, gammas, alphas:
+        [batch, num_challenges]; public_inputs_hashes [batch, 4]. Returns a DeviceBuffer [batch][num_quotient][n] of coefficients.
+        QpGpuError -4 concerns the whole batch; the message names the proof."""
+        b, g, a = (self._challenges_batch(x, batch) for x in (betas, gammas, alphas))
+        pih = self._challenges_batch(public_inputs_hashes, batch, 4)
+        out = self.gpu.alloc(batch * self.num_quotient * self.n * 8)
+        rc = self.gpu.lib.qpgpu_stage_quotient_batch(self.h, wires_oracle.h, zs_pp_oracle.h, batch, b.ctypes.data, g.ctypes.data,
+                                                     a.ctypes.data, pih.ctypes.data, out.ptr)
+        if rc != 0:
+            out.free(scrub=True)
+            self.gpu._check(rc)
+        return out
+
+
 def _fri_args(oracles, batches, reduction_arity_bits, rate_bits, cap_height, proof_of_work_bits, num_query_rounds):
     hs = (ctypes.c_void_p * len(oracles))(*[o.h for o in oracles])
     bs = (_FriBatch * len(batches))()
     for b, (point, ranges) in zip(bs, batches):
-        b.point[0], b.point[1] = int(point[0]), int(point[1])
+        if np.ndim(point) == 1:     # the batch entries do not read this field: their points travel in an array of their own
+            b.point[0], b.point[1] = int(point[0]), int(point[1])
         b.num_ranges = len(ranges)
         for r, (o, f, cnt) in zip(b.ranges, ranges):
             r.oracle, r.first, r.count = o, f, cnt
@@ -928,6 +1043,41 @@ def fri_prove(gpu, oracles, batches, challenger, reduction_arity_bits, rate_bits
     return out[:ln.value].tobytes()
 
 
+def fri_prove_batch(gpu, oracles, batches, challengers, reduction_arity_bits, rate_bits=3, cap_height=4, proof_of_work_bits=16,
+                    num_query_rounds=28):
+    """qpgpu_fri_prove_batch: fri_prove for len(challengers) proofs in lockstep. oracles hold that many proofs (PolyOracle.commit_batch)
+    or one shared by all; batches: [(points [batch, 2], ranges), ...]; the challengers are advanced in place. Returns a list of
+    FriProof bytes."""
+    nb = len(challengers)
+    hs, bs, prm = _fri_args(oracles, batches, reduction_arity_bits, rate_bits, cap_height, proof_of_work_bits, num_query_rounds)
+    pts = np.ascontiguousarray(np.array([np.array(pt, dtype=np.uint64).reshape(nb, 2) for pt, _ in batches], dtype=np.uint64))
+    size = gpu.lib.qpgpu_fri_proof_size(hs, len(oracles), ctypes.byref(prm))
+    if size == 0:
+        raise QpGpuError(-1, "fri_prove: bad oracles or FRI parameters")
+    states = (ChallengerState * nb)()
+    for i, ch in enumerate(challengers):
+        ctypes.memmove(ctypes.byref(states[i]), ctypes.byref(ch.state), ctypes.sizeof(ChallengerState))
+    outs = [np.empty(size, dtype=np.uint8) for _ in range(nb)]
+    optr = (ctypes.c_void_p * nb)(*[o.ctypes.data for o in outs])
+    lens = (ctypes.c_size_t * nb)()
+    gpu._check(gpu.lib.qpgpu_fri_prove_batch(gpu.ctx, hs, len(oracles), ctypes.byref(bs), len(batches), pts.ctypes.data, nb,
+                                             ctypes.byref(prm), ctypes.byref(states), optr, size, lens))
+    for i, ch in enumerate(challengers):
+        ctypes.memmove(ctypes.byref(ch.state), ctypes.byref(states[i]), ctypes.sizeof(ChallengerState))
+    return [outs[i][:lens[i]].tobytes() for i in range(nb)]
+
+
+def fri_grind_batch(gpu, challengers, proof_of_work_bits):
+    """qpgpu_fri_grind_batch: the minimum nonces of len(challengers) transcripts in one search; none is advanced."""
+    nb = len(challengers)
+    states = (ChallengerState * nb)()
+    for i, ch in enumerate(challengers):
+        ctypes.memmove(ctypes.byref(states[i]), ctypes.byref(ch.state), ctypes.sizeof(ChallengerState))
+    nonces = (ctypes.c_uint64 * nb)()
+    gpu._check(gpu.lib.qpgpu_fri_grind_batch(gpu.ctx, ctypes.byref(states), nb, proof_of_work_bits, nonces))
+    return [int(x) for x in nonces]
+
+
 def fri_grind(gpu, challenger, proof_of_work_bits):
     """The minimum proof-of-work nonce for a transcript in `challenger`'s state (qpgpu_fri_grind); the challenger is not advanced."""
     nonce = ctypes.c_uint64()
@@ -946,13 +1096,23 @@ class FriSession:
             nonce = fri_grind(gpu, ch, pow_bits); ch.observe([nonce]); ch.get()
             queries = fs.open([ch.get() % fs.lde_size for _ in range(num_query_rounds)])"""
 
-    def __init__(self, gpu, oracles, batches, alpha, reduction_arity_bits, rate_bits=3, cap_height=4):
-        self.gpu, self.oracles = gpu, list(oracles)
+    def __init__(self, gpu, oracles, batches, alpha, reduction_arity_bits, rate_bits=3, cap_height=4, batch=None):
+        """batch: None = qpgpu_fri_begin. A number = qpgpu_fri_begin_batch, that many proofs in lockstep: alpha is [batch, 2], each
+        opening batch's point [batch, 2]; round_commit returns [batch, cap_words], round_fold takes [batch, 2], final_poly returns
+        [batch, final_len, 2], open takes [batch, n] indices and returns a list of bytes, one per proof."""
+        self.gpu, self.oracles, self.batch = gpu, list(oracles), batch
         hs, bs, prm = _fri_args(oracles, batches, reduction_arity_bits, rate_bits, cap_height, 0, 0)
-        a = np.array([int(alpha[0]), int(alpha[1])], dtype=np.uint64)
         h = ctypes.c_void_p()
-        gpu._check(gpu.lib.qpgpu_fri_begin(gpu.ctx, hs, len(oracles), ctypes.byref(bs), len(batches), ctypes.byref(prm), a.ctypes.data,
-                                           ctypes.byref(h)))
+        if batch is None:
+            a = np.array([int(alpha[0]), int(alpha[1])], dtype=np.uint64)
+            gpu._check(gpu.lib.qpgpu_fri_begin(gpu.ctx, hs, len(oracles), ctypes.byref(bs), len(batches), ctypes.byref(prm), a.ctypes.data,
+                                               ctypes.byref(h)))
+        else:
+            a = np.ascontiguousarray(np.array(alpha, dtype=np.uint64).reshape(batch, 2))
+            pts = np.ascontiguousarray(np.array([np.array(pt, dtype=np.uint64).reshape(batch, 2) for pt, _ in batches], dtype=np.uint64))
+            gpu._check(gpu.lib.qpgpu_fri_begin_batch(gpu.ctx, hs, len(oracles), ctypes.byref(bs), len(batches), pts.ctypes.data, batch,
+                                                     ctypes.byref(prm), a.ctypes.data, ctypes.byref(h)))
+            assert int(gpu.lib.qpgpu_fri_session_batch(h)) == batch
         self.h = h
         self.cap_height, self.arity_bits = cap_height, list(reduction_arity_bits)
         self.lde_size = 1 << (oracles[0].degree_bits + rate_bits)
@@ -972,17 +1132,18 @@ class FriSession:
 
     def round_commit(self):
         """Commit the current layer: its cap, [2^cap_height, 4]."""
-        cap = np.empty((1 << self.cap_height, 4), dtype=np.uint64)
+        shape = (1 << self.cap_height, 4) if self.batch is None else (self.batch, 4 << self.cap_height)
+        cap = np.empty(shape, dtype=np.uint64)
         self.gpu._check(self.gpu.lib.qpgpu_fri_round_commit(self.h, cap.ctypes.data, cap.size))
         return cap
 
     def round_fold(self, beta):
-        b = np.array([int(beta[0]), int(beta[1])], dtype=np.uint64)
+        b = np.ascontiguousarray(np.array(beta, dtype=np.uint64).reshape(self.batch or 1, 2))
         self.gpu._check(self.gpu.lib.qpgpu_fri_round_fold(self.h, b.ctypes.data))
 
     def final_poly(self):
         """The final polynomial's coefficients, [final_len, 2]."""
-        out = np.empty((self.final_len, 2), dtype=np.uint64)
+        out = np.empty((self.final_len, 2) if self.batch is None else (self.batch, self.final_len, 2), dtype=np.uint64)
         n = ctypes.c_size_t()
         self.gpu._check(self.gpu.lib.qpgpu_fri_final_poly(self.h, out.ctypes.data, out.size, ctypes.byref(n)))
         assert n.value == self.final_len
@@ -990,6 +1151,15 @@ class FriSession:
 
     def open(self, indices):
         """The FriQueryRound bytes of each index, back to back (query_size bytes each)."""
+        if self.batch is not None:
+            idx = np.ascontiguousarray(np.array(indices, dtype=np.uint64).reshape(self.batch, -1))
+            n, per = idx.shape[1], idx.shape[1] * self.query_size
+            out = np.empty(max(1, self.batch * per), dtype=np.uint8)
+            ln = ctypes.c_size_t()
+            self.gpu._check(self.gpu.lib.qpgpu_fri_open(self.h, idx.ctypes.data if n else None, n, out.ctypes.data, self.batch * per,
+                                                        ctypes.byref(ln)))
+            assert ln.value == self.batch * per
+            return [out[b * per:(b + 1) * per].tobytes() for b in range(self.batch)]
         idx = np.ascontiguousarray(indices, dtype=np.uint64).ravel()
         out = np.empty(max(1, idx.size * self.query_size), dtype=np.uint8)
         ln = ctypes.c_size_t()

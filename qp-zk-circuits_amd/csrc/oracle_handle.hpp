@@ -7,10 +7,10 @@
 struct qpgpu_oracle {
     qpgpu_ctx *ctx = nullptr;
     PolyOracle o;
-    gl::u64 *block = nullptr;     // one allocation: coeffs | lde | digests | salt | eval scratch | salt key
+    gl::u64 *block = nullptr;     // one allocation: coeffs | lde | digests | salt | eval scratch | salt keys, each [o.nb][...]
     size_t block_words = 0;
-    gl::e2 *d_point = nullptr, *d_eval = nullptr;
-    uint32_t *d_key = nullptr;
+    gl::e2 *d_point = nullptr, *d_eval = nullptr;   // [nb] opening points, [nb][ncols] evaluations
+    uint32_t *d_key = nullptr;                      // [nb][8]
 };
 
 // plonky2 never holds a full input buffer (a duplex runs when the eighth element arrives) nor more than eight outputs: a

@@ -1,7 +1,7 @@
 // prover_stages.hpp — stages s5 (partial products) and s6 (quotient) as launch sequences over plain device views, and the
 // witness-independent tables they read. Two callers: the all-in-one prover (prover.cpp, a lockstep batch on a circuit handle's
-// workspace) and the stage-level C ABI (stage_api.cpp, one proof on a stage plan's workspace, reading the caller's oracles in
-// place). One sequence, two callers: the two routes cannot drift apart in bytes.
+// workspace) and the stage-level C ABI (stage_api.cpp, one proof or a lockstep batch on a stage plan's workspace, reading the
+// caller's oracles in place). One sequence, two callers: the two routes cannot drift apart in bytes.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <functional>
