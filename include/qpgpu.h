@@ -182,6 +182,12 @@ int qpgpu_circuit_set_witness_check(qpgpu_circuit *c, int on);
  * the next proof of this circuit runs (either pointer may be NULL). */
 int qpgpu_circuit_set_quotient_fused(qpgpu_circuit *c, int on);
 int qpgpu_circuit_quotient_info(const qpgpu_circuit *c, int *fused_enabled, int *fused_selected);
+/* Quotient stage, hash gates: a circuit whose PoseidonGate and Poseidon2 gate sit on the same wires (the Poseidon2 layout
+ * carried over from PoseidonGate: the leaf circuit) gets both from one kernel that shares the wire pass and the S-boxes; any
+ * other circuit, and every circuit loaded under QPGPU_QUOTIENT_PAIR=0, one kernel per gate. Same proof bytes either way.
+ * enabled: the switch as read at load; selected: whether the one kernel is what the next proof of this circuit runs. A NULL
+ * argument is QPGPU_EINVAL. */
+int qpgpu_circuit_quotient_pair_info(const qpgpu_circuit *c, int *enabled, int *selected);
 size_t qpgpu_proof_size(const qpgpu_circuit *c);   /* bytes written by qpgpu_prove for this circuit */
 /*
  * prove(): wires = the full witness matrix (num_wires x 2^degree_bits, column-major, as

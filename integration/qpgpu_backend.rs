@@ -68,6 +68,7 @@ extern "C" {
     pub fn qpgpu_circuit_free(c: *mut QpgpuCircuit);
     pub fn qpgpu_circuit_scrub(c: *mut QpgpuCircuit) -> i32;
     pub fn qpgpu_circuit_set_witness_check(c: *mut QpgpuCircuit, on: i32) -> i32;
+    pub fn qpgpu_circuit_quotient_pair_info(c: *const QpgpuCircuit, enabled: *mut i32, selected: *mut i32) -> i32;   // introspection
     pub fn qpgpu_proof_size(c: *const QpgpuCircuit) -> usize;
     pub fn qpgpu_prove(c: *mut QpgpuCircuit, wires: *const u64, public_inputs: *const u64, out: *mut u8, out_cap: usize, out_len: *mut usize) -> i32;
     pub fn qpgpu_generate_witness_partial_dev(c: *mut QpgpuCircuit, cells: *const u64, values: *const u64, count: usize,

@@ -109,6 +109,7 @@ def load_library():
         "qpgpu_circuit_set_witness_check": (c.c_int, [vp, c.c_int]),
         "qpgpu_circuit_set_quotient_fused": (c.c_int, [vp, c.c_int]),
         "qpgpu_circuit_quotient_info": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_int)]),
+        "qpgpu_circuit_quotient_pair_info": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_int)]),
         "qpgpu_circuit_gate_rows": (c.c_int, [vp, c.c_uint, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "qpgpu_prove": (c.c_int, [vp, u64p, u64p, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "qpgpu_prove_dev": (c.c_int, [vp, u64p, u64p, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
@@ -534,6 +535,12 @@ class Circuit:
         """(the switch, whether the one-pass kernel is what the next proof of this circuit runs)."""
         a, b = ctypes.c_int(), ctypes.c_int()
         self.gpu._check(self.gpu.lib.qpgpu_circuit_quotient_info(self.h, ctypes.byref(a), ctypes.byref(b)))
+        return bool(a.value), bool(b.value)
+
+    def quotient_pair_info(self):
+        """(QPGPU_QUOTIENT_PAIR as read at load, whether one kernel serves both hash gates in the next proof of this circuit)."""
+        a, b = ctypes.c_int(), ctypes.c_int()
+        self.gpu._check(self.gpu.lib.qpgpu_circuit_quotient_pair_info(self.h, ctypes.byref(a), ctypes.byref(b)))
         return bool(a.value), bool(b.value)
 
     def set_blinding_seed(self, seed):

@@ -219,6 +219,13 @@ int qpgpu_circuit_quotient_info(const qpgpu_circuit *c, int *fused_enabled, int 
     return QPGPU_OK;
 }
 
+int qpgpu_circuit_quotient_pair_info(const qpgpu_circuit *c, int *enabled, int *selected) {
+    if (!c || !enabled || !selected) return QPGPU_EINVAL;
+    *enabled = c->tab.quotient_pair ? 1 : 0;
+    *selected = c->tab.pair_selected(c->pack) ? 1 : 0;
+    return QPGPU_OK;
+}
+
 int qpgpu_circuit_set_blinding_seed(qpgpu_circuit *c, uint64_t seed) {
     if (!c) return QPGPU_EINVAL;
     c->blinding_seed = seed; c->seed_set = true;

@@ -49,6 +49,10 @@ bool StageTables::fused_selected(const CircuitPack &p) const {
                                                      (uint32_t)p.quotient_degree_factor, (uint32_t)p.num_partial_products + 1, nullptr);
 }
 
+bool StageTables::pair_selected(const CircuitPack &p) const {
+    return quotient_pair && fold_words != 0 && pk_quotient_pairable(h_gates.data(), (uint32_t)h_gates.size(), p.p2_layout);
+}
+
 std::string stage_limits(const CircuitPack &p) {
     if (p.num_chunks() > 16 || p.num_challenges > 4) return "too many chunks/challenges";
     if (p.degree_bits + p.rate_bits > 23) return "LDE larger than 2^23 not supported";
@@ -120,6 +124,10 @@ int stage_tables_build(qpgpu_ctx *ctx, const CircuitPack &p, const StageAlloc &a
     // measurements.
     if (const char *e = getenv("QPGPU_QUOTIENT_FUSED")) if (*e == '0') t.quotient_fused = false;
     if (const char *e = getenv("QPGPU_QUOTIENT_XCD_MAP")) if (*e == '0') t.quotient_plain_map = true;
+    // A folded PoseidonGate and Poseidon2 gate on the same wires (qfold::pairable: the leaf circuit) share one launch, the target
+    // wires' S-boxes and the linear term. QPGPU_QUOTIENT_PAIR=0, read here and nowhere else, keeps one launch per gate: the A/B
+    // measurement and the parity test.
+    if (const char *e = getenv("QPGPU_QUOTIENT_PAIR")) if (*e == '0') t.quotient_pair = false;
     return QPGPU_OK;
 }
 
@@ -210,7 +218,7 @@ int stage_quotient(qpgpu_ctx *ctx, const CircuitPack &p, const StageTables &t, c
         ta.chunk = (uint32_t)p.quotient_degree_factor; ta.nchunks = nchunks; ta.sig0 = (uint32_t)sig0;
         ta.num_selectors = (uint32_t)p.num_selectors; ta.num_gates = (uint32_t)p.gates.size(); ta.nterms = (uint32_t)nterms;
         ta.batch = nb; ta.ps_wires = v.ps_check_wires; ta.ps_zs = 0; ta.ps_small = SW; ta.ps_acc = (u64)nch * n; ta.ps_out = (u64)nch * n;
-        ta.fold = w.d_fold; ta.ps_fold = t.fold_words;
+        ta.fold = w.d_fold; ta.ps_fold = t.fold_words; ta.pair = t.quotient_pair ? 1 : 0;
         QP_HIP(ctx, hipMemsetAsync(w.d_qacc, 0, (size_t)nb * nch * n * 8, st));
         std::vector<u64> init(2 * (size_t)nb);
         for (uint32_t b = 0; b < nb; b++) { init[2 * b] = ~0ull; init[2 * b + 1] = 0; }
@@ -233,7 +241,7 @@ int stage_quotient(qpgpu_ctx *ctx, const CircuitPack &p, const StageTables &t, c
     qa.num_routed = (uint32_t)R; qa.chunk = (uint32_t)p.quotient_degree_factor; qa.nchunks = nchunks; qa.sig0 = (uint32_t)sig0;
     qa.num_selectors = (uint32_t)p.num_selectors; qa.num_gates = (uint32_t)p.gates.size(); qa.nterms = (uint32_t)nterms;
     qa.batch = nb; qa.ps_wires = v.ps_wires_lde; qa.ps_zs = v.ps_zs_lde; qa.ps_small = SW; qa.ps_acc = (u64)nch * lde_n; qa.ps_out = (u64)nch * q_n;
-    qa.fused = t.quotient_fused ? 1 : 0; qa.fused_plain_map = t.quotient_plain_map ? 1 : 0;
+    qa.fused = t.quotient_fused ? 1 : 0; qa.fused_plain_map = t.quotient_plain_map ? 1 : 0; qa.pair = t.quotient_pair ? 1 : 0;
     QP_HIP(ctx, pk_quotient(qa, t.h_gates.data(), st));
     // coset_ifft(g) on the quotient domain: ifft then scale coefficient i by g^-i; the qdf*n coefficients of a challenge
     // are its qdf chunks of n, contiguous

@@ -30,7 +30,9 @@ struct StageTables {
     size_t fold_words = 0;               // words of the per-proof folded hash-gate weights (quotient_fold.hpp); 0: round by round
     bool quotient_fused = true;          // stage s6: quotient_perm_gates_kernel where the gate list allows it (QPGPU_QUOTIENT_FUSED)
     bool quotient_plain_map = false;     // QPGPU_QUOTIENT_XCD_MAP=0: that kernel's workgroups in proof-major order (measurement)
+    bool quotient_pair = true;           // stage s6: both folded hash gates from quotient_hash_pair_kernel where they pair (QPGPU_QUOTIENT_PAIR)
     bool fused_selected(const CircuitPack &p) const;
+    bool pair_selected(const CircuitPack &p) const;
 };
 
 // Per-proof workspace of s5 / s6: every buffer is [max_batch][one proof's size]

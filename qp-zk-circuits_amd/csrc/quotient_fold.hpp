@@ -54,7 +54,7 @@ constexpr u32 NO_SWAP = P2GateLayout::NO_SWAP;
 constexpr u32 T_HEAD = 0, T_OMEGA = 12, T_NALPHA = 130, T_KAPPA = 260, WORDS = 264;
 constexpr u32 MAX_GATES = 2;        // hash gates of one circuit that get a table (PoseidonGate, Poseidon2 gate)
 
-inline Schedule poseidon_schedule() {
+GL_HD Schedule poseidon_schedule() {
     Schedule s{};
     s.kind = GATE_POSEIDON; s.head = HEAD_SBOX; s.q0 = 5; s.nw = 106; s.nseg = 30;
     s.run_wire[0] = 29; s.run_len[0] = 36; s.run_wire[1] = 65; s.run_len[1] = 22; s.run_wire[2] = 87; s.run_len[2] = 48;
@@ -69,6 +69,18 @@ inline Schedule poseidon2_schedule(const P2GateLayout &lay) {
     s.nw = s.run_len[0] + 70; s.nseg = lay.first_round_wires ? 31 : 30;
     s.w_input = lay.w_input; s.w_output = lay.w_output; s.w_swap = lay.w_swap; s.w_delta = lay.w_delta;
     return s;
+}
+
+// Two hash gates whose sums one pass over the wires can form together (quotient_hash_pair_kernel): a PoseidonGate and a Poseidon2
+// gate, both with their first S-boxes computed from the inputs, on the same wires in the same constraint order. Then the swap and
+// delta constraints, the target wires with their S-boxes and the -alpha^q weights of targets and outputs (T_NALPHA) are the same
+// for both, and the Poseidon2 gate's layout is PoseidonGate's (poseidon_schedule is the only one that gate has); omega, kappa, the
+// twelve head S-boxes and the filter stay each gate's own. Anything else (no swap, round 0 on wires, one hash gate) is not a pair.
+GL_HD bool pairable(const Schedule &a, const Schedule &b) {
+    if (!((a.kind == GATE_POSEIDON && b.kind == GATE_POSEIDON2) || (a.kind == GATE_POSEIDON2 && b.kind == GATE_POSEIDON))) return false;
+    if (a.head != HEAD_SBOX || b.head != HEAD_SBOX || a.q0 != b.q0 || a.nw != b.nw) return false;
+    for (int r = 0; r < 3; r++) if (a.run_wire[r] != b.run_wire[r] || a.run_len[r] != b.run_len[r]) return false;
+    return a.w_input == b.w_input && a.w_output == b.w_output && a.w_swap == b.w_swap && a.w_delta == b.w_delta;
 }
 
 struct Consts { const u64 *rc; const poseidon2::Params *p2; };   // PoseidonGate's 360 round constants; the Poseidon2 gate's set
@@ -231,6 +243,28 @@ GL_HD u64 folded_sum(const Schedule &s, const Consts &c, const u64 *row, const u
     }
     for (int i = 0; i < 12; i++) sum = gl::add(sum, gl::mul(table[T_NALPHA + s.nw + i], row[s.w_output + i]));
     return gl::canon(sum);
+}
+
+// The filtered sums of a pairable pair of gates at one point in plain arithmetic: what quotient_hash_pair_kernel computes. The
+// linear part (swap and delta constraints, targets and outputs by -alpha^q) and every target wire's S-box are formed once and
+// serve both gates; T_NALPHA is read from gate a's table alone (equal in b's: both copy the same alpha powers). fa, fb: the filters.
+GL_HD u64 pair_sum(const Schedule &a, const Schedule &b, const Consts &c, const u64 *row, const u64 *ap, const u64 *ta, const u64 *tb, u64 fa, u64 fb) {
+    u64 lin = 0, oma = 0, omb = 0, st[12], h[12];
+    swapped_inputs(a, [&](u32 w) { return row[w]; }, [&](u32 q, u64 cst) { lin = gl::add(lin, gl::mul(ap[q], cst)); }, st);
+    for (int i = 0; i < 12; i++) h[i] = st[i];
+    head_inputs(a, c, h);
+    for (int i = 0; i < 12; i++) oma = gl::add(oma, gl::mul(ta[T_HEAD + i], poseidon::sbox7(h[i])));
+    head_inputs(b, c, st);
+    for (int i = 0; i < 12; i++) omb = gl::add(omb, gl::mul(tb[T_HEAD + i], poseidon::sbox7(st[i])));
+    for (u32 j = 0; j < a.nw; j++) {
+        const u64 v = row[target_wire(a, j)], y = poseidon::sbox7(v);
+        lin = gl::add(lin, gl::mul(ta[T_NALPHA + j], v));
+        oma = gl::add(oma, gl::mul(ta[T_OMEGA + j], y));
+        omb = gl::add(omb, gl::mul(tb[T_OMEGA + j], y));
+    }
+    for (int i = 0; i < 12; i++) lin = gl::add(lin, gl::mul(ta[T_NALPHA + a.nw + i], row[a.w_output + i]));
+    const u64 sa = gl::add(gl::add(oma, lin), ta[T_KAPPA]), sb = gl::add(gl::add(omb, lin), tb[T_KAPPA]);
+    return gl::canon(gl::add(gl::mul(fa, sa), gl::mul(fb, sb)));
 }
 
 #undef QFOLD_UNROLL

@@ -6,6 +6,8 @@
 //                                                         other gates are Constant, PublicInput, Arithmetic and BaseSum<2> only
 //   quotient_poseidon_kernel, quotient_poseidon2_kernel   the hash gates, linear layers folded into the alpha weights by
 //   quotient_fold_sweep_kernel                            (quotient_fold.hpp: Schedule, sweep)
+//   quotient_hash_pair_kernel                             both folded hash gates in one pass where they sit on the same wires
+//                                                         (qfold::pairable: the leaf circuit), S-boxes and linear term shared
 //   quotient_hash_rounds_kernel                           the hash gates round by round: the forward walk of the same Schedule
 //                                                         (qfold::walk), the fold's A/B partner under QPGPU_QUOTIENT_FOLD=0
 // Layout as in prover_kernels.hip: LDEs column-major in leaf order (slot j = point bitrev(j)).
@@ -634,6 +636,111 @@ __global__ void __launch_bounds__(256) quotient_poseidon2_kernel(QuotientArgs a,
     s.kind = GATE_POSEIDON2;
     hash_gate_folded<NCH>(a, s, gi, t0, slot, finalize);
 }
+// ---- (3'+4') a PoseidonGate and a Poseidon2 gate on the same wires (qfold::pairable) in one pass ----
+// Both gates' layout is then qfold::poseidon_schedule(), known here. What the two folded kernels each did on their own is done once:
+// the swapped inputs, the swap / delta constraints, the load of every target wire and output, their -alpha^q weights and the
+// target wires' S-boxes. Per challenge three sums: lin (swap / delta constraints, targets and outputs by -alpha^q; T_NALPHA is read
+// from table slot 0, the other slot holds the same values) and omA, omB (each gate's head and wire S-boxes by its own omega). A
+// target wire costs one S-box and 3 * NCH weighted products instead of two and 4 * NCH. PAIR_GROUP: wires per product group, as
+// FOLD_GROUP above (it divides 12 and leaves the same tail); resources and times of 4 and 6 in profiles/quotient_pair_notes.txt.
+// Acc192::top: lin takes 5 + 106 + 12 = 123 products below 2^128, omA and omB 12 + 106 = 118 each, and the sum of lin and one of
+// them counts at most 241 carries and one of its own: below 2^8, under the 265 of hash_gate_folded.
+#ifndef PAIR_GROUP
+#define PAIR_GROUP FOLD_GROUP
+#endif
+constexpr int PAIR_TAIL = 106 % PAIR_GROUP;
+static_assert(12 % PAIR_GROUP == 0 && PAIR_TAIL > 0, "whole groups in the head, one tail group behind the 106 target wires");
+__device__ __forceinline__ gl::Acc192 acc_sum(const gl::Acc192 &x, const gl::Acc192 &y) {
+    gl::Acc192 r;
+    r.lo = x.lo + y.lo;
+    const u64 c0 = r.lo < x.lo ? 1 : 0, h = x.hi + y.hi;
+    r.hi = h + c0;
+    r.top = x.top + y.top + (u32)(h < x.hi ? 1 : 0) + (u32)(r.hi < c0 ? 1 : 0);
+    return r;
+}
+// the twelve head S-boxes of one gate, in product groups, weighted into its omega sums
+template <int NCH>
+__device__ __forceinline__ void pair_head(const u64 (&st)[12], const u64 *F, gl::Acc192 (&om)[NCH]) {
+#pragma unroll
+    for (int g0 = 0; g0 < 12; g0 += PAIR_GROUP) {
+        u64 h[PAIR_GROUP];
+#pragma unroll
+        for (int i = 0; i < PAIR_GROUP; i++) h[i] = st[g0 + i];
+        sbox7_group(h);
+#pragma unroll
+        for (int i = 0; i < PAIR_GROUP; i++)
+#pragma unroll
+            for (int c = 0; c < NCH; c++) gl::acc_mul(om[c], h[i], F[c * qfold::WORDS + qfold::T_HEAD + g0 + i]);
+    }
+}
+// N target wires from number j0 on: loaded once, wire * (-alpha^q) into lin, one S-box, wire^7 * omega into each gate's sums
+template <int NCH, int N>
+__device__ __forceinline__ void pair_targets(const QuotientArgs &a, const qfold::Schedule &s, const u64 *FA, const u64 *FB, u64 j, u32 j0,
+                                             gl::Acc192 (&lin)[NCH], gl::Acc192 (&omA)[NCH], gl::Acc192 (&omB)[NCH]) {
+    u64 v[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) v[i] = a.wires[(u64)qfold::target_wire(s, j0 + i) * a.lde_n + j];
+#pragma unroll
+    for (int i = 0; i < N; i++)
+#pragma unroll
+        for (int c = 0; c < NCH; c++) gl::acc_mul(lin[c], v[i], a.fold[c * qfold::WORDS + qfold::T_NALPHA + j0 + i]);
+    sbox7_group(v);
+#pragma unroll
+    for (int i = 0; i < N; i++)
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            gl::acc_mul(omA[c], v[i], FA[c * qfold::WORDS + qfold::T_OMEGA + j0 + i]);
+            gl::acc_mul(omB[c], v[i], FB[c * qfold::WORDS + qfold::T_OMEGA + j0 + i]);
+        }
+}
+// giA / slotA: the PoseidonGate's index in the gate list and its table slot, giB / slotB: the Poseidon2 gate's
+template <int NCH>
+__global__ void __launch_bounds__(256, NCH <= 2 ? 4 : 2) quotient_hash_pair_kernel(QuotientArgs a, u32 giA, u32 giB, u32 slotA, u32 slotB, u32 t0, int finalize) {
+    const u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (j >= a.q_n) return;
+    quotient_select_proof(a);
+    const u64 S = a.lde_n;
+    const u64 *ap = a.alpha_pows + t0;
+    const u64 *FA = a.fold + (u64)slotA * NCH * qfold::WORDS, *FB = a.fold + (u64)slotB * NCH * qfold::WORDS;
+    const qfold::Consts K = {a.poseidon_rc, a.p2_gate};
+    const qfold::Schedule s = qfold::poseidon_schedule();
+    qfold::Schedule sB = s;
+    sB.kind = GATE_POSEIDON2;
+    gl::Acc192 lin[NCH], omA[NCH], omB[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) { lin[c] = gl::acc_zero(); omA[c] = gl::acc_zero(); omB[c] = gl::acc_zero(); }
+    u64 st[12];
+    qfold::swapped_inputs(s, WireAt{a.wires, S, j}, WeighInto<NCH>{lin, ap, a.nterms}, st);
+    {
+        u64 h[12];
+#pragma unroll
+        for (int i = 0; i < 12; i++) h[i] = st[i];
+        qfold::head_inputs(s, K, h);
+        pair_head<NCH>(h, FA, omA);
+    }
+    qfold::head_inputs(sB, K, st);
+    pair_head<NCH>(st, FB, omB);
+    u32 j0 = 0;
+#pragma unroll 1
+    for (; j0 + PAIR_GROUP <= s.nw; j0 += PAIR_GROUP) pair_targets<NCH, PAIR_GROUP>(a, s, FA, FB, j, j0, lin, omA, omB);
+    pair_targets<NCH, PAIR_TAIL>(a, s, FA, FB, j, j0, lin, omA, omB);
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        const u64 o = a.wires[(u64)(s.w_output + i) * S + j];
+#pragma unroll
+        for (int c = 0; c < NCH; c++) gl::acc_mul(lin[c], o, a.fold[c * qfold::WORDS + qfold::T_NALPHA + s.nw + i]);
+    }
+    const u64 fA = gate_filter(a, giA, a.cs[(u64)a.gates[giA].selector_index * S + j]);
+    const u64 fB = gate_filter(a, giB, a.cs[(u64)a.gates[giB].selector_index * S + j]);
+    u64 sum[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const u64 gA = gl::add(gl::acc_reduce(acc_sum(omA[c], lin[c])), FA[c * qfold::WORDS + qfold::T_KAPPA]);
+        const u64 gB = gl::add(gl::acc_reduce(acc_sum(omB[c], lin[c])), FB[c * qfold::WORDS + qfold::T_KAPPA]);
+        sum[c] = gl::add(gl::mul(fA, gA), gl::mul(fB, gB));
+    }
+    quotient_add_store(a, S, j, 1, sum, finalize);     // the filters are in already
+}
 // the backward walk: block (hash gate, challenge, proof), one wave; 48 of its lanes share a step's 144 products
 __global__ void __launch_bounds__(64) quotient_fold_sweep_kernel(FoldSweepArgs fa) {
     __shared__ qfold::Scratch scratch;
@@ -688,6 +795,19 @@ static void hash_gate_launch(const QuotientArgs &a, const GateDev *host_gates, u
         else hipLaunchKernelGGL((quotient_hash_rounds_kernel<NCH, GATE_POSEIDON2>), g, b, 0, st, a, s, gi, t0, finalize);
     }
 }
+// the two hash gates of a pairable list: idx[0], idx[1] in gate-list order (their table slots are 0 and 1)
+static bool hash_gate_pair(const GateDev *host_gates, u32 num_gates, const P2GateLayout &lay, u32 (&idx)[2]) {
+    u32 n = 0;
+    for (u32 i = 0; i < num_gates; i++)
+        if (is_hash_gate(host_gates[i])) { if (n == 2) return false; idx[n++] = i; }
+    if (n != 2) return false;
+    auto sched = [&](u32 i) { return host_gates[i].type == GATE_POSEIDON ? qfold::poseidon_schedule() : qfold::poseidon2_schedule(lay); };
+    return qfold::pairable(sched(idx[0]), sched(idx[1]));
+}
+bool pk_quotient_pairable(const GateDev *host_gates, uint32_t num_gates, const P2GateLayout &p2_layout) {
+    u32 idx[2];
+    return hash_gate_pair(host_gates, num_gates, p2_layout, idx);
+}
 hipError_t pk_quotient_fold_sweep(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st) {
     if (!a.fold || a.batch == 0) return hipSuccess;
     FoldSweepArgs fa{};
@@ -724,8 +844,9 @@ bool pk_quotient_fused_gates(const GateDev *host_gates, uint32_t num_gates, uint
     if (out) *out = fg;
     return true;
 }
-// The stage's launches: the permutation terms (perm), every other gate, then the hash gates (heavy, one launch each); with
-// `finalize` the last of them also applies 1/Z_H and stores. Without either: the gate sums alone, for the witness check.
+// The stage's launches: the permutation terms (perm), every other gate, then the hash gates (heavy, one launch each, or one for
+// the two of a folded pair); with `finalize` the last of them also applies 1/Z_H and stores. Without either: the gate sums alone,
+// for the witness check.
 template <int NCH>
 static hipError_t quotient_launch(const QuotientArgs &a, const GateDev *host_gates, bool perm, bool finalize, hipStream_t st) {
     dim3 b(256), g((unsigned)((a.q_n + 255) / 256), 1, a.batch);
@@ -742,6 +863,12 @@ static hipError_t quotient_launch(const QuotientArgs &a, const GateDev *host_gat
         if (perm) hipLaunchKernelGGL((quotient_perm_kernel<NCH>), g, b, 0, st, a);
         if (wide_random_access(a, host_gates)) hipLaunchKernelGGL((quotient_gates_kernel<NCH, true>), g, b, 0, st, a, t0, fin_gates);
         else hipLaunchKernelGGL((quotient_gates_kernel<NCH, false>), g, b, 0, st, a, t0, fin_gates);
+    }
+    u32 pr[2];
+    if (a.fold && a.pair && hash_gate_pair(host_gates, a.num_gates, a.p2_layout, pr)) {
+        const u32 sa = host_gates[pr[0]].type == GATE_POSEIDON ? 0 : 1;      // the PoseidonGate's table slot
+        hipLaunchKernelGGL((quotient_hash_pair_kernel<NCH>), g, b, 0, st, a, pr[sa], pr[sa ^ 1], sa, sa ^ 1, t0, finalize ? 1 : 0);
+        return hipGetLastError();
     }
     u32 slot = 0;
     for (u32 i = 0; i < a.num_gates; i++)

@@ -34,6 +34,8 @@ struct QuotientArgs {
     // pk_quotient: 1 = quotient_perm_gates_kernel where the gate list allows it (pk_quotient_fused_gates), 0 = always the two
     // launches; fused_plain_map = 1 gives that kernel the proof-major workgroup order of the (tiles, 1, batch) grids (measurement)
     uint32_t fused, fused_plain_map;
+    // 1 = both hash gates from quotient_hash_pair_kernel where they are a pair (pk_quotient_pairable) and fold is set, 0 = one launch each
+    uint32_t pair;
 };
 
 // the gates quotient_perm_gates_kernel evaluates on its walk: their indices in the gate list (0xFFFFFFFF = the circuit has none)
@@ -56,6 +58,8 @@ hipError_t pk_quotient(const QuotientArgs &a, const GateDev *host_gates, hipStre
 bool pk_quotient_fused_gates(const GateDev *host_gates, uint32_t num_gates, uint32_t num_routed, uint32_t chunk, uint32_t nchunks, FusedGates *out);
 // hash gates of the list that carry constraints; more than qfold::MAX_GATES: the circuit runs without the fold
 uint32_t pk_count_hash_gates(const GateDev *host_gates, uint32_t num_gates);
+// true: the list holds exactly two hash gates and their schedules are qfold::pairable (one launch serves both, given the fold)
+bool pk_quotient_pairable(const GateDev *host_gates, uint32_t num_gates, const P2GateLayout &p2_layout);
 // fills a.fold for the batch from its alpha powers (run before pk_quotient / pk_gate_sums whenever QuotientArgs::fold is set)
 hipError_t pk_quotient_fold_sweep(const QuotientArgs &a, const GateDev *host_gates, hipStream_t st);
 // gate kernels only (no permutation terms, no 1/Z_H): the witness check runs them on the trace rows
