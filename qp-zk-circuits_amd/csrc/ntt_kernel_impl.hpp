@@ -123,12 +123,13 @@ struct PassGeom {
     u64 lane0;
     const u64 *in;
     u64 *out;
+    const u64 *sa, *sb;   // COSET only: this coset's slices of in_scale_a / in_scale_b
 };
 
 // Round A of a pass: loads 2^KA points per thread, coset scale, register transform, inner twiddles. With KB == 0 it also
 // finishes the pass. On return x holds the values to exchange and wr_base the LDS word of x[0] (x[q] goes NB + 1 words
 // further per q); TO_LDS stores them as whole 8-byte words right away. Returns whether this thread took part.
-template <int KA, int KB, bool INV, bool TO_LDS, int SPARSE>
+template <int KA, int KB, bool INV, bool TO_LDS, int SPARSE, bool COSET = false>
 __device__ __forceinline__ bool ntt_round_a(const NttPassArgs &a, const PassGeom &g, u64 *lds, u64 (&x)[1 << KA], int &wr_base) {
     constexpr int NA = 1 << KA, NB = 1 << KB;
     const int T = g.T, tid = g.tid;
@@ -154,7 +155,16 @@ __device__ __forceinline__ bool ntt_round_a(const NttPassArgs &a, const PassGeom
         if (lane_ok && p < a.p_valid) v = in[base + (u32)i * istep];
         x[i] = v;
     }
-    if (a.in_scale_a) {  // coset: x[p, lane] *= A[p] * B[mm]
+    if constexpr (COSET) {
+        if (g.sa) {  // the coset's own shift g w^k: x[p, lane] *= A_k[p] * B_k[mm]
+            const u64 sb = g.sb[mm];
+#pragma unroll
+            for (int i = 0; i < NA; i++) {
+                const u32 p = (u32)(i * NB + m);
+                if (p < a.p_valid) x[i] = gl::mul(x[i], gl::mul(g.sa[p], sb));
+            }
+        }
+    } else if (a.in_scale_a) {  // coset: x[p, lane] *= A[p] * B[mm]
         const u64 sb = a.in_scale_b[mm];
 #pragma unroll
         for (int i = 0; i < NA; i++) {
@@ -246,7 +256,7 @@ __device__ __forceinline__ void ntt_round_b(const NttPassArgs &a, const PassGeom
 // One pass of one tile. Element s = j * NB + m of lane l crosses the rounds through LDS word l * RP + s + (s >> KB).
 // Whole-word mode: one 8-byte exchange, one barrier. SPLIT: the low and the high 32-bit halves go through the same 4-byte
 // slots one after the other — half the LDS per workgroup, so twice as many wavefronts share a CU, for two more barriers.
-template <int KA, int KB, bool INV, bool SPLIT, int SPARSE = 0>
+template <int KA, int KB, bool INV, bool SPLIT, int SPARSE = 0, bool COSET = false>
 __device__ __forceinline__ void ntt_pass_body(const NttPassArgs &a) {
     constexpr int NA = 1 << KA, NB = 1 << KB;
     extern __shared__ __align__(16) u64 lds[];
@@ -255,15 +265,26 @@ __device__ __forceinline__ void ntt_pass_body(const NttPassArgs &a) {
     g.tid = threadIdx.x;
     g.RP = (int)a.row_pitch;   // R + NA + a pad chosen for the exchange width and the tile shape (ntt_pass_row_pitch)
     g.lane0 = (u64)blockIdx.x << a.log_t;          // first lane of this tile (global lane index)
-    const u64 col = blockIdx.y;
-    g.in = a.in + col * a.in_col_stride + (u64)blockIdx.z * a.in_proof_stride;
-    g.out = a.out + col * a.out_col_stride + (u64)blockIdx.z * a.out_proof_stride;
+    if constexpr (COSET) {
+        // grid.y = column << coset_bits | k: coset k of the column (NttPassArgs)
+        const u32 cb = a.coset_bits, k = blockIdx.y & ((1u << cb) - 1u);
+        const u64 col = blockIdx.y >> cb;
+        const u32 c = a.coset_brev ? (__brev(k) >> (32u - cb)) : k;
+        g.in = a.in + col * a.in_col_stride + (u64)blockIdx.z * a.in_proof_stride + (u64)c * a.in_coset_stride;
+        g.out = a.out + col * a.out_col_stride + (u64)blockIdx.z * a.out_proof_stride + (u64)c * a.out_coset_stride;
+        g.sa = a.in_scale_a ? a.in_scale_a + (u64)k * a.scale_a_coset_stride : nullptr;
+        g.sb = a.in_scale_b + (u64)k * a.scale_b_coset_stride;
+    } else {
+        const u64 col = blockIdx.y;
+        g.in = a.in + col * a.in_col_stride + (u64)blockIdx.z * a.in_proof_stride;
+        g.out = a.out + col * a.out_col_stride + (u64)blockIdx.z * a.out_proof_stride;
+    }
 
     if constexpr (!SPLIT) {
         {
             u64 x[NA];
             int wr_base;
-            ntt_round_a<KA, KB, INV, true, SPARSE>(a, g, lds, x, wr_base);
+            ntt_round_a<KA, KB, INV, true, SPARSE, COSET>(a, g, lds, x, wr_base);
         }
         if constexpr (KB == 0) return;
         __syncthreads();
@@ -283,7 +304,7 @@ __device__ __forceinline__ void ntt_pass_body(const NttPassArgs &a) {
         u32 *lds32 = reinterpret_cast<u32 *>(lds);
         u64 x[NA];
         int wr_base;
-        const bool active_a = ntt_round_a<KA, KB, INV, false, SPARSE>(a, g, lds, x, wr_base);
+        const bool active_a = ntt_round_a<KA, KB, INV, false, SPARSE, COSET>(a, g, lds, x, wr_base);
         int j, l;   // round B thread mapping
         if (a.store_lane_fast) { l = g.tid & (g.T - 1); j = g.tid >> a.log_t; }
         else { j = g.tid & (NA - 1); l = g.tid >> KA; }
@@ -341,8 +362,24 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))
     ntt_pass_body<KA, KB, false, true, lde_sparse_lv<KA, KB>()>(a);
 }
 
+// One coset of a coset-decomposed LDE per grid.y entry (forward only; coset_bits >= 1): the pass kernels above stay as they are.
+template <int KA, int KB>
+__global__ void __launch_bounds__(512) ntt_pass_coset_kernel(const NttPassArgs a) { ntt_pass_body<KA, KB, false, false, 0, true>(a); }
+template <int KA, int KB>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) ntt_pass_coset_split_kernel(const NttPassArgs a) {
+    ntt_pass_body<KA, KB, false, true, 0, true>(a);
+}
+
 template <int KA, int KB>
 hipError_t launch_dir(const NttPassArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
+    if (a.coset_bits) {
+        if (a.inverse || a.coset_bits > 15) return hipErrorInvalidValue;
+        if constexpr (has_split_variant<KA, KB>()) {
+            if (a.split_lds) { hipLaunchKernelGGL((ntt_pass_coset_split_kernel<KA, KB>), grid, block, lds, st, a); return hipGetLastError(); }
+        }
+        hipLaunchKernelGGL((ntt_pass_coset_kernel<KA, KB>), grid, block, lds, st, a);
+        return hipGetLastError();
+    }
     const bool rows = KB > 0 && a.log_m == 0 && a.load_lane_fast == 0 && a.in_p_stride == 1 && a.in_row_stride > 1 && a.in_col_stride != 0;
     if constexpr (lde_sparse_lv<KA, KB>() > 0) {
         if (a.sparse_lv == lde_sparse_lv<KA, KB>() && !a.inverse) {
@@ -390,6 +427,14 @@ hipError_t set_lds_attr() {
         if (e != hipSuccess) return e;
         if constexpr (has_split_variant<KA, KB>()) {
             e = hipFuncSetAttribute((const void *)ntt_pass_lde_split_kernel<KA, KB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) return e;
+        }
+    }
+    {
+        hipError_t e = hipFuncSetAttribute((const void *)ntt_pass_coset_kernel<KA, KB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        if constexpr (has_split_variant<KA, KB>()) {
+            e = hipFuncSetAttribute((const void *)ntt_pass_coset_split_kernel<KA, KB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return e;
         }
     }

@@ -1,4 +1,4 @@
-// ntt_lde_column.hip — column-resident coset LDE for proof-sized columns (2^11..2^13 coefficients, rate_bits <= 3).
+// ntt_lde_column.hip — column-resident coset LDE for proof-sized columns (2^11..2^13 coefficients, any rate_bits the planner sends: 1..8).
 //
 // The generic plan (ntt_plan.cpp) runs every transform above 2^10 points as two launches with an intermediate of the output's
 // size in HBM. A zero-padded transform of 2^(d+r) points on the coset g<w_(d+r)> is 2^r independent 2^d-point transforms:
@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(LDE_COL_THREADS) __attribute__((amdgpu_waves_p
 }  // namespace
 
 hipError_t ntt_lde_column_launch(const NttLdeColumnArgs &a, unsigned log_n_in, uint32_t n_proofs, hipStream_t st) {
-    if (a.rate_bits > 3 || a.ncols == 0 || n_proofs == 0 || n_proofs > 65535) return hipErrorInvalidValue;
+    if (a.rate_bits + log_n_in > 23 || a.ncols == 0 || n_proofs == 0 || n_proofs > 65535) return hipErrorInvalidValue;
     if (a.xcd_map && a.ncols % 8) return hipErrorInvalidValue;
     const uint64_t blocks = (uint64_t)a.ncols << a.rate_bits;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;

@@ -38,6 +38,14 @@ struct NttPassArgs {
     uint32_t split_lds;        // set by ntt_pass_launch: exchange the 32-bit halves one after the other (half the LDS per workgroup)
     const uint64_t *in_scale_a;  // coset input scale: x[p, mm] *= a[p] * b[mm]; null: none
     const uint64_t *in_scale_b;
+    // coset decomposition of a zero-padded LDE (coset_bits > 0; the ntt_pass_coset kernels): grid.y = column << coset_bits | k.
+    // Coset k is a transform of its own: it reads the column's coefficients (plus k * in_coset_stride where the input is an
+    // intermediate of the decomposition), scales them by slice k of the scale tables and writes at c * out_coset_stride, with
+    // c = brev_(coset_bits)(k) when coset_brev is set (leaf order: the coset's contiguous block) and c = k otherwise.
+    uint32_t coset_bits;
+    uint32_t coset_brev;
+    uint64_t in_coset_stride, out_coset_stride;
+    uint64_t scale_a_coset_stride, scale_b_coset_stride;   // words between two cosets' slices of in_scale_a / in_scale_b
 };
 
 // Column-resident coset LDE (ntt_lde_column.hip): 2^log_n_in coefficients per column, 2^rate_bits cosets, leaf (bit-reversed)

@@ -126,6 +126,23 @@ int cached_table(qpgpu_ctx *ctx, const std::string &key, Build build, const uint
     return QPGPU_OK;
 }
 
+// Scale table of the coset decomposition: t[k][i] = ((shift w_(d + r)^k)^step)^i for k < 2^r, i < count
+int coset_powers(qpgpu_ctx *ctx, const char *tag, u64 shift, unsigned d, unsigned r, u64 step, u64 count, const uint64_t **out) {
+    const std::string key = std::string(tag) + std::to_string(shift) + "_" + std::to_string(d) + "_" + std::to_string(r);
+    return cached_table(ctx, key, [&] {
+        std::vector<uint64_t> t((size_t)count << r);
+        const u64 wL = gl::root_of_unity(d + r);
+        u64 base = gl::canon(shift);
+        for (u64 k = 0; k < (1ull << r); k++) {
+            const u64 b = gl::pow(base, step);
+            u64 acc = 1;
+            for (u64 i = 0; i < count; i++) { t[(size_t)(k * count + i)] = gl::canon(acc); acc = gl::mul(acc, b); }
+            base = gl::mul(base, wL);
+        }
+        return t;
+    }, out);
+}
+
 unsigned brev_bits(unsigned x, unsigned bits) {
     unsigned r = 0;
     for (unsigned i = 0; i < bits; i++) r |= ((x >> i) & 1u) << (bits - 1 - i);
@@ -135,6 +152,13 @@ unsigned brev_bits(unsigned x, unsigned bits) {
 // QPGPU_NTT_LDE_COLUMN: 1 (default) proof-sized coset LDEs run column-resident in one launch (ntt_lde_column.hip); 0 restores the
 // two generic passes; 2 keeps the new kernel but maps workgroups to (column, coset) in plain order (measurements only).
 int lde_column_mode() { static const int m = env_int("QPGPU_NTT_LDE_COLUMN", 1); return m; }
+
+// QPGPU_NTT_LDE_COSETS: which zero-padded LDEs run as 2^r independent 2^d-point coset transforms (lde_coset_run below).
+// 0 (default): the shapes the pruned full-size plan cannot take (an input shorter than one pass-1 row; more than 2^20 points with
+// less than 1/8 of them given), and d = 11..13 at rate_bits 4..8 on the column-resident kernel. 1: every LDE of more than 2^10 points with
+// rate_bits >= 4 (measurements: the shapes both routes can take). 2: as 0, but d = 11..13 at rate_bits >= 4 stays on the full-size plan wherever
+// that plan can take it (measurements only).
+int lde_cosets_mode() { static const int m = env_int("QPGPU_NTT_LDE_COSETS", 0); return m; }
 
 // Tables and launch of the column-resident LDE: 2^d coefficients per column -> 2^(d + r) values on shift <w_(d+r)>, leaf order.
 int lde_column_run(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned d, unsigned r, size_t batch, u64 shift,
@@ -188,9 +212,14 @@ struct Geom {
     u64 scratch_off = 0;      // words into ctx->scratch the natural-order intermediate may use
     uint32_t nproofs = 1;     // lockstep batch: proof b at d_in + b * in_ps, d_out + b * out_ps
     u64 in_ps = 0, out_ps = 0;
+    // coset decomposition (lde_coset_run): the call is a 2^d-point transform of every column on each of the 2^coset_bits shifts
+    // coset_shift * w_(d + coset_bits)^k; the output column holds 2^(d + coset_bits) words (out_col_stride is the LDE's)
+    unsigned coset_bits = 0;
 };
 int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log_n_in, unsigned log_n_out,
              size_t batch, bool inverse, bool out_bitrev, uint64_t coset_shift, const Geom &g);
+int lde_coset_run(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned d, unsigned r, size_t batch, bool out_bitrev,
+                  uint64_t coset_shift, const Geom &g);
 }  // namespace
 
 // Forward / inverse / coset-LDE transform. log_n_in <= log_n_out; inputs beyond 2^log_n_in are zero.
@@ -215,6 +244,12 @@ int ntt_run(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log_
         g.nproofs = np.nproofs; g.in_ps = np.in_ps; g.out_ps = np.out_ps;
         return ntt_core(ctx, d_in, d_out, log_n_in, log_n_out, batch, inverse, out_bitrev, coset_shift, g);
     }
+    // a zero-padded input of less than 1/8 of the output: 2^r coset transforms of the input's size, the proofs on the grid
+    if (!inverse && log_n_in + 3 < log_n_out) {
+        Geom g;
+        g.nproofs = np.nproofs; g.in_ps = np.in_ps; g.out_ps = np.out_ps;
+        return lde_coset_run(ctx, d_in, d_out, log_n_in, log_n_out - log_n_in, batch, out_bitrev, coset_shift, g);
+    }
     if (np.nproofs > 1) {   // the three-pass sizes take the proofs one after the other
         for (uint32_t b = 0; b < np.nproofs; b++) {
             int rc = ntt_run(ctx, d_in + b * np.in_ps, d_out + b * np.out_ps, log_n_in, log_n_out, batch, inverse, out_bitrev, coset_shift);
@@ -228,7 +263,7 @@ int ntt_run(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log_
     // (natural order: X[k0 + 8 k']) or land in bit-reversed block order (leaf order). ----
     const unsigned L = log_n_out, L0 = 3, Li = L - L0;
     const u64 N = 1ull << L, M0 = 1ull << Li, n_in = 1ull << log_n_in;
-    if (log_n_in < Li) return ctx->fail(QPGPU_EINVAL, "lde: for 2^21..2^23 outputs the input must be at least 1/8 of the output");
+    if (log_n_in < Li) return ctx->fail(QPGPU_EINVAL, "ntt: an inverse transform of 2^21..2^23 points takes an input of at least 1/8 of them");
     {
         static std::once_flag once;
         static hipError_t init_err = hipSuccess;
@@ -282,11 +317,61 @@ int ntt_run(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log_
 }
 
 namespace {
+// Whether the column-resident kernel can take these buffers: 16-byte stores, and no workgroup may write what another still reads.
+bool lde_column_fits(const uint64_t *d_in, const uint64_t *d_out, unsigned log_n_in, unsigned L, size_t batch, const Geom &g) {
+    const u64 n_in = 1ull << log_n_in, N = 1ull << L;
+    const u64 in_cs = g.in_col_stride ? g.in_col_stride : n_in, out_cs = g.out_col_stride ? g.out_col_stride : N;
+    const u64 in_span = (g.nproofs - 1) * g.in_ps + (batch - 1) * in_cs + n_in, out_span = (g.nproofs - 1) * g.out_ps + (batch - 1) * out_cs + N;
+    const bool aligned = ((uintptr_t)d_out % 16 == 0) && out_cs % 2 == 0 && g.out_ps % 2 == 0;
+    bool disjoint = d_in + in_span <= d_out || d_out + out_span <= d_in;
+    if (!disjoint && g.nproofs > 1 && g.in_ps == g.out_ps) {
+        // a lockstep batch keeps input and output in one workspace per proof: the regions interleave without touching
+        const int64_t ps = (int64_t)g.in_ps, delta = d_out - d_in, nb = (int64_t)g.nproofs;
+        const int64_t in_one = (int64_t)((batch - 1) * in_cs + n_in), out_one = (int64_t)((batch - 1) * out_cs + N);
+        disjoint = true;
+        for (int64_t e = -(nb - 1); e <= nb - 1 && disjoint; e++)
+            if (e * ps < delta + out_one && delta < e * ps + in_one) disjoint = false;
+    }
+    return aligned && disjoint;
+}
+
+// A zero-padded 2^(d + r)-point transform on the coset shift<w_(d+r)> as 2^r transforms of 2^d points: LDE point k + 2^r t is
+// (shift w_(d+r)^k) w_d^t, so coset k is the 2^d-point transform of the coefficients scaled by the powers of shift w_(d+r)^k. In
+// leaf order its values are the contiguous block brev_r(k) 2^d of the output, in natural order the points k + 2^r t. The
+// cosets ride on grid.y next to the columns (the ntt_pass_coset kernels), so an LDE is one or two launches at any rate; column
+// slices only where columns x cosets would pass 65535.
+int lde_coset_run(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned d, unsigned r, size_t batch, bool out_bitrev,
+                  uint64_t coset_shift, const Geom &g) {
+    const unsigned L = d + r;
+    if (d < 1 || r < 1 || r > 15 || d > 19 || L > 23) return ctx->fail(QPGPU_EINVAL, "lde: the coset decomposition takes 2^1..2^19 coefficients and up to 2^15 cosets");
+    if (g.out_mul != 1 || g.scale) return ctx->fail(QPGPU_EINVAL, "lde: the coset decomposition is not a block of a larger transform");
+    const u64 shift = coset_shift > 1 ? coset_shift : 1, n = 1ull << d, N = 1ull << L;
+    if (lde_column_mode() && out_bitrev && d >= 11 && d <= 13 && r <= 8 && lde_column_fits(d_in, d_out, d, L, batch, g)) {
+        const u64 in_cs = g.in_col_stride ? g.in_col_stride : n, out_cs = g.out_col_stride ? g.out_col_stride : N;
+        return lde_column_run(ctx, d_in, d_out, d, r, batch, shift, in_cs, out_cs, g.nproofs, g.in_ps, g.out_ps);
+    }
+    Geom c = g;
+    c.coset_bits = r;
+    c.in_col_stride = g.in_col_stride ? g.in_col_stride : n;
+    c.out_col_stride = g.out_col_stride ? g.out_col_stride : N;
+    // d <= 10: the polynomials are lanes, their 32-bit word offsets (row x stride) bound a slice; above, columns x cosets on grid.y
+    size_t per = d <= 10 ? (size_t)((1ull << 32) / std::max(c.in_col_stride, c.out_col_stride)) : (size_t)(65535u >> r);
+    if (per == 0) per = 1;
+    for (size_t c0 = 0; c0 < batch; c0 += per) {
+        const size_t cnt = std::min(per, batch - c0);
+        QP_TRY_NTT(ntt_core(ctx, d_in + c0 * c.in_col_stride, d_out + c0 * c.out_col_stride, d, d, cnt, false, out_bitrev, shift, c));
+    }
+    return QPGPU_OK;
+}
+}  // namespace
+
+namespace {
 int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log_n_in, unsigned log_n_out,
              size_t batch, bool inverse, bool out_bitrev, uint64_t coset_shift, const Geom &g) {
     const unsigned L = log_n_out;
     const u64 N = 1ull << L, n_in = 1ull << log_n_in;
-    const bool coset = coset_shift > 1;
+    const bool coset = coset_shift > 1 || g.coset_bits;
+    const unsigned cb = g.coset_bits;
     if (L == 0) {
         if (d_in != d_out && !ctx->plan_only) QP_HIP(ctx, hipMemcpyAsync(d_out, d_in, batch * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
         return QPGPU_OK;
@@ -300,22 +385,15 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
 
     // proof-sized coset LDE in leaf order: one launch, no intermediate (ntt_lde_column.hip). Everything else, and buffers the
     // kernel's 16-byte stores or its read-while-others-write order do not suit, stays on the generic passes.
-    if (lde_column_mode() && !inverse && out_bitrev && coset && log_n_in >= 11 && log_n_in <= 13 && L > log_n_in && L - log_n_in <= 3) {
+    const unsigned pad_bits = L - log_n_in;
+    if (lde_column_mode() && !g.coset_bits && !inverse && out_bitrev && coset && log_n_in >= 11 && log_n_in <= 13 && pad_bits >= 1 &&
+        (pad_bits <= 3 || (pad_bits <= 8 && lde_cosets_mode() != 2)) && lde_column_fits(d_in, d_out, log_n_in, L, batch, g)) {
         const u64 in_cs = g.in_col_stride ? g.in_col_stride : n_in, out_cs = g.out_col_stride ? g.out_col_stride : N;
-        const u64 in_span = (g.nproofs - 1) * g.in_ps + (batch - 1) * in_cs + n_in, out_span = (g.nproofs - 1) * g.out_ps + (batch - 1) * out_cs + N;
-        const bool aligned = ((uintptr_t)d_out % 16 == 0) && out_cs % 2 == 0 && g.out_ps % 2 == 0;
-        bool disjoint = d_in + in_span <= d_out || d_out + out_span <= d_in;
-        if (!disjoint && g.nproofs > 1 && g.in_ps == g.out_ps) {
-            // a lockstep batch keeps input and output in one workspace per proof: the regions interleave without touching
-            const int64_t ps = (int64_t)g.in_ps, delta = d_out - d_in, nb = (int64_t)g.nproofs;
-            const int64_t in_one = (int64_t)((batch - 1) * in_cs + n_in), out_one = (int64_t)((batch - 1) * out_cs + N);
-            disjoint = true;
-            for (int64_t e = -(nb - 1); e <= nb - 1 && disjoint; e++)
-                if (e * ps < delta + out_one && delta < e * ps + in_one) disjoint = false;
-        }
-        if (aligned && disjoint)
-            return lde_column_run(ctx, d_in, d_out, log_n_in, L - log_n_in, batch, coset_shift, in_cs, out_cs, g.nproofs, g.in_ps, g.out_ps);
+        return lde_column_run(ctx, d_in, d_out, log_n_in, pad_bits, batch, coset_shift, in_cs, out_cs, g.nproofs, g.in_ps, g.out_ps);
     }
+    // a zero-padded input shorter than one pass-1 row (2^(L/2) words): the pruned full-size plan below cannot take it
+    if (!g.coset_bits && !inverse && pad_bits >= 1 && L > 10 && (log_n_in < L / 2 || (lde_cosets_mode() == 1 && pad_bits >= 4)))
+        return lde_coset_run(ctx, d_in, d_out, log_n_in, pad_bits, batch, out_bitrev, coset_shift, g);
 
     const std::string dir = inverse ? "i" : "f";
     const u64 wN = inverse ? gl::inv(gl::root_of_unity(L)) : gl::root_of_unity(L);
@@ -337,6 +415,12 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
         a.log_m = 0; a.lanes_total = batch;  // every polynomial is one row = one lane
         a.in_row_stride = n_in; a.in_l_stride = 0; a.in_p_stride = 1;
         a.out_row_stride = N; a.out_l_stride = 0; a.out_p_stride = 1;
+        if (cb) {   // the cosets on grid.y: block brev(k) of the polynomial's row in leaf order, points k + 2^cb t in natural order
+            a.in_row_stride = g.in_col_stride; a.out_row_stride = g.out_col_stride;
+            a.coset_bits = cb; a.coset_brev = out_bitrev ? 1 : 0;
+            a.out_coset_stride = out_bitrev ? N : 1;
+            if (!out_bitrev) a.out_p_stride = 1ull << cb;
+        }
         a.log_t = pick_log_t(s.ka, s.kb, batch);
         a.p_valid = (uint32_t)n_in;
         a.load_lane_fast = 0; a.store_lane_fast = 0;
@@ -347,7 +431,13 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
             int rc = cached(ctx, "in" + dir + std::to_string(L1), wR, 1ull << L1, (uint64_t **)&a.tw_inner);
             if (rc) return rc;
         }
-        if (coset) {
+        if (cb) {
+            int rc = coset_powers(ctx, "ccS", coset_shift, L, cb, 1, N, &a.in_scale_a);    // [2^cb][N]: (shift w^k)^i
+            if (rc) return rc;
+            a.scale_a_coset_stride = N;
+            rc = cached(ctx, "one", 1, 1, (uint64_t **)&a.in_scale_b);
+            if (rc) return rc;
+        } else if (coset) {
             int rc = cached(ctx, "csA" + std::to_string(coset_shift) + "_1_" + std::to_string(log_n_in), coset_shift, n_in, (uint64_t **)&a.in_scale_a);
             if (rc) return rc;
             rc = cached(ctx, "one", 1, 1, (uint64_t **)&a.in_scale_b);
@@ -358,7 +448,7 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
         u64 tiles = (batch + (1ull << a.log_t) - 1) >> a.log_t;
         a.in_proof_stride = g.in_ps; a.out_proof_stride = g.out_ps;
         ctx->prof_begin("ntt_pass_single");
-        hipError_t le = ctx->plan_only ? hipSuccess : ntt_pass_launch(a, tiles, 1, ctx->stream, g.nproofs);
+        hipError_t le = ctx->plan_only ? hipSuccess : ntt_pass_launch(a, tiles, 1ull << cb, ctx->stream, g.nproofs);
         ctx->prof_end();
         QP_HIP(ctx, le);
         return QPGPU_OK;
@@ -371,9 +461,12 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
     bool folded_scale = false;
     u64 mid_cs = out_cs, mid_ps = g.out_ps;
     if (!out_bitrev) {
-        int rc = ctx->ensure_scratch((g.scratch_off + (u64)g.nproofs * batch * N) * sizeof(u64));
+        int rc = ctx->ensure_scratch((g.scratch_off + (((u64)g.nproofs * batch * N) << cb)) * sizeof(u64));
         if (rc) return rc;
-        mid = ctx->scratch + g.scratch_off; mid_cs = N; mid_ps = batch * N;
+        mid = ctx->scratch + g.scratch_off; mid_cs = N << cb; mid_ps = (batch * N) << cb;
+    }
+    if (cb) {   // coset k's transform sits at block brev(k) (leaf order: its place in the output) or k (the scratch) of the column
+        a.coset_bits = cb; a.coset_brev = out_bitrev ? 1 : 0;
     }
     {
         Split s = split_round(L1);
@@ -381,6 +474,7 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
         p.ka = s.ka; p.kb = s.kb;
         p.in = d_in; p.out = mid;
         p.in_col_stride = in_cs; p.out_col_stride = mid_cs;
+        p.out_coset_stride = N;
         p.log_m = L2; p.lanes_total = M1;
         p.in_row_stride = 0; p.in_l_stride = 1; p.in_p_stride = M1;
         p.out_row_stride = 0; p.out_l_stride = 1; p.out_p_stride = M1;
@@ -427,7 +521,13 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
         if (rc) return rc;
         rc = cached(ctx, "hi" + dir + std::to_string(L), gl::pow(wN, 1ull << p.tw_lo_bits), 1ull << (L - p.tw_lo_bits), (uint64_t **)&p.tw_hi);
         if (rc) return rc;
-        if (coset) {
+        if (cb) {   // factored per coset as below: 2^cb (R1 + M1) words, never N << cb
+            rc = coset_powers(ctx, "ccA", coset_shift, L, cb, M1, R1, &p.in_scale_a);     // [2^cb][R1]: (shift w^k)^(M1 p)
+            if (rc) return rc;
+            rc = coset_powers(ctx, "ccB", coset_shift, L, cb, 1, M1, &p.in_scale_b);      // [2^cb][M1]: (shift w^k)^mm
+            if (rc) return rc;
+            p.scale_a_coset_stride = R1; p.scale_b_coset_stride = M1;
+        } else if (coset) {
             const std::string k = std::to_string(coset_shift) + "_" + std::to_string(L2);
             rc = cached(ctx, "csA" + k + "_" + std::to_string(p.p_valid), gl::pow(coset_shift, M1), p.p_valid, (uint64_t **)&p.in_scale_a);
             if (rc) return rc;
@@ -438,7 +538,7 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
         folded_scale = p.tw_scale != 0;
         p.in_proof_stride = g.in_ps; p.out_proof_stride = mid_ps;
         ctx->prof_begin("ntt_pass_strided");
-        hipError_t le = ctx->plan_only ? hipSuccess : ntt_pass_launch(p, tiles, batch, ctx->stream, g.nproofs);
+        hipError_t le = ctx->plan_only ? hipSuccess : ntt_pass_launch(p, tiles, batch << cb, ctx->stream, g.nproofs);
         ctx->prof_end();
         QP_HIP(ctx, le);
     }
@@ -448,6 +548,7 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
         p.ka = s.ka; p.kb = s.kb;
         p.in = mid; p.out = d_out;
         p.in_col_stride = mid_cs; p.out_col_stride = out_cs;
+        p.in_coset_stride = N; p.out_coset_stride = out_bitrev ? N : 1;
         p.log_m = 0; p.lanes_total = R1;
         p.in_row_stride = M1; p.in_l_stride = 0; p.in_p_stride = 1;
         p.log_t = pick_log_t(s.ka, s.kb, R1);
@@ -455,7 +556,7 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
         p.p_valid = (uint32_t)M1;
         p.load_lane_fast = 0;
         if (out_bitrev) { p.out_row_stride = M1; p.out_p_stride = 1; p.store_lane_fast = 0; p.out_bitrev = 1; }
-        else { p.out_row_stride = g.out_mul; p.out_p_stride = R1 * g.out_mul; p.store_lane_fast = 1; p.out_bitrev = 0; }
+        else { p.out_row_stride = g.out_mul << cb; p.out_p_stride = (R1 * g.out_mul) << cb; p.store_lane_fast = 1; p.out_bitrev = 0; }
         p.out_l_stride = 0;
         p.has_out_scale = inverse && !folded_scale ? 1 : 0; p.out_scale = out_scale;
         if (s.kb > 0) {
@@ -465,7 +566,7 @@ int ntt_core(qpgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log
         u64 tiles = (R1 + (1ull << p.log_t) - 1) >> p.log_t;
         p.in_proof_stride = mid_ps; p.out_proof_stride = g.out_ps;
         ctx->prof_begin("ntt_pass_rows");
-        hipError_t le = ctx->plan_only ? hipSuccess : ntt_pass_launch(p, tiles, batch, ctx->stream, g.nproofs);
+        hipError_t le = ctx->plan_only ? hipSuccess : ntt_pass_launch(p, tiles, batch << cb, ctx->stream, g.nproofs);
         ctx->prof_end();
         QP_HIP(ctx, le);
     }

@@ -31,8 +31,8 @@ namespace {
 // what qpgpu_oracle_commit and qpgpu_oracle_commit_batch share: `batch` proofs' matrices into one dense [batch][...] oracle
 int commit_impl(qpgpu_ctx *ctx, const uint64_t *const *polys, uint32_t batch, uint32_t num_polys, unsigned degree_bits, unsigned rate_bits,
                 unsigned cap_height, unsigned flags, uint64_t blinding_seed, uint32_t blinding_stream, qpgpu_oracle **out) {
-    if (degree_bits + rate_bits > 23 || degree_bits < 1 || (degree_bits + rate_bits > 20 && rate_bits > 3))
-        return ctx->fail(QPGPU_EINVAL, "oracle_commit: LDE sizes up to 2^23 (rate_bits <= 3 above 2^20) supported");
+    if (degree_bits + rate_bits > 23 || degree_bits < 1)
+        return ctx->fail(QPGPU_EINVAL, "oracle_commit: LDE sizes up to 2^23 supported");
     if (cap_height > degree_bits + rate_bits) return ctx->fail(QPGPU_EINVAL, "oracle_commit: cap_height exceeds the tree height");
     if (flags & ~7u) return ctx->fail(QPGPU_EINVAL, "oracle_commit: unknown flags");
     ctx->hasher_in_use = true;

@@ -56,7 +56,6 @@ bool StageTables::pair_selected(const CircuitPack &p) const {
 std::string stage_limits(const CircuitPack &p) {
     if (p.num_chunks() > 16 || p.num_challenges > 4) return "too many chunks/challenges";
     if (p.degree_bits + p.rate_bits > 23) return "LDE larger than 2^23 not supported";
-    if (p.degree_bits + p.rate_bits > 20 && p.rate_bits > 3) return "an LDE beyond 2^20 points needs rate_bits <= 3";
     return "";
 }
 

@@ -4,7 +4,7 @@
       Wall time of the wires-shaped commitment of one lockstep batch (2^21 leaves x 135 columns, cap height 4) and of its leaf level
       alone, host timers around a synchronised loop.
 
-  leaf_time.py --config {leaf,zk} [--min-degree-bits N] [--copies K|dense] [--hints] [--proofs N] [--workers W] [--max-batch B] [--pool-proofs N] [--batch-probe B]
+  leaf_time.py --config {leaf,zk} [--min-degree-bits N] [--rate-bits R] [--copies K|dense] [--hints] [--proofs N] [--workers W] [--max-batch B] [--pool-proofs N] [--batch-probe B]
       The leaf PROVER under a CircuitConfig (WormholeProver::new(config)): "leaf" is wormhole_leaf_circuit_config(), "zk" the
       zero-knowledge wormhole_private_batch_circuit_config() of the reference's prover_create_proof_zk bench target. Prints one JSON
       line: single-proof latency of commit -> stage s1 -> s2..s12 (median, host timer), the share of stage s1 (host timer around the
@@ -36,6 +36,7 @@ def prover_mode(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", choices=("leaf", "zk"), required=True)
     ap.add_argument("--min-degree-bits", type=int, default=0)
+    ap.add_argument("--rate-bits", type=int, default=0, help="with --config leaf: the leaf config at another rate_bits (3..8)")
     ap.add_argument("--hints", action="store_true")
     ap.add_argument("--copies", default="1")
     ap.add_argument("--proofs", type=int, default=20)
@@ -46,9 +47,12 @@ def prover_mode(argv):
     a = ap.parse_args(argv)
     L = pkg.leaf
     cfg = "private_batch" if a.config == "zk" else "leaf"
+    if a.rate_bits:
+        assert a.config == "leaf"
+        cfg = pkg.circuit_config("leaf", rate_bits=a.rate_bits)
     c = L.LeafCircuit.dense(a.min_degree_bits, config=cfg) if a.copies == "dense" else L.LeafCircuit(min_degree_bits=a.min_degree_bits, config=cfg, copies=int(a.copies))
     x = L.dummy_circuit_inputs()
-    out = {"config": a.config, "copies": c.copies, "rows_poseidon2": c.info["rows_poseidon2"], "hash_hints": a.hints, "degree_bits": c.info["degree_bits"], "rows_before_padding": c.info["rows_before_padding"],
+    out = {"config": a.config, "rate_bits": int(pkg.pack_header(c.pack)["rate_bits"]), "copies": c.copies, "rows_poseidon2": c.info["rows_poseidon2"], "hash_hints": a.hints, "degree_bits": c.info["degree_bits"], "rows_before_padding": c.info["rows_before_padding"],
            "blinding_cells": int(c.blinding_cells.size), "zero_knowledge": c.zero_knowledge}
     if c.zero_knowledge:
         routed = int(c.config.num_routed_wires)
