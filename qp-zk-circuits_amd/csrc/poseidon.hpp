@@ -131,6 +131,86 @@ GL_HD void mds_layer_rows(u64 (&s)[WIDTH]) {
 // s <- MDS * s
 GL_HD void mds_layer(u64 (&s)[WIDTH]) { mds_layer_rows<0, WIDTH>(s); }
 
+// ---- the same layer on whole words: one wrapping 64-bit transform and one 32-bit transform of the top bits ----
+// mds_circulant_half's transform is additions, subtractions and left shifts only, so it is exact modulo 2^64 (or 2^32) in unsigned
+// wrapping arithmetic whatever the signs of its intermediate values. Every sum with a minus sign is written as (sum of the terms
+// with a plus) - (sum of the terms with a minus): one subtraction per output, and no shifted operand is subtracted on its own
+// (a 64-bit subtraction is two vector instructions and takes no shift; an addition with a shift of at most 4 is one).
+template <class W>
+GL_HD void mds_circulant_wrapping(const W (&x)[WIDTH], W (&o)[WIDTH]) {
+    W U1[3], Um[3], F[3], H[3];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int b = 0; b < 3; b++) {
+        const W e = x[b] + x[b + 6], g = x[b + 3] + x[b + 9];
+        U1[b] = e + g; Um[b] = e - g; F[b] = x[b] - x[b + 6]; H[b] = x[b + 3] - x[b + 9];
+    }
+    const W T = U1[0] + U1[1] + U1[2];
+    const W A[3] = {T + U1[2], T + U1[0], T + U1[1]};                                               // V_1 / 64
+    const W B[3] = {(Um[2] << 3) - ((Um[1] << 1) + Um[0]),                                          // V_-1 / 4, the middle one negated
+                    (Um[0] << 3) + (Um[2] << 1) + Um[1],
+                    (Um[0] << 1) - ((Um[1] << 3) + Um[2])};
+    const W f0 = F[0], f1 = F[1], f2 = F[2], h0 = H[0], h1 = H[1], h2 = H[2];
+    const W R[3] = {((f0 << 1) + (h2 << 2) + f1 + f2) - ((h1 << 4) + h0),                           // Re(V_i / 2)
+                    ((f1 << 1) + h0 + f2) - ((f0 << 2) + (h2 << 4) + h1),
+                    ((f0 << 4) + (f2 << 1) + h0 + h1) - ((f1 << 2) + h2)};
+    const W I[3] = {((h0 << 1) + (f1 << 4) + f0 + h1 + h2) - (f2 << 2),                             // Im(V_i / 2)
+                    ((h1 << 1) + (f2 << 4) + f1 + h2) - ((h0 << 2) + f0),
+                    ((h0 << 4) + (h2 << 1) + f2) - ((h1 << 2) + f0 + f1)};
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int b = 0; b < 3; b++) {
+        const W a16 = A[b] << 4;
+        const W p = b == 1 ? a16 - B[b] : a16 + B[b], q = b == 1 ? a16 + B[b] : a16 - B[b];
+        o[b] = p + R[b]; o[b + 3] = q + I[b]; o[b + 6] = p - R[b]; o[b + 9] = q - I[b];
+    }
+}
+// s[r] <- (MDS * s)[r] for the rows r in [FIRST, FIRST + COUNT), as mds_layer_rows (same contract, same values mod p), without
+// splitting the state into 32-bit halves. Row r of the product is the integer V = sum_j M[r][j] s[j] < 264 * 2^64 (the row sums
+// of the matrix are 256, and 264 in row 0): 73 bits.
+//   * L = V mod 2^64 comes from the transform on the words themselves, wrapping: no half is zero-extended into a register pair.
+//   * V >> 64 comes from the transform on t[j] = s[j] >> 41 in 32-bit wrapping arithmetic, where a subtraction is one instruction:
+//     t[j] < 2^23, so Ht = sum_j M[r][j] t[j] <= 264 (2^23 - 1) < 2^32 is exact, and V / 2^41 = Ht + sum_j M[r][j] (s[j] mod 2^41) /
+//     2^41 with the second sum in [0, 264). So Q = V >> 41 lies in [Ht, Ht + 264), and Q mod 2^23 = L >> 41 is known:
+//     Q = Ht + ((L >> 41) - Ht mod 2^23), because the difference Q - Ht is below 264 < 2^23. V >> 64 = Q >> 23 (below 264).
+//   * ADD_RC: the rows come out as V + rc[r] (the constants of the round that follows, any 64-bit values): rc[r] goes onto L and
+//     rc[r] >> 41 onto Ht, which stays below 265 (2^23 - 1) < 2^32; the two fractions together are below 265, so the same join
+//     holds for V + rc[r] < 265 * 2^64. Two additions instead of a modular addition after the reduction (four instructions).
+template <int FIRST, int COUNT, bool ADD_RC>
+GL_HD void mds_layer_rows_words_rc(u64 (&s)[WIDTH], const u64 *rc) {
+    static_assert(FIRST >= 0 && COUNT >= 1 && FIRST + COUNT <= WIDTH, "rows of the state");
+    constexpr int TOP_SHIFT = 41, TOP_BITS = 64 - TOP_SHIFT;
+    static_assert(265ull * ((1ull << TOP_BITS) - 1) < (1ull << 32), "the top transform, with a constant's top bits, fits 32 bits");
+    u64 ol[WIDTH];
+    u32 t[WIDTH], ot[WIDTH];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < WIDTH; i++) t[i] = (u32)(s[i] >> TOP_SHIFT);
+    mds_circulant_wrapping<u64>(s, ol);
+    mds_circulant_wrapping<u32>(t, ot);
+    ol[0] += s[0] << 3; ot[0] += t[0] << 3;           // the diagonal term 8 * s[0]
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int r = FIRST; r < FIRST + COUNT; r++) {
+        u64 L = ol[r];
+        u32 Ht = ot[r];
+        if (ADD_RC) { L += rc[r]; Ht += (u32)(rc[r] >> TOP_SHIFT); }
+        // Q >> 23 = (Ht >> 23) + 1 exactly when adding Q - Ht carried out of the low 23 bits, i.e. when Q mod 2^23 = L >> 41 is
+        // below Ht mod 2^23; compared 9 bits up, where L's upper word stands as it is (Ht 2^9 has no bit below 2^9)
+        const u32 carry = (u32)(L >> 32) < (Ht << (32 - TOP_BITS)) ? 1u : 0u;
+        s[r] = gl::reduce96(L, (Ht >> TOP_BITS) + carry);
+    }
+}
+template <int FIRST, int COUNT>
+GL_HD void mds_layer_rows_words(u64 (&s)[WIDTH]) { mds_layer_rows_words_rc<FIRST, COUNT, false>(s, nullptr); }
+// the layer and the constants of the round that follows in one step: s <- MDS * s + rc (loose)
+GL_HD void mds_layer_words_rc(u64 (&s)[WIDTH], const u64 *rc) { mds_layer_rows_words_rc<0, WIDTH, true>(s, rc); }
+GL_HD void mds_layer_words(u64 (&s)[WIDTH]) { mds_layer_rows_words<0, WIDTH>(s); }
+
 // ---- the 22 partial rounds in the circulant's spectral domain ----
 // In a partial round only lane 0 goes through the S-box; lanes 1..11 see nothing but the MDS matrix, round after round. The
 // matrix is circ(C) + 8 e0 e0^T, and mds_circulant_half evaluates circ(C) as: forward transform (the butterflies e, f, g, h,

@@ -542,12 +542,11 @@ __device__ __forceinline__ void partial_rounds(u64 (&s)[12], const unsigned char
 // whole wave); lds: the table of build_tables, 16-byte aligned.
 __device__ __forceinline__ void permute_head(u64 (&s)[12], const u64 *rc, const unsigned char *lds) {
     using namespace poseidon;
-    int r = 0;
-    for (int k = 0; k < HALF_FULL; k++, r++) {
 #pragma unroll
-        for (int i = 0; i < WIDTH; i++) s[i] = gl::add_canonical(s[i], rc[r * WIDTH + i]);
+    for (int i = 0; i < WIDTH; i++) s[i] = gl::add_canonical(s[i], rc[i]);
+    for (int k = 0; k < HALF_FULL; k++) {          // a round's layer brings the next round's constants (the fourth round's layer is part of the matrix)
         sbox7_layer(s);
-        if (k + 1 < HALF_FULL) mds_layer(s);
+        if (k + 1 < HALF_FULL) mds_layer_words_rc(s, rc + (k + 1) * WIDTH);
     }
     SboxOfInput f;
     partial_rounds<true>(s, lds, f);
@@ -563,15 +562,13 @@ __device__ __forceinline__ void permute_tail_rounds(u64 (&s)[12], const u64 *rc)
     int r = HALF_FULL + 1 + PARTIAL;
     for (int k = 1; k < HALF_FULL; k++, r++) {
         sbox7_layer(s);
-        mds_layer(s);
-#pragma unroll
-        for (int i = 0; i < WIDTH; i++) s[i] = gl::add_canonical(s[i], rc[r * WIDTH + i]);
+        mds_layer_words_rc(s, rc + r * WIDTH);
     }
     sbox7_layer(s);
 }
 template <int FIRST, int COUNT, bool CANON>
 __device__ __forceinline__ void last_layer_rows(u64 (&s)[12]) {
-    poseidon::mds_layer_rows<FIRST, COUNT>(s);
+    poseidon::mds_layer_rows_words<FIRST, COUNT>(s);
     if (CANON) {
 #pragma unroll
         for (int i = FIRST; i < FIRST + COUNT; i++) s[i] = gl::canon(s[i]);
