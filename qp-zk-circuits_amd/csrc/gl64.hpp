@@ -184,6 +184,34 @@ GL_HD u64 mul(u64 a, u64 b) {
     mul64wide(a, b, lo, hi);
     return reduce128(lo, hi);
 }
+// a b + c with ONE reduction: the 128-bit product plus the 64-bit addend, then reduce128. Exact for every a, b, c:
+// (2^64-1)^2 + 2^64-1 = (2^64-1) 2^64 < 2^128, so the addend cannot carry out of the high word. On the device the addend rides in
+// the multiply-adds' own 64-bit addends: c_lo with a0 b0 (at most (2^32-1)^2 + 2^32-1 = (2^32-1) 2^32: the high word h stays
+// below 2^32), c_hi with the cross term (a0 b1 + h + c_hi <= (2^32-1)^2 + 2^33 - 2 = 2^64 - 1: no wrap); from there on it is
+// mul64wide's second half, carry word included. (The quotient kernel's callers pass canonical a and b, which the bound does not need.)
+GL_HD void mul_add64wide(u64 a, u64 b, u64 c, u64 &lo, u64 &hi) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const u32 a0 = (u32)a, a1 = (u32)(a >> 32), b0 = (u32)b, b1 = (u32)(b >> 32);
+    const u64 p00 = (u64)a0 * b0 + (u64)(u32)c;
+    u64 m = (u64)a0 * b1 + ((p00 >> 32) + (c >> 32));
+    u32 cm;
+    asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\t"       // m = a1 b0 + m, carry cM in vcc
+        "v_cndmask_b32_e32 %1, 0, %[one], vcc"        // cm = cM
+        : "+v"(m), "=v"(cm)
+        : "v"(a1), "v"(b0), [one] "v"(1u)
+        : "vcc");
+    hi = (u64)a1 * b1 + (((u64)cm << 32) | (u32)(m >> 32));
+    lo = ((u64)(u32)m << 32) | (u32)p00;
+#else
+    const unsigned __int128 m = (unsigned __int128)a * b + c;
+    lo = (u64)m; hi = (u64)(m >> 64);
+#endif
+}
+GL_HD u64 mul_add(u64 a, u64 b, u64 c) {
+    u64 lo, hi;
+    mul_add64wide(a, b, c, lo, hi);
+    return reduce128(lo, hi);
+}
 #if defined(__HIP_DEVICE_COMPILE__)
 // ---- lazy products for throughput builds: the rare folds of a group of independent products behind ONE wave-uniform branch ----
 // reduce128 begins with t = lo - hi_hi, whose borrow (lo < hi_hi < 2^32) random data sees about once in 2^32 products, and spends

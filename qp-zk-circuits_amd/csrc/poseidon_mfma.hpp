@@ -69,13 +69,12 @@ constexpr u32 G0 = (u32)small_g(0), G1 = (u32)small_g(1), G2 = (u32)small_g(2);
 static_assert(small_g(0) == 25 && small_g(1) < small_g(2) && small_g(2) < (1ull << 21), "group coefficients: the bound of reduce96_terms");
 
 // ---- pieces shared by the device code and the host emulation ----
-// v -> eight signed digits d_b in [-128, 127] packed in a u64 with sum d_b 256^b = v (mod p): the integer v if v + BIAS does not
-// wrap, else v - p (then v + BIAS + 2^32 - 1 wraps exactly once); digit = byte - 128, i.e. byte ^ 0x80 read as signed
-GL_HD u64 to_digits(u64 v) {
-    u64 t = v + DIGIT_BIAS;
-    t += (t < v) ? 0xFFFFFFFFull : 0ull;
-    return t ^ DIGIT_BIAS;
-}
+// v -> eight signed digits d_b in [-128, 127] packed in a u64: d_b = byte b of v, minus 128, i.e. byte ^ 0x80 read as signed. As
+// integers sum d_b 256^b = v - BIAS for EVERY 64-bit v: no carry, no wrap, no representative to choose. The gemm is linear, so
+// output row o comes out short of the constant BIAS sum_e w[o][e] over the elements whose digits are in; host::build_tables puts
+// that constant into the row's accumulator start (Rows::addc). Elements that are not known yet and the two pad elements keep the
+// literal digits 0 (not 0 ^ BIAS): their weights are zero.
+GL_HD u64 to_digits(u64 v) { return v ^ DIGIT_BIAS; }
 GL_HD u32 byte_perm(u32 s0, u32 s1, u32 sel) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_perm(s0, s1, sel);
@@ -177,6 +176,17 @@ inline bool fill_tiles(const Rows &rw, int steps, unsigned char *tiles, unsigned
         }
     return true;
 }
+// to_digits hands the gemm v - BIAS for every element whose digits are in: row o gets BIAS sum_e w[o][e] back through its additive
+// constant. A tile's rows carry weights only on elements that are known when the tile runs (the twelve state elements and the y
+// of the groups before it; all 34 in the final tiles) and zero on the rest, whose digits are the literal 0: the sum over all
+// columns is the sum over exactly the biased ones.
+inline void fold_digit_bias(Rows &rw) {
+    for (int o = 0; o < 4; o++) {
+        u64 sw = 0;
+        for (int e = 0; e < N_ELEM; e++) sw = fadd(sw, rw.w[o][e] % gl::P);
+        rw.addc[o] = fadd(rw.addc[o], fmul(DIGIT_BIAS % gl::P, sw));
+    }
+}
 // The partial-round block of a Poseidon-family permutation as the builder sees it: 22 rounds of `lane 0 <- (lane 0 + c_k)^7, state
 // <- M state`, entered with `pre t + cvec` (t = the S-box outputs of the full round before: that round's linear layer is `pre`)
 // and left with `+ after` (the constants of the full round behind).
@@ -220,6 +230,7 @@ inline bool build_tables(const Linear &L, unsigned char *tab) {
             for (int j = 0; j < 4 * g; j++) rw.w[o][12 + j] = G[k - 1 - j];
             rw.addc[o] = fadd(accv[k][0], L.rc[k][0] % gl::P);
         }
+        fold_digit_bias(rw);
         if (!fill_tiles(rw, group_steps(g), tab + (size_t)group_base(g) * 1024, tab + CINIT_OFF + g * 128)) return false;
     }
     for (int f = 0; f < N_FIN; f++) {
@@ -230,6 +241,7 @@ inline bool build_tables(const Linear &L, unsigned char *tab) {
             for (int j = 0; j < 22; j++) rw.w[o][12 + j] = Q[21 - j][i];
             rw.addc[o] = fadd(accv[22][i], L.after[i] % gl::P);
         }
+        fold_digit_bias(rw);
         if (!fill_tiles(rw, FIN_STEPS, tab + (size_t)(N_GROUP_TILES + f * FIN_STEPS) * 1024, tab + CINIT_OFF + (N_GROUP + f) * 128)) return false;
     }
     memcpy(tab + G_OFF, G, 3 * sizeof(u64));                  // the running group's coefficients (Poseidon: 25, 5 017, 1 259 209)

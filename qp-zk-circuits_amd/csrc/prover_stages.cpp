@@ -147,7 +147,8 @@ size_t stage_ring_words(const StageTables &t, uint32_t B) { return (size_t)B * (
 void stage_fill_betas(const CircuitPack &p, u64 *row, const u64 *betas, const u64 *gammas) {
     const SmallLayout sl(p);
     for (size_t k = 0; k < sl.nch; k++) {
-        row[sl.betas + k] = betas[k]; row[sl.gammas + k] = gammas[k];
+        // every entry canonical: quotient_perm_gates_kernel adds gamma_k with one carry fold (gl::add_canonical needs it)
+        row[sl.betas + k] = gl::canon(betas[k]); row[sl.gammas + k] = gl::canon(gammas[k]);
         for (size_t j = 0; j < sl.R; j++) row[sl.bk + k * sl.R + j] = gl::canon(gl::mul(betas[k], p.k_is[j]));
     }
 }

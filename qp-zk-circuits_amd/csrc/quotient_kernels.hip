@@ -357,7 +357,7 @@ constexpr u32 FUSED_CHUNK = 8;
 constexpr u32 FUSED_NONE = 0xFFFFFFFFu;
 
 template <int NCH>
-__global__ void __launch_bounds__(256, NCH <= 2 ? 4 : 2) quotient_perm_gates_kernel(QuotientArgs a, FusedGates fg, u32 tiles, u32 grouped, int finalize) {
+__global__ void __launch_bounds__(256, NCH <= 2 ? 4 : NCH == 3 ? 3 : 2) quotient_perm_gates_kernel(QuotientArgs a, FusedGates fg, u32 tiles, u32 grouped, int finalize) {
     const qmap::Place pl = qmap::place(blockIdx.x, tiles, a.batch, grouped != 0);
     if (!pl.valid) return;
     const u64 j = pl.tile * (u64)blockDim.x + threadIdx.x;
@@ -405,12 +405,23 @@ __global__ void __launch_bounds__(256, NCH <= 2 ? 4 : 2) quotient_perm_gates_ker
     // Arithmetic work past the last operation, behind chunk-uniform branches costs the two-challenge kernel 20 to 28 bytes of
     // scratch at four waves per SIMD: profiles/quotient_pass_notes.txt.)
     auto wire = [&](u32 r, u64 v, u64 sg, u64 (&pn)[NCH], u64 (&pd)[NCH]) {
+        // A factor is beta_k k_r x + (v + gamma_k), resp. beta_k sigma + (v + gamma_k): v + gamma_k once for both, and the 128-bit
+        // product takes it as a 64-bit addend before its ONE reduction (gl::mul_add, exact for any 64-bit operands; the table's
+        // beta_k k_r are canonical, stage_fill_betas) where a reduced product and two modular sums cost 29 vector instructions.
+        // gamma_k is canonical in the table (stage_fill_betas), so v + gamma_k needs one carry fold (gl::add_canonical).
+        if constexpr (NCH == 1) {
+            // one challenge: the reduced forms stay (the forms below cost this instantiation its fifth wave per SIMD: 102 registers for 96)
+            const u64 sid = gl::mul(a.beta_k_is[r], x);
+            const u64 ssg = gl::mul(a.betas[0], sg);
+            pn[0] = gl::mul(pn[0], gl::add(gl::add(v, sid), a.gammas[0]));
+            pd[0] = gl::mul(pd[0], gl::add(gl::add(v, ssg), a.gammas[0]));
+        } else {
 #pragma unroll
-        for (int k = 0; k < NCH; k++) {
-            const u64 sid = gl::mul(a.beta_k_is[k * R + r], x);
-            const u64 ssg = gl::mul(a.betas[k], sg);
-            pn[k] = gl::mul(pn[k], gl::add(gl::add(v, sid), a.gammas[k]));
-            pd[k] = gl::mul(pd[k], gl::add(gl::add(v, ssg), a.gammas[k]));
+            for (int k = 0; k < NCH; k++) {
+                const u64 vg = gl::add_canonical(v, a.gammas[k]);
+                pn[k] = gl::mul(pn[k], gl::mul_add(a.beta_k_is[k * R + r], x, vg));
+                pd[k] = gl::mul(pd[k], gl::mul_add(a.betas[k], sg, vg));
+            }
         }
         // BaseSumGate<2>: limb l on wire 1 + l, constraint 1 + l (the sum, wire 0, after the walk)
         const bool limb = r >= 1 && r <= n_limbs;

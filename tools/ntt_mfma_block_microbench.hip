@@ -27,6 +27,13 @@ __global__ void columns_kernel(u64 *m) {      // m[pos * 32 + j] = output pos of
 }
 
 struct Cinit { u32 c[8]; };
+// eight signed digits that sum to v mod p (the integer v, or v - p where v + BIAS wraps): this block has ONE accumulator start for
+// all its rows, so it keeps the carry form that pmf::to_digits had before the per-row constant took the bias
+__host__ __device__ inline u64 carry_digits(u64 v) {
+    u64 t = v + pmf::DIGIT_BIAS;
+    t += (t < v) ? 0xFFFFFFFFull : 0ull;
+    return t ^ pmf::DIGIT_BIAS;
+}
 // eight signed base-256 digits of the representative of w mod p in the balanced range (as pmf::host::const_digits)
 static bool balanced_digits(u64 w, signed char (&d)[8]) {
     w %= gl::P;
@@ -57,7 +64,7 @@ __global__ __launch_bounds__(256) void block_kernel(u64 *out, const uint4 *table
 #if defined(__HIP_DEVICE_COMPILE__)
         u32 Dlo[32], Dhi[32];
 #pragma unroll
-        for (int e = 0; e < 32; e++) { const u64 d = pmf::to_digits(x[e]); Dlo[e] = (u32)d; Dhi[e] = (u32)(d >> 32); }
+        for (int e = 0; e < 32; e++) { const u64 d = carry_digits(x[e]); Dlo[e] = (u32)d; Dhi[e] = (u32)(d >> 32); }
         pmf::v4i B0[STEPS], B1[STEPS];
 #pragma unroll
         for (int q = 0; q < STEPS; q++) {
