@@ -19,6 +19,7 @@
 #define QPGPU_VERIFY_H
 #include <stddef.h>
 #include <stdint.h>
+#include "qpgpu.h"      /* qpgpu_fri_params, qpgpu_fri_batch, qpgpu_challenger: the FRI verifier below */
 
 #ifdef __cplusplus
 extern "C" {
@@ -80,6 +81,63 @@ int qpgpu_verifier_verify_many_device(const qpgpu_verifier *v, struct qpgpu_ctx 
 #define QPGPU_VERIFY_HEAD_ON_DEVICE 1u
 int qpgpu_verifier_verify_many_device_ex(const qpgpu_verifier *v, struct qpgpu_ctx *ctx, const uint8_t *const *proofs, const size_t *lens,
                                          size_t count, unsigned threads, unsigned flags, int *results, char *reasons, char *err);
+
+/*
+ * fri::verifier::verify_fri_proof on its own: the counterpart of qpgpu.h's qpgpu_fri_prove and step entries for a caller who
+ * keeps the verifier's head (transcript, constraints at zeta) in its own code and hands over the rest, i.e. all the hashing of a
+ * verification. It does not depend on a circuit: an instance is the oracles' shapes, the opening batches and the FRI
+ * parameters. A qpgpu_fri_verifier is made once per instance and hasher, shared and thread-safe.
+ *
+ *   fri::verifier::verify_fri_proof   -> qpgpu_fri_verify, qpgpu_fri_verify_many_device
+ *   Challenger::fri_challenges        -> qpgpu_fri_verifier_challenges
+ */
+typedef struct { uint32_t num_polys; uint32_t blinded; } qpgpu_fri_oracle_shape;   /* blinded: rows end in 4 salt words, hashed, not opened */
+typedef struct {
+    uint32_t degree_bits;
+    uint32_t num_oracles;  const qpgpu_fri_oracle_shape *oracles;
+    uint32_t num_batches;  const qpgpu_fri_batch *batches;     /* ranges as in qpgpu_fri_prove; `point` is not read here */
+    qpgpu_fri_params params;
+} qpgpu_fri_instance;
+typedef struct qpgpu_fri_verifier qpgpu_fri_verifier;
+
+/* Validates what qpgpu_fri_prove validates, in its words under the prefix "fri_verifier_create:" (ranges inside their oracle,
+ * 1..8 ranges per batch, rounds of 1..8 bits, the schedule against degree and cap height, proof_of_work_bits <= 40, the LDE
+ * within 2^23), and takes at most 255 oracles. The verifier keeps a copy of the instance that owns its arrays. hasher_kind / params as qpgpu_verifier_create. */
+int    qpgpu_fri_verifier_create(const qpgpu_fri_instance *inst, int hasher_kind, const uint64_t *hasher_params, size_t n_params,
+                                 qpgpu_fri_verifier **out, char *err);
+void   qpgpu_fri_verifier_free(qpgpu_fri_verifier *v);
+size_t qpgpu_fri_verifier_proof_size(const qpgpu_fri_verifier *v);   /* == qpgpu_fri_proof_size for oracles of these shapes */
+size_t qpgpu_fri_verifier_num_openings(const qpgpu_fri_verifier *v); /* sum over batches and ranges of count */
+
+/* Challenger::fri_challenges, the order qpgpu_fri_prove uses: alpha = two draws; per round observe(cap), beta = two draws;
+ * observe(final polynomial); observe(nonce); one draw = the proof-of-work response; num_query_rounds draws mod the LDE size.
+ * Host only; *c (the transcript after the openings were observed) is advanced in place. betas: [rounds][2]; indices:
+ * [num_query_rounds]. A caller with other transcript rules computes the four itself. */
+int qpgpu_fri_verifier_challenges(const qpgpu_fri_verifier *v, qpgpu_challenger *c, const uint8_t *proof, size_t len,
+                                  uint64_t alpha[2], uint64_t *betas, uint64_t *pow_response, uint64_t *indices, char *err);
+
+/* verify_fri_proof for one proof, on the host. caps: [num_oracles] pointers to 4 << cap_height words; points: [num_batches][2];
+ * openings: [num_openings][2], batch by batch, range by range. Returns 0, or QPGPU_EVERIFY with the first failing check in err,
+ * in this order: length; a non-canonical element anywhere in the proof; the proof-of-work response (leading zero bits); then
+ * per query round the checks and texts of qpgpu_verifier_verify's query rounds. What the caller itself supplies is not judged:
+ * a non-canonical cap word, point, opening or challenge, or an index >= the LDE size, is QPGPU_EINVAL. Thread-safe. */
+int qpgpu_fri_verify(const qpgpu_fri_verifier *v, const uint64_t *const *caps, const uint64_t *points, const uint64_t *openings,
+                     const uint64_t alpha[2], const uint64_t *betas, uint64_t pow_response, const uint64_t *indices,
+                     const uint8_t *proof, size_t len, char *err);
+
+/* The same for `count` proofs with the query rounds on ctx's GPU. cap_counts[o]: 1 = caps[o] holds one cap shared by all proofs,
+ * count = one cap per proof, back to back; anything else is QPGPU_EINVAL naming the oracle. points: [num_batches][count][2];
+ * openings [count][num_openings][2]; alphas [count][2]; betas [count][rounds][2]; pow_responses [count]; indices
+ * [count][num_query_rounds]. results[i], reasons row i (QPGPU_VERIFY_ERR_CAP bytes, "" when accepted; reasons may be NULL), the
+ * return value and err ("proof i: ...") are what `count` calls of qpgpu_fri_verify give. The verifier's hasher must equal the
+ * context's, else QPGPU_EINVAL. count == 0 returns 0. A HIP error returns QPGPU_EDEVICE and the proofs not decided by then get
+ * QPGPU_EDEVICE (no host fallback). Synchronous on the ctx stream. Instances of more than 16 oracles, 16 rounds or 8 batches
+ * are QPGPU_EINVAL here (the host entry takes them). */
+int qpgpu_fri_verify_many_device(const qpgpu_fri_verifier *v, struct qpgpu_ctx *ctx, size_t count,
+                                 const uint64_t *const *caps, const uint32_t *cap_counts,
+                                 const uint64_t *points, const uint64_t *openings,
+                                 const uint64_t *alphas, const uint64_t *betas, const uint64_t *pow_responses, const uint64_t *indices,
+                                 const uint8_t *const *proofs, const size_t *lens, int *results, char *reasons, char *err);
 
 #ifdef __cplusplus
 }

@@ -152,6 +152,25 @@ extern "C" {
     // the same with flags: 1 (QPGPU_VERIFY_HEAD_ON_DEVICE) runs the transcript, proof of work and quotient identity on the GPU too
     pub fn qpgpu_verifier_verify_many_device_ex(v: *const QpgpuVerifier, ctx: *mut QpgpuCtx, proofs: *const *const u8, lens: *const usize, count: usize,
                                                 threads: u32, flags: u32, results: *mut i32, reasons: *mut c_char, err: *mut c_char) -> i32;
+    // include/qpgpu_verify.h — fri::verifier::verify_fri_proof on its own, the counterpart of qpgpu_fri_prove: the Rust side keeps its
+    // verifier head (transcript, gates at zeta) and hands over all the hashing of a verification. An instance is the oracles' shapes,
+    // the opening batches and the FRI parameters; no circuit pack is involved. caps: [num_oracles] pointers; points [num_batches][2];
+    // openings [num_openings][2], batch by batch, range by range. _many_device: arrays [count][..] (points [num_batches][count][2]),
+    // cap_counts[o] 1 (shared) or count; results / reasons (count * 200 bytes or null) / err as `count` calls of qpgpu_fri_verify.
+    pub fn qpgpu_fri_verifier_create(inst: *const QpgpuFriInstance, hasher_kind: i32, hasher_params: *const u64, n_params: usize,
+                                     out: *mut *mut QpgpuFriVerifier, err: *mut c_char) -> i32;
+    pub fn qpgpu_fri_verifier_free(v: *mut QpgpuFriVerifier);
+    pub fn qpgpu_fri_verifier_proof_size(v: *const QpgpuFriVerifier) -> usize;
+    pub fn qpgpu_fri_verifier_num_openings(v: *const QpgpuFriVerifier) -> usize;
+    // Challenger::fri_challenges; *c is advanced in place. betas [rounds][2], indices [num_query_rounds]
+    pub fn qpgpu_fri_verifier_challenges(v: *const QpgpuFriVerifier, c: *mut QpgpuChallenger, proof: *const u8, len: usize, alpha: *mut u64,
+                                         betas: *mut u64, pow_response: *mut u64, indices: *mut u64, err: *mut c_char) -> i32;
+    pub fn qpgpu_fri_verify(v: *const QpgpuFriVerifier, caps: *const *const u64, points: *const u64, openings: *const u64, alpha: *const u64,
+                            betas: *const u64, pow_response: u64, indices: *const u64, proof: *const u8, len: usize, err: *mut c_char) -> i32;
+    pub fn qpgpu_fri_verify_many_device(v: *const QpgpuFriVerifier, ctx: *mut QpgpuCtx, count: usize, caps: *const *const u64,
+                                        cap_counts: *const u32, points: *const u64, openings: *const u64, alphas: *const u64, betas: *const u64,
+                                        pow_responses: *const u64, indices: *const u64, proofs: *const *const u8, lens: *const usize,
+                                        results: *mut i32, reasons: *mut c_char, err: *mut c_char) -> i32;
     // include/qpgpu.h — the proving pool over one GPU or several: one queue, a worker set per device,
     // proofs written into the caller's host buffers
     pub fn qpgpu_pool_create_multi(devices: *const i32, n_devices: u32, pack: *const u64, n_words: usize, workers_per_device: u32,
@@ -260,6 +279,10 @@ pub const QPGPU_LEVEL_LEAF: i32 = 0;
 pub const QPGPU_LEVEL_PRIVATE_BATCH: i32 = 1;
 pub const QPGPU_LEVEL_PUBLIC_BATCH: i32 = 2;
 #[repr(C)] pub struct QpgpuVerifier { _private: [u8; 0] }
+#[repr(C)] pub struct QpgpuFriVerifier { _private: [u8; 0] }
+#[repr(C)] pub struct QpgpuFriOracleShape { pub num_polys: u32, pub blinded: u32 }
+#[repr(C)] pub struct QpgpuFriInstance { pub degree_bits: u32, pub num_oracles: u32, pub oracles: *const QpgpuFriOracleShape,
+                                         pub num_batches: u32, pub batches: *const QpgpuFriBatch, pub params: QpgpuFriParams }
 #[repr(C)] pub struct QpgpuPool { _private: [u8; 0] }
 pub const QPGPU_POOL_HOST_WITNESS: u32 = 1;
 

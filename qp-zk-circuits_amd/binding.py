@@ -49,6 +49,13 @@ def load_library():
         "qpgpu_verifier_verify_many": (c.c_int, [vp, vp, vp, c.c_size_t, c.c_uint, vp, c.c_char_p]),
         "qpgpu_verifier_verify_many_device": (c.c_int, [vp, vp, vp, vp, c.c_size_t, c.c_uint, vp, vp, c.c_char_p]),
         "qpgpu_verifier_verify_many_device_ex": (c.c_int, [vp, vp, vp, vp, c.c_size_t, c.c_uint, c.c_uint, vp, vp, c.c_char_p]),
+        "qpgpu_fri_verifier_create": (c.c_int, [vp, c.c_int, vp, c.c_size_t, c.POINTER(vp), c.c_char_p]),
+        "qpgpu_fri_verifier_free": (None, [vp]),
+        "qpgpu_fri_verifier_proof_size": (c.c_size_t, [vp]),
+        "qpgpu_fri_verifier_num_openings": (c.c_size_t, [vp]),
+        "qpgpu_fri_verifier_challenges": (c.c_int, [vp, vp, c.c_char_p, c.c_size_t, u64p, u64p, c.POINTER(c.c_uint64), u64p, c.c_char_p]),
+        "qpgpu_fri_verify": (c.c_int, [vp, vp, u64p, u64p, u64p, u64p, c.c_uint64, u64p, c.c_char_p, c.c_size_t, c.c_char_p]),
+        "qpgpu_fri_verify_many_device": (c.c_int, [vp, vp, c.c_size_t, vp, vp, u64p, u64p, u64p, u64p, u64p, u64p, vp, vp, vp, vp, c.c_char_p]),
         "qpgpu_ctx_create": (c.c_int, [c.c_int, c.POINTER(vp)]),
         "qpgpu_ctx_destroy": (None, [vp]),
         "qpgpu_last_error": (c.c_char_p, [vp]),
@@ -1173,6 +1180,127 @@ class FriSession:
         self.gpu._check(self.gpu.lib.qpgpu_fri_open(self.h, idx.ctypes.data if idx.size else None, idx.size, out.ctypes.data,
                                                     idx.size * self.query_size, ctypes.byref(ln)))
         return out[:ln.value].tobytes()
+
+
+class _FriOracleShape(ctypes.Structure):
+    _fields_ = [("num_polys", ctypes.c_uint32), ("blinded", ctypes.c_uint32)]
+
+
+class _FriInstance(ctypes.Structure):
+    _fields_ = [("degree_bits", ctypes.c_uint32), ("num_oracles", ctypes.c_uint32), ("oracles", ctypes.POINTER(_FriOracleShape)),
+                ("num_batches", ctypes.c_uint32), ("batches", ctypes.POINTER(_FriBatch)), ("params", _FriParams)]
+
+
+class FriVerifier:
+    """qpgpu_fri_verifier (include/qpgpu_verify.h): fri::verifier::verify_fri_proof for the proofs fri_prove / FriSession make.
+    oracles: [(num_polys, blinded), ...]; batches: one list of (oracle, first, count) per opening point, as fri_prove's without
+    the points. hasher / params as Verifier's. Host only except verify_many(gpu=...)."""
+
+    def __init__(self, degree_bits, oracles, batches, reduction_arity_bits, rate_bits=3, cap_height=4, proof_of_work_bits=16,
+                 num_query_rounds=28, hasher=0, params=None):
+        self.lib = load_library()
+        shapes = (_FriOracleShape * max(1, len(oracles)))(*[_FriOracleShape(int(n), int(bool(b))) for n, b in oracles])
+        _, bs, prm = _fri_args([], [((0, 0), r) for r in batches], reduction_arity_bits, rate_bits, cap_height, proof_of_work_bits,
+                               num_query_rounds)
+        inst = _FriInstance(degree_bits, len(oracles), shapes, len(batches), bs, prm)
+        pr = None if params is None else np.ascontiguousarray(params, dtype=np.uint64)
+        h = ctypes.c_void_p(); err = ctypes.create_string_buffer(200)
+        rc = self.lib.qpgpu_fri_verifier_create(ctypes.byref(inst), hasher, None if pr is None else pr.ctypes.data,
+                                                0 if pr is None else pr.size, ctypes.byref(h), err)
+        if rc:
+            raise QpGpuError(rc, err.value.decode())
+        self.h = h
+        self.num_oracles, self.num_batches, self.num_rounds = len(oracles), len(batches), len(reduction_arity_bits)
+        self.num_queries, self.cap_words = num_query_rounds, 4 << cap_height
+        self.reason, self.code = "", 0
+
+    def close(self):
+        if self.h:
+            self.lib.qpgpu_fri_verifier_free(self.h); self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def proof_size(self):
+        return int(self.lib.qpgpu_fri_verifier_proof_size(self.h))
+
+    def num_openings(self):
+        return int(self.lib.qpgpu_fri_verifier_num_openings(self.h))
+
+    def challenges(self, challenger, proof):
+        """Challenger::fri_challenges: (alpha (a, b), betas [(a, b)], proof-of-work response, query indices); `challenger`
+        (the transcript after the openings) is advanced in place, under the verifier's hasher."""
+        b = bytes(proof)
+        alpha = np.zeros(2, dtype=np.uint64); betas = np.zeros((max(1, self.num_rounds), 2), dtype=np.uint64)
+        idx = np.zeros(self.num_queries, dtype=np.uint64); powr = ctypes.c_uint64(); err = ctypes.create_string_buffer(200)
+        rc = self.lib.qpgpu_fri_verifier_challenges(self.h, ctypes.byref(challenger.state), b, len(b), alpha.ctypes.data, betas.ctypes.data,
+                                                    ctypes.byref(powr), idx.ctypes.data, err)
+        if rc:
+            raise QpGpuError(rc, err.value.decode())
+        return ((int(alpha[0]), int(alpha[1])), [(int(x[0]), int(x[1])) for x in betas[:self.num_rounds]], int(powr.value),
+                [int(x) for x in idx])
+
+    @staticmethod
+    def _words(x, shape):
+        return np.ascontiguousarray(np.array(x, dtype=np.uint64).reshape(shape))
+
+    def verify(self, caps, points, openings, alpha, betas, pow_response, indices, proof):
+        """qpgpu_fri_verify. caps: one array of 4 << cap_height words per oracle; points: [(a, b)] per batch; openings:
+        [num_openings, 2]. True when accepted; else False with .code (-6 rejected, -1 the caller's own values refused) and
+        .reason."""
+        keep = [self._words(cp, -1) for cp in caps]
+        assert len(keep) == self.num_oracles and all(k.size == self.cap_words for k in keep)
+        cptr = (ctypes.c_void_p * max(1, len(keep)))(*[k.ctypes.data for k in keep])
+        pts, ops = self._words(points, (self.num_batches, 2)), self._words(openings, (self.num_openings(), 2))
+        a, bt = self._words(alpha, 2), self._words(betas if self.num_rounds else [0, 0], (max(1, self.num_rounds), 2))
+        idx = self._words(indices, self.num_queries)
+        b = bytes(proof); err = ctypes.create_string_buffer(200)
+        self.code = self.lib.qpgpu_fri_verify(self.h, cptr, pts.ctypes.data, ops.ctypes.data, a.ctypes.data, bt.ctypes.data, int(pow_response),
+                                              idx.ctypes.data, b, len(b), err)
+        self.reason = err.value.decode()
+        return self.code == 0
+
+    def verify_many(self, caps, points, openings, alphas, betas, pow_responses, indices, proofs, gpu=None, cap_counts=None):
+        """qpgpu_fri_verify_many_device on gpu's device (gpu=None: one qpgpu_fri_verify per proof on the host). caps: per oracle
+        [cap_words] (shared by all proofs) or [count, cap_words]; points [num_batches, count, 2]; openings [count, num_openings, 2];
+        alphas [count, 2]; betas [count, rounds, 2]; pow_responses [count]; indices [count, num_queries]. Returns [accepted?];
+        .results the codes, .reasons the texts ("" when accepted), .code / .reason the call's."""
+        n = len(proofs)
+        keep = [self._words(cp, -1) for cp in caps]
+        counts = list(cap_counts) if cap_counts is not None else [k.size // self.cap_words for k in keep]
+        pts = self._words(points, (self.num_batches, n, 2)) if n else np.zeros(2, dtype=np.uint64)
+        ops = self._words(openings, (n, self.num_openings(), 2)) if n else np.zeros(2, dtype=np.uint64)
+        al = self._words(alphas, (n, 2)) if n else np.zeros(2, dtype=np.uint64)
+        bt = self._words(betas, (n, self.num_rounds, 2)) if n and self.num_rounds else np.zeros(2, dtype=np.uint64)
+        pw = self._words(pow_responses, n) if n else np.zeros(1, dtype=np.uint64)
+        idx = self._words(indices, (n, self.num_queries)) if n else np.zeros(1, dtype=np.uint64)
+        if gpu is None:
+            self.results, self.reasons = [], []
+            for i in range(n):
+                own = [k.reshape(-1, self.cap_words)[i if c != 1 else 0] for k, c in zip(keep, counts)]
+                self.verify(own, pts[:, i], ops[i], al[i], bt[i] if self.num_rounds else None, int(pw[i]), idx[i], proofs[i])
+                self.results.append(self.code); self.reasons.append(self.reason)
+            bad = [i for i, r in enumerate(self.results) if r]
+            self.code = self.results[bad[0]] if bad else 0
+            self.reason = "proof %d: %s" % (bad[0], self.reasons[bad[0]]) if bad else ""
+            return [r == 0 for r in self.results]
+        bufs = [bytes(p) for p in proofs]
+        ptrs = (ctypes.c_char_p * max(1, n))(*bufs)
+        lens = (ctypes.c_size_t * max(1, n))(*[len(b) for b in bufs])
+        cptr = (ctypes.c_void_p * max(1, len(keep)))(*[k.ctypes.data for k in keep])
+        cc = (ctypes.c_uint32 * max(1, len(keep)))(*counts)
+        res = (ctypes.c_int * max(1, n))()
+        rows = ctypes.create_string_buffer(200 * max(1, n)); err = ctypes.create_string_buffer(200)
+        self.code = self.lib.qpgpu_fri_verify_many_device(self.h, gpu.ctx, n, cptr, cc, pts.ctypes.data, ops.ctypes.data, al.ctypes.data,
+                                                          bt.ctypes.data, pw.ctypes.data, idx.ctypes.data, ptrs, lens, res, rows, err)
+        self.reason = err.value.decode()
+        raw = rows.raw
+        self.reasons = [raw[200 * i:200 * (i + 1)].split(b"\0", 1)[0].decode() for i in range(n)]
+        self.results = list(res)[:n]
+        return [r == 0 for r in self.results]
 
 
 class ProvingPool:

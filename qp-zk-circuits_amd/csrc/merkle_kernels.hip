@@ -26,6 +26,7 @@ hipError_t merkle_tp_nodes(const u64 *in, u64 *out, u64 n_out, u32 batch, u64 ps
 hipError_t merkle_tp_pow(const PowArgs &a, dim3 g, const HasherDev &h, hipStream_t st);
 hipError_t verify_upload_constants(const u64 *rc360);   // verify_kernels.hip
 hipError_t verify_head_upload_constants(const u64 *rc360);   // verify_head_kernels.hip
+hipError_t fri_verify_upload_constants(const u64 *rc360);    // fri_verify_kernels.hip
 // matrix-pipe build (merkle_kernels_mx.hip)
 hipError_t merkle_mx_upload_constants(const u64 *rc360);
 hipError_t merkle_mx_leaves(const MerkleLeafArgs &a, u64 total, const HasherDev &h, hipStream_t st);
@@ -73,6 +74,7 @@ hipError_t merkle_upload_constants(const u64 *rc360) {
     if (e == hipSuccess) e = merkle_tp_upload_constants(rc360);
     if (e == hipSuccess) e = verify_upload_constants(rc360);     // the batch verifier's units (verify_kernels.hip, verify_head_kernels.hip)
     if (e == hipSuccess) e = verify_head_upload_constants(rc360);
+    if (e == hipSuccess) e = fri_verify_upload_constants(rc360);
     if (e != hipSuccess || !mx_enabled()) return e;       // QPGPU_MX=0: no matrix build, no table, no device self-test
     return merkle_mx_upload_constants(rc360);
 }

@@ -34,6 +34,27 @@ int verify::fail(char *err, int code, const char *fmt, ...) {
 }
 using verify::fail;
 
+int verify::parse_hasher(int hasher_kind, const uint64_t *hasher_params, size_t n_params, hasher::Config &out, char *err) {
+    if (hasher_kind == hasher::POSEIDON) { out.kind = hasher::POSEIDON; return QPGPU_OK; }
+    if (hasher_kind != hasher::POSEIDON2) return fail(err, QPGPU_EINVAL, "unknown hasher kind");
+    out.kind = hasher::POSEIDON2;
+    if (!hasher_params && n_params == 0) { out.p2 = poseidon2::qp_params(); return QPGPU_OK; }
+    if (!hasher_params || n_params != (size_t)poseidon2::PARAM_WORDS) return fail(err, QPGPU_EINVAL, "bad Poseidon2 parameter block");
+    for (size_t i = 0; i < n_params; i++) if (hasher_params[i] >= gl::P) return fail(err, QPGPU_EINVAL, "Poseidon2 parameter %zu is not canonical", i);
+    std::memcpy(out.p2.rc_ext, hasher_params, 96 * 8);
+    std::memcpy(out.p2.rc_int, hasher_params + 96, 22 * 8);
+    std::memcpy(out.p2.diag_m1, hasher_params + 118, 12 * 8);
+    std::memcpy(out.p2.m4, hasher_params + 130, 16 * 8);
+    return QPGPU_OK;
+}
+
+bool verify::same_hasher(const hasher::Config &a, const hasher::Config &b) {
+    if (a.kind != b.kind) return false;
+    if (a.kind != hasher::POSEIDON2) return true;
+    return memcmp(a.p2.rc_ext, b.p2.rc_ext, sizeof a.p2.rc_ext) == 0 && memcmp(a.p2.rc_int, b.p2.rc_int, sizeof a.p2.rc_int) == 0 &&
+           memcmp(a.p2.diag_m1, b.p2.diag_m1, sizeof a.p2.diag_m1) == 0 && memcmp(a.p2.m4, b.p2.m4, sizeof a.p2.m4) == 0;
+}
+
 namespace {
 
 // ---- extension-field shorthands (F[x]/(x^2 - 7)) ----
@@ -85,6 +106,143 @@ using vmath::gate_constraints;
 }  // namespace
 
 namespace {
+bool path_ok(const Hash &H, const u64 *leaf, size_t width, size_t index, const u64 *path, size_t plen, const u64 *cap) {
+    u64 cur[4], nxt[4];
+    H.leaf(leaf, width, cur);
+    for (size_t i = 0; i < plen; i++) {
+        if (index & 1) H.two_to_one(path + 4 * i, cur, nxt); else H.two_to_one(cur, path + 4 * i, nxt);
+        std::memcpy(cur, nxt, 32);
+        index >>= 1;
+    }
+    return std::memcmp(cur, cap + 4 * index, 32) == 0;
+}
+}  // namespace
+
+// ---- the query rounds of any FRI instance (fri_verify.hpp): verify_impl below and qpgpu_fri_verify (fri_verify.cpp) ----
+namespace friv {
+
+void reduced_openings(const Instance &in, const e2 *openings, e2 alpha, e2 *out) {
+    for (size_t b = 0; b < in.batches.size(); b++) {
+        const size_t n = in.batch_count(b);
+        e2 red = E(0);
+        for (size_t j = n; j-- > 0;) red = red * alpha + openings[j];
+        out[b] = red;
+        openings += n;
+    }
+}
+
+void query_reason(char *out, size_t qi, uint32_t code) {
+    const unsigned kind = code >> 8, at = code & 0xff;
+    switch (kind) {
+    case VQ_ORACLE_PLEN: fail(out, 0, "query %zu: Merkle path length of oracle %d out of range", qi, (int)at); break;
+    case VQ_ORACLE_PATH: fail(out, 0, "query %zu: Merkle path of initial oracle %d does not lead to its cap", qi, (int)at); break;
+    case VQ_ROUND_PLEN: fail(out, 0, "query %zu: Merkle path length of FRI round %zu out of range", qi, (size_t)at); break;
+    case VQ_ROUND_CONT: fail(out, 0, "query %zu: FRI round %zu does not continue the previous evaluation", qi, (size_t)at); break;
+    case VQ_ROUND_PATH: fail(out, 0, "query %zu: Merkle path of FRI round %zu does not lead to its cap", qi, (size_t)at); break;
+    default: fail(out, 0, "query %zu: the final polynomial does not match the last FRI round", qi); break;
+    }
+}
+
+// A query round has one layout (proof_layout::Fri): a path-length byte that differs from the layout's is a verdict, never a
+// length, so every read is at a fixed offset inside the round.
+uint32_t query_rounds(const hasher::Config &h, const Instance &in, const QueryInput &q, const uint8_t *queries, size_t *query) {
+    const Hash H{&h};
+    const proof_layout::Fri &lay = in.lay;
+    const proof_layout::Opening *op = lay.op.data();     // the initial oracles, then the FRI rounds
+    const size_t n_oracles = in.widths.size(), n_rounds = in.arity_bits.size(), n_batches = in.batches.size(), cap_words = in.cap_words();
+    const unsigned L = in.degree_bits + in.rate_bits;
+    std::vector<size_t> row_at(n_oracles);
+    size_t row_words = 0;
+    for (size_t o = 0; o < n_oracles; o++) { row_at[o] = row_words; row_words += in.widths[o]; }
+    std::vector<u64> row(row_words + 1), path(64 * 4), ev(2 << 8);
+    std::vector<e2> shift(n_batches);                    // ReducingFactor::shift of a batch: alpha^(its polynomials)
+    for (size_t b = 0; b < n_batches; b++) shift[b] = gl::e2_pow(q.alpha, in.batch_count(b));
+    const u64 w_lde = gl::root_of_unity(L);
+    auto words = [](u64 *out, const uint8_t *p, size_t n) { std::memcpy(out, p, 8 * n); };
+    for (size_t qi = 0; qi < lay.num_query_rounds; qi++) {
+        *query = qi;
+        const uint8_t *base = queries + qi * lay.round_bytes;
+        size_t x_index = (size_t)q.indices[qi];
+        for (size_t o = 0; o < n_oracles; o++) {
+            u64 *r = row.data() + row_at[o];
+            const uint8_t *at = base + op[o].off;
+            words(r, at, in.widths[o]);
+            const size_t plen = at[8 * in.widths[o]];
+            if (plen > 60) return VQ_ORACLE_PLEN << 8 | (uint32_t)o;
+            if (plen != op[o].path_len) return VQ_ORACLE_PATH << 8 | (uint32_t)o;
+            words(path.data(), at + 8 * in.widths[o] + 1, plen * 4);
+            if (!path_ok(H, r, in.widths[o], x_index, path.data(), plen, q.caps[o])) return VQ_ORACLE_PATH << 8 | (uint32_t)o;
+        }
+        u64 subgroup_x = gl::mul(gl::MULT_GEN, gl::pow(w_lde, bitrev((uint32_t)x_index, L)));
+        const e2 sx = E(subgroup_x);
+        e2 sum = E(0);                                   // fri_combine_initial: salts are not opened
+        for (size_t b = 0; b < n_batches; b++) {
+            e2 e = E(0);
+            const std::vector<Range> &rg = in.batches[b];
+            for (size_t k = rg.size(); k-- > 0;) {
+                const u64 *r = row.data() + row_at[rg[k].oracle] + rg[k].first;
+                for (size_t j = rg[k].count; j-- > 0;) e = e * q.alpha + E(r[j]);
+            }
+            sum = sum * shift[b] + (e - q.reduced[b]) * gl::e2_inv(sx - q.points[b]);
+        }
+        e2 old_eval = sum;
+        for (size_t r = 0; r < n_rounds; r++) {
+            const unsigned ab = (unsigned)in.arity_bits[r];
+            const size_t arity = (size_t)1 << ab;
+            const uint8_t *at = base + op[n_oracles + r].off;
+            words(ev.data(), at, 2 * arity);
+            const size_t plen = at[16 * arity];
+            if (plen > 60) return VQ_ROUND_PLEN << 8 | (uint32_t)r;
+            const size_t coset_index = x_index >> ab, within = x_index & (arity - 1);
+            if (!same(gl::e2_make(ev[2 * within], ev[2 * within + 1]), old_eval)) return VQ_ROUND_CONT << 8 | (uint32_t)r;
+            if (plen != op[n_oracles + r].path_len) return VQ_ROUND_PATH << 8 | (uint32_t)r;
+            words(path.data(), at + 16 * arity + 1, plen * 4);
+            if (!path_ok(H, ev.data(), 2 * arity, coset_index, path.data(), plen, q.round_caps + r * cap_words)) return VQ_ROUND_PATH << 8 | (uint32_t)r;
+            // compute_evaluation: interpolate the coset's 2^ab evaluations and evaluate at beta
+            const u64 g = gl::root_of_unity(ab);
+            const size_t rev_within = bitrev((uint32_t)within, ab);
+            const u64 coset_start = gl::mul(subgroup_x, gl::pow(g, arity - rev_within));
+            std::vector<u64> px(arity); std::vector<e2> py(arity);
+            for (size_t i = 0; i < arity; i++) {
+                const size_t src = bitrev((uint32_t)i, ab);
+                py[i] = gl::e2_make(ev[2 * src], ev[2 * src + 1]);
+                px[i] = gl::mul(coset_start, gl::pow(g, i));
+            }
+            const e2 beta = q.betas[r];
+            e2 acc = E(0);
+            if (ab <= 5) {
+                for (size_t i = 0; i < arity; i++) {      // Lagrange form
+                    e2 num = E(1); u64 den = 1;
+                    for (size_t j = 0; j < arity; j++) if (j != i) { num = num * (beta - E(px[j])); den = gl::mul(den, gl::sub(px[i], px[j])); }
+                    acc = acc + py[i] * scale(num, gl::inv(den));
+                }
+            } else {
+                // the same value in barycentric form (the points are a coset of the 2^ab-th roots of unity): beyond arity 32 the
+                // quadratic Lagrange loop is 2^16 multiplications per round and query
+                //   p(beta) = (beta^n - s^n) / (n s^n) * sum_i y_i x_i / (beta - x_i)
+                const u64 s_n = gl::pow(coset_start, arity);
+                bool hit = false;
+                for (size_t i = 0; i < arity && !hit; i++) if (same(beta, E(px[i]))) { acc = py[i]; hit = true; }
+                if (!hit) {
+                    for (size_t i = 0; i < arity; i++) acc = acc + scale(py[i], px[i]) * gl::e2_inv(beta - E(px[i]));
+                    acc = scale(acc * (gl::e2_pow(beta, arity) - E(s_n)), gl::inv(gl::mul(s_n, (u64)arity)));
+                }
+            }
+            old_eval = acc;
+            subgroup_x = gl::pow(subgroup_x, arity);
+            x_index = coset_index;
+        }
+        e2 fe = E(0);
+        const e2 sxe = E(subgroup_x);
+        for (size_t i = lay.final_len; i-- > 0;) fe = fe * sxe + q.final_poly[i];
+        if (!same(fe, old_eval)) return VQ_FINAL << 8;
+    }
+    return 0;
+}
+
+}  // namespace friv
+
+namespace {
 
 // constants/sigmas cap from the pack: per column values -> coefficients -> coset LDE in leaf order; leaves hashed, tree to the cap
 void host_cs_cap(const CircuitPack &p, const Hash &H, std::vector<u64> &cap) {
@@ -117,18 +275,6 @@ void host_cs_cap(const CircuitPack &p, const Hash &H, std::vector<u64> &cap) {
 using proof_layout::Reader;
 void read_exts(Reader &b, std::vector<e2> &v, size_t n) { v.resize(n); b.vec((u64 *)v.data(), 2 * n); }
 
-bool path_ok(const Hash &H, const u64 *leaf, size_t width, size_t index, const u64 *path, size_t plen, const u64 *cap, size_t layout_plen) {
-    if (plen != layout_plen) return false;
-    u64 cur[4], nxt[4];
-    H.leaf(leaf, width, cur);
-    for (size_t i = 0; i < plen; i++) {
-        if (index & 1) H.two_to_one(path + 4 * i, cur, nxt); else H.two_to_one(cur, path + 4 * i, nxt);
-        std::memcpy(cur, nxt, 32);
-        index >>= 1;
-    }
-    return std::memcmp(cur, cap + 4 * index, 32) == 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -140,18 +286,7 @@ int qpgpu_verifier_create(const uint64_t *pack_words, size_t n_words, const uint
     if (!v) return fail(err, QPGPU_ENOMEM, "out of memory");
     const std::string why = v->pack.parse(pack_words, n_words);
     if (!why.empty()) { delete v; return fail(err, QPGPU_EINVAL, "circuit pack: %s", why.c_str()); }
-    if (hasher_kind == hasher::POSEIDON) v->hash.kind = hasher::POSEIDON;
-    else if (hasher_kind == hasher::POSEIDON2) {
-        v->hash.kind = hasher::POSEIDON2;
-        if (!hasher_params && n_params == 0) v->hash.p2 = poseidon2::qp_params();
-        else if (hasher_params && n_params == (size_t)poseidon2::PARAM_WORDS) {
-            for (size_t i = 0; i < n_params; i++) if (hasher_params[i] >= gl::P) { delete v; return fail(err, QPGPU_EINVAL, "Poseidon2 parameter %zu is not canonical", i); }
-            std::memcpy(v->hash.p2.rc_ext, hasher_params, 96 * 8);
-            std::memcpy(v->hash.p2.rc_int, hasher_params + 96, 22 * 8);
-            std::memcpy(v->hash.p2.diag_m1, hasher_params + 118, 12 * 8);
-            std::memcpy(v->hash.p2.m4, hasher_params + 130, 16 * 8);
-        } else { delete v; return fail(err, QPGPU_EINVAL, "bad Poseidon2 parameter block"); }
-    } else { delete v; return fail(err, QPGPU_EINVAL, "unknown hasher kind"); }
+    if (int rc = verify::parse_hasher(hasher_kind, hasher_params, n_params, v->hash, err)) { delete v; return rc; }
     const CircuitPack &p = v->pack;
     if (p.num_challenges > 4 || p.arity_bits.size() > 16) { delete v; return fail(err, QPGPU_EINVAL, "circuit outside the supported range"); }
     for (u64 ab : p.arity_bits) if (ab == 0 || ab > 5) { delete v; return fail(err, QPGPU_EINVAL, "FRI arity outside 2..32"); }
@@ -172,6 +307,18 @@ int qpgpu_verifier_create(const uint64_t *pack_words, size_t n_words, const uint
         host_cs_cap(p, H, v->cs_cap);
     }
     v->layout = proof_layout::of(p);
+    {   // the FRI part as fri::verifier sees it: batch 0 opens every polynomial at zeta, batch 1 the Zs at g zeta
+        friv::Instance &f = v->fri;
+        f.degree_bits = (unsigned)p.degree_bits; f.rate_bits = (unsigned)p.rate_bits; f.cap_height = (unsigned)p.cap_height;
+        f.pow_bits = (unsigned)p.proof_of_work_bits;
+        f.widths.assign(v->layout.widths, v->layout.widths + 4);
+        f.polys.assign(v->layout.polys, v->layout.polys + 4);
+        f.arity_bits = p.arity_bits;
+        f.batches.resize(2);
+        for (uint32_t o = 0; o < 4; o++) f.batches[0].push_back({o, 0, (uint32_t)f.polys[o]});
+        f.batches[1].push_back({2, 0, (uint32_t)p.num_challenges});
+        f.lay = v->layout.fri;
+    }
     {   // the consistency check vanishing_at_zeta makes of the gate table does not read the openings: asked once, on zeros, for
         // the device head (verify_device.cpp), which reports it where verify_head does
         const size_t nch = p.num_challenges;
@@ -302,84 +449,17 @@ static int verify_impl(const qpgpu_verifier *v, const uint8_t *proof, size_t len
     const int head = verify_head(v, proof, len, err, h);
     if (head != QPGPU_OK) return head;
     if (indices_out) { for (size_t qi = 0; qi < h.x_indices.size(); qi++) indices_out[qi] = h.x_indices[qi]; return QPGPU_OK; }
-    const CircuitPack &c = v->pack;
-    const Hash H{&v->hash};
-    const proof_layout::Proof &lay = v->layout;
-    const size_t *widths = lay.widths, *polys = lay.polys;
-    const proof_layout::Opening *op = lay.fri.op.data();     // the four initial oracles, then the FRI rounds
-    const unsigned L = (unsigned)(c.degree_bits + c.rate_bits);
-    const size_t nch = c.num_challenges, cap_words = lay.cap_bytes / 8, n_rounds = c.arity_bits.size();
-    const std::vector<size_t> &x_indices = h.x_indices;
-    const std::vector<u64> &fri_caps = h.fri_caps;
-    const std::vector<e2> &fri_betas = h.fri_betas, &final_poly = h.final_poly;
-    const e2 zeta = h.zeta, g_zeta = h.g_zeta, fri_alpha = h.fri_alpha, alpha_nch = h.alpha_nch, red0 = h.red0, red1 = h.red1;
-
+    // the query rounds: fri::verifier::verify_fri_proof's loop (friv::query_rounds above), shared with qpgpu_fri_verify
     const u64 *caps0[4] = {v->cs_cap.data(), h.wires_cap.data(), h.zs_cap.data(), h.q_cap.data()};
-    Reader q{proof, len, lay.queries_pos};
-    std::vector<u64> row(widths[0] + widths[1] + widths[2] + widths[3]), path(64 * 4), ev(64);
-    const u64 w_lde = gl::root_of_unity(L);
-    for (size_t qi = 0; qi < c.num_query_rounds; qi++) {
-        size_t x_index = x_indices[qi];
-        const u64 *rows[4];
-        size_t off = 0;
-        for (int o = 0; o < 4; o++) {
-            u64 *r = row.data() + off;
-            rows[o] = r;
-            q.vec(r, widths[o]); off += widths[o];
-            const size_t plen = q.byte();
-            if (plen > 60) return fail(err, QPGPU_EVERIFY, "query %zu: Merkle path length of oracle %d out of range", qi, o);
-            q.vec(path.data(), plen * 4);
-            if (q.bad || !path_ok(H, r, widths[o], x_index, path.data(), plen, caps0[o], op[o].path_len))
-                return fail(err, QPGPU_EVERIFY, "query %zu: Merkle path of initial oracle %d does not lead to its cap", qi, o);
-        }
-        u64 subgroup_x = gl::mul(gl::MULT_GEN, gl::pow(w_lde, bitrev((uint32_t)x_index, L)));
-        e2 e0 = E(0), e1 = E(0);     // fri_combine_initial: salts are not opened
-        for (int o = 3; o >= 0; o--) for (size_t j = polys[o]; j-- > 0;) e0 = e0 * fri_alpha + E(rows[o][j]);
-        for (size_t j = nch; j-- > 0;) e1 = e1 * fri_alpha + E(rows[2][j]);
-        const e2 sx = E(subgroup_x);
-        e2 sum = (e0 - red0) * gl::e2_inv(sx - zeta);
-        sum = sum * alpha_nch + (e1 - red1) * gl::e2_inv(sx - g_zeta);
-        e2 old_eval = sum;
-        for (size_t r = 0; r < n_rounds; r++) {
-            const unsigned ab = (unsigned)c.arity_bits[r];
-            const size_t arity = (size_t)1 << ab;
-            q.vec(ev.data(), 2 * arity);
-            const size_t plen = q.byte();
-            if (plen > 60) return fail(err, QPGPU_EVERIFY, "query %zu: Merkle path length of FRI round %zu out of range", qi, r);
-            q.vec(path.data(), plen * 4);
-            const size_t coset_index = x_index >> ab, within = x_index & (arity - 1);
-            if (!same(gl::e2_make(ev[2 * within], ev[2 * within + 1]), old_eval))
-                return fail(err, QPGPU_EVERIFY, "query %zu: FRI round %zu does not continue the previous evaluation", qi, r);
-            if (q.bad || !path_ok(H, ev.data(), 2 * arity, coset_index, path.data(), plen, fri_caps.data() + r * cap_words, op[4 + r].path_len))
-                return fail(err, QPGPU_EVERIFY, "query %zu: Merkle path of FRI round %zu does not lead to its cap", qi, r);
-            // compute_evaluation: interpolate the coset's 2^ab evaluations and evaluate at beta
-            const u64 g = gl::root_of_unity(ab);
-            const size_t rev_within = bitrev((uint32_t)within, ab);
-            const u64 coset_start = gl::mul(subgroup_x, gl::pow(g, arity - rev_within));
-            u64 px[32]; e2 py[32];
-            for (size_t i = 0; i < arity; i++) {
-                const size_t src = bitrev((uint32_t)i, ab);
-                py[i] = gl::e2_make(ev[2 * src], ev[2 * src + 1]);
-                px[i] = gl::mul(coset_start, gl::pow(g, i));
-            }
-            const e2 beta = fri_betas[r];
-            e2 acc = E(0);
-            for (size_t i = 0; i < arity; i++) {      // Lagrange form
-                e2 num = E(1); u64 den = 1;
-                for (size_t j = 0; j < arity; j++) if (j != i) { num = num * (beta - E(px[j])); den = gl::mul(den, gl::sub(px[i], px[j])); }
-                acc = acc + py[i] * scale(num, gl::inv(den));
-            }
-            old_eval = acc;
-            subgroup_x = gl::pow(subgroup_x, arity);
-            x_index = coset_index;
-        }
-        e2 fe = E(0);
-        const e2 sxe = E(subgroup_x);
-        for (size_t i = final_poly.size(); i-- > 0;) fe = fe * sxe + final_poly[i];
-        if (!same(fe, old_eval)) return fail(err, QPGPU_EVERIFY, "query %zu: the final polynomial does not match the last FRI round", qi);
-    }
-    if (q.bad) return fail(err, QPGPU_EVERIFY, "proof layout does not match the circuit");
-    return QPGPU_OK;
+    const e2 points[2] = {h.zeta, h.g_zeta}, reduced[2] = {h.red0, h.red1};
+    static_assert(sizeof(size_t) == sizeof(uint64_t), "query indices are passed on as 64-bit words");
+    const friv::QueryInput q{caps0, h.fri_caps.data(), points, reduced, h.fri_alpha, h.fri_betas.data(), h.final_poly.data(),
+                             reinterpret_cast<const uint64_t *>(h.x_indices.data())};
+    size_t qi = 0;
+    const uint32_t code = friv::query_rounds(v->hash, v->fri, q, proof + v->layout.queries_pos, &qi);
+    if (!code) return QPGPU_OK;
+    friv::query_reason(err, qi, code);
+    return QPGPU_EVERIFY;
 }
 
 int qpgpu_verifier_verify_many(const qpgpu_verifier *v, const uint8_t *const *proofs, const size_t *lens, size_t count, unsigned threads,

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "circuit.hpp"
+#include "fri_verify.hpp"
 #include "gl64.hpp"
 #include "poseidon.hpp"
 #include "proof_layout.hpp"
@@ -16,6 +17,7 @@ struct qpgpu_verifier {
     std::vector<gl::u64> cs_cap;
     proof_layout::Proof layout;      // byte layout of this circuit's proofs
     std::string pack_why;            // "" or what vanishing_at_zeta finds inconsistent in the pack's gate table (it depends on the pack alone)
+    friv::Instance fri;              // the proof's FRI part as an instance: four oracles, everything at zeta, the Zs at g zeta
 };
 
 // Everything the query rounds need, as the head of verify_impl leaves it: the transcript replayed through the proof of work,
@@ -28,7 +30,12 @@ struct VerifyHead {
 };
 
 // the reason (printf form) into the caller's QPGPU_VERIFY_ERR_CAP bytes, where there are any; returns `code`
-namespace verify { int fail(char *err, int code, const char *fmt, ...); }
+namespace verify {
+int fail(char *err, int code, const char *fmt, ...);
+// the proof system's permutation as the _create entries take it (qpgpu_ctx_set_hasher's kinds); 0 or QPGPU_EINVAL with err
+int parse_hasher(int hasher_kind, const uint64_t *hasher_params, size_t n_params, hasher::Config &out, char *err);
+bool same_hasher(const hasher::Config &a, const hasher::Config &b);      // a verifier's against a context's, parameter blocks included
+}
 
 // 0, or the code and reason the verifier gives for a proof that fails before its query rounds (size, layout, non-canonical
 // element, proof of work, quotient identity)

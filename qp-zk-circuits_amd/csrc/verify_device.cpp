@@ -31,13 +31,6 @@ using gl::u64;
 
 namespace {
 
-bool same_hasher(const hasher::Config &a, const hasher::Config &b) {
-    if (a.kind != b.kind) return false;
-    if (a.kind != hasher::POSEIDON2) return true;
-    return memcmp(a.p2.rc_ext, b.p2.rc_ext, sizeof a.p2.rc_ext) == 0 && memcmp(a.p2.rc_int, b.p2.rc_int, sizeof a.p2.rc_int) == 0 &&
-           memcmp(a.p2.diag_m1, b.p2.diag_m1, sizeof a.p2.diag_m1) == 0 && memcmp(a.p2.m4, b.p2.m4, sizeof a.p2.m4) == 0;
-}
-
 // the proof layout (proof_layout.hpp) as the kernels read it, and the strides of the device buffer
 bool make_layout(const CircuitPack &c, const proof_layout::Proof &p, VerifyLayout &lay) {
     const size_t n_rounds = c.arity_bits.size();
@@ -62,19 +55,6 @@ bool make_layout(const CircuitPack &c, const proof_layout::Proof &p, VerifyLayou
     lay.log_lde = (uint32_t)(c.degree_bits + c.rate_bits);
     lay.nch = (uint32_t)c.num_challenges;
     return true;
-}
-
-// the host verifier's words for a query round's first failing check (verifier.cpp: verify_impl)
-void query_reason(char *out, size_t qi, uint32_t code) {
-    const unsigned kind = code >> 8, at = code & 0xff;
-    switch (kind) {
-    case VQ_ORACLE_PLEN: verify::fail(out, 0, "query %zu: Merkle path length of oracle %d out of range", qi, (int)at); break;
-    case VQ_ORACLE_PATH: verify::fail(out, 0, "query %zu: Merkle path of initial oracle %d does not lead to its cap", qi, (int)at); break;
-    case VQ_ROUND_PLEN: verify::fail(out, 0, "query %zu: Merkle path length of FRI round %zu out of range", qi, (size_t)at); break;
-    case VQ_ROUND_CONT: verify::fail(out, 0, "query %zu: FRI round %zu does not continue the previous evaluation", qi, (size_t)at); break;
-    case VQ_ROUND_PATH: verify::fail(out, 0, "query %zu: Merkle path of FRI round %zu does not lead to its cap", qi, (size_t)at); break;
-    default: verify::fail(out, 0, "query %zu: the final polynomial does not match the last FRI round", qi); break;
-    }
 }
 
 // what the head kernels read, beyond VerifyLayout; false: a gate beyond the bounds of the device code's local arrays
@@ -140,7 +120,7 @@ extern "C" int qpgpu_verifier_verify_many_device_ex(const qpgpu_verifier *v, qpg
     const bool device_head = (flags & QPGPU_VERIFY_HEAD_ON_DEVICE) != 0;
     if (count == 0) return QPGPU_OK;
     if (!proofs || !lens || !results) return verify::fail(err, QPGPU_EINVAL, "null argument");
-    if (!same_hasher(v->hash, ctx->hasher)) {
+    if (!verify::same_hasher(v->hash, ctx->hasher)) {
         ctx->fail(QPGPU_EINVAL, "verify_many_device: the verifier's hasher is not the context's (qpgpu_ctx_set_hasher)");
         return verify::fail(err, QPGPU_EINVAL, "%s", ctx->err.c_str());
     }
@@ -326,7 +306,7 @@ extern "C" int qpgpu_verifier_verify_many_device_ex(const qpgpu_verifier *v, qpg
                 const uint32_t code = qcodes[k * nq + q];
                 if (!code) continue;
                 results[i] = QPGPU_EVERIFY;
-                query_reason(reason_row(i), q, code);
+                friv::query_reason(reason_row(i), q, code);
                 break;
             }
         }

@@ -23,17 +23,7 @@ __constant__ u64 c_poseidon_rc[poseidon::ROUNDS * poseidon::WIDTH];
 #define MERKLE_HASH_PLUGS_ONLY
 #include "merkle_hash_impl.hpp"
 
-// the little-endian word at byte offset `off` of a word array
-__device__ __forceinline__ u64 ld(const u64 *w, u32 off) {
-    const u64 *p = w + (off >> 3);
-    const u32 sh = (off & 7) * 8;
-    const u64 lo = p[0], hi = p[1];
-    return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
-}
-__device__ __forceinline__ e2 ld_ext(const u64 *w, u32 off) { return gl::e2_make(ld(w, off), ld(w, off + 8)); }
-__device__ __forceinline__ e2 rec_ext(const u64 *rec, u32 i) { return gl::e2_make(rec[i], rec[i + 1]); }
-__device__ __forceinline__ bool same(e2 x, e2 y) { x = gl::e2_canon(x); y = gl::e2_canon(y); return x.a == y.a && x.b == y.b; }
-__device__ __forceinline__ u32 bitrev(u32 x, u32 bits) { return __brev(x) >> (32 - bits); }
+#include "verify_dev.hpp"     // ld, hash_row, climb_path, coset_interpolate, final_poly_at: shared with fri_verify_kernels.hip
 
 // blockIdx.y = opening (wave-uniform, so the layout entry is read from the kernel arguments with scalar loads)
 template <class Perm>
@@ -54,30 +44,8 @@ __global__ void __launch_bounds__(256) merkle_open_kernel(VerifyLayout lay, cons
     if (plen != op.plen) { *out = VQ_ORACLE_PATH; return; }
     u64 index = rec[VREC_BETAS + 2 * (lay.n_open - 4) + qi] >> op.shift;
     u64 s[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = 0;
-    if (op.width <= 4) {                                        // hash_or_noop: a short row is its own digest
-#pragma unroll
-        for (u32 i = 0; i < 4; i++) s[i] = i < op.width ? ld(pw, row + 8 * i) : 0;
-    } else {
-        for (u32 c = 0; c < op.width; c += 8) {                 // hash_n_to_hash_no_pad: overwrite absorption, rate 8
-#pragma unroll
-            for (u32 i = 0; i < 8; i++)
-                if (c + i < op.width) s[i] = ld(pw, row + 8 * (c + i));
-            Perm::permute(s, p2);
-        }
-    }
-    u32 at = row + 8 * op.width + 1;
-    for (u32 l = 0; l < plen; l++, at += 32) {
-        u64 sib[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) sib[i] = ld(pw, at + 8 * i);
-        const bool right = index & 1;
-#pragma unroll
-        for (int i = 0; i < 4; i++) { const u64 cur = s[i]; s[i] = right ? sib[i] : cur; s[4 + i] = right ? cur : sib[i]; s[8 + i] = 0; }
-        Perm::permute(s, p2);
-        index >>= 1;
-    }
+    hash_row<Perm>(s, pw, row, op.width, p2);
+    climb_path<Perm>(s, pw, row + 8 * op.width + 1, plen, index, p2);
     bool ok = true;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -124,33 +92,11 @@ __global__ void __launch_bounds__(256) fri_query_kernel(VerifyLayout lay, const 
         const u32 within = (u32)x_index & (arity - 1);
         if (!same(ld_ext(pw, ev + 16 * within), old_eval)) { qcodes[t] = VQ_ROUND_CONT << 8 | r; return; }
         if (m) { qcodes[t] = VQ_ROUND_PATH << 8 | r; return; }
-        // compute_evaluation: the coset's points x_i = start g^i carry the values ev[bitrev(i)]; barycentric form
-        //   p(beta) = (beta^n - start^n) / (n start^n) * sum_i y_i x_i / (beta - x_i),  accumulated as one fraction num / den
-        const u64 g = gl::root_of_unity(ab);
-        const u64 start = gl::mul(subgroup_x, gl::pow(g, arity - bitrev(within, ab)));
-        const e2 beta = rec_ext(rec, VREC_BETAS + 2 * r);
-        e2 num = gl::e2_from(0), den = gl::e2_from(1), hit = gl::e2_from(0);
-        bool at_point = false;
-        u64 x = start;
-        for (u32 i = 0; i < arity; i++, x = gl::mul(x, g)) {
-            const e2 y = ld_ext(pw, ev + 16 * bitrev(i, ab));
-            const e2 d = gl::e2_canon(gl::e2_sub(beta, gl::e2_from(x)));
-            if (d.a == 0 && d.b == 0) { at_point = true; hit = y; continue; }
-            num = gl::e2_add(gl::e2_mul(num, d), gl::e2_mul(gl::e2_scale(y, x), den));
-            den = gl::e2_mul(den, d);
-        }
-        const u64 start_n = gl::pow(start, arity);
-        e2 beta_n = beta;
-        for (u32 i = 0; i < ab; i++) beta_n = gl::e2_mul(beta_n, beta_n);
-        const e2 zb = gl::e2_sub(beta_n, gl::e2_from(start_n));
-        const e2 val = gl::e2_scale(gl::e2_mul(gl::e2_mul(zb, num), gl::e2_inv(den)), gl::inv(gl::mul(start_n, arity)));
-        old_eval = at_point ? hit : val;
+        old_eval = coset_interpolate(pw, ev, ab, within, subgroup_x, rec_ext(rec, VREC_BETAS + 2 * r));
         subgroup_x = gl::pow(subgroup_x, arity);
         x_index >>= ab;
     }
-    e2 fe = gl::e2_from(0);
-    const e2 sxe = gl::e2_from(subgroup_x);
-    for (u32 i = lay.final_n; i-- > 0;) fe = gl::e2_add(gl::e2_mul(fe, sxe), ld_ext(pw, lay.final_off + 16 * i));
+    const e2 fe = final_poly_at(pw, lay.final_off, lay.final_n, subgroup_x);
     qcodes[t] = same(fe, old_eval) ? 0 : VQ_FINAL << 8;
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include "circuit.hpp"
+#include "fri_verify.hpp"
 #include "merkle.hpp"
 
 // one Merkle opening of a query round: the four initial oracles, then one per FRI round
@@ -39,8 +40,7 @@ struct VerifyLayout {
 enum : uint32_t { VREC_LIVE = 0, VREC_ZETA = 1, VREC_GZETA = 3, VREC_ALPHA = 5, VREC_ALPHA_NCH = 7, VREC_RED0 = 9, VREC_RED1 = 11, VREC_BETAS = 13 };
 inline uint32_t vrec_words(uint32_t rounds, uint32_t nq) { return VREC_BETAS + 2 * rounds + nq; }
 
-// first failing check of a query round, in the host verifier's order: code = kind << 8 | oracle or round; 0 = accepted
-enum : uint32_t { VQ_ORACLE_PLEN = 1, VQ_ORACLE_PATH = 2, VQ_ROUND_PLEN = 3, VQ_ROUND_CONT = 4, VQ_ROUND_PATH = 5, VQ_FINAL = 6 };
+// the verdict codes of a query round (VQ_*): fri_verify.hpp, shared with the host loop
 
 hipError_t verify_upload_constants(const uint64_t *rc360);   // plonky2 Poseidon round constants of this unit (merkle_upload_constants)
 // proofs: nproofs x stride_words; recs: nproofs x rec_words; mcodes: nproofs x nq x n_open bytes (scratch); qcodes: nproofs x nq
