@@ -14,9 +14,11 @@
 //   * A operand: column (element e, digit b) of output o holds the 8 signed digits of the constant w[o][e] 256^b mod p (the
 //     representative in the balanced range: w or w - p always fits 8 digits in [-128, 127]), one digit per output limb: 8 limbs per
 //     output, 4 outputs per 32-row tile. Tiles live in LDS (60 KB), one ds_read_b128 per MFMA pair.
-//   * C operand = 2^23 + the additive constant's bytes: every limb comes out in [0, 2^24) (|sum| < 2^22.2), so recombining 8 limbs
-//     at 8-bit spacing is three byte concatenations (limbs l, l+3, l+6 do not overlap), one 96-bit add chain and one reduce96:
-//     about 20 vector instructions per output where an MDS layer in the spectral form costs about 270.
+//   * C operand = 2^23 + the additive constant's bytes: every limb comes out in [3 670 016, 13 107 455] (|sum| <= 288 x 2^14), and
+//     any two limbs up to 16 711 935 = (2^32 - 1) / 257 join at 8-bit spacing in one 32-bit shift-add. Recombining 8 limbs is four
+//     such shift-adds and three words with two carries (recombine_wide, 14 to 15 vector instructions), then one reduce96: about 20
+//     vector instructions per output where an MDS layer in the spectral form costs about 270. The table builder proves the limb
+//     bound from the table bytes before a table may be uploaded (host::chain_limb_max).
 //   * The K dimension only ever holds complete groups of four y; the y of the running group reach the rounds of that group through
 //     three small integer coefficients (25, 5 017, 1 259 209) on the VALU.
 // The accumulator layout gives a lane 16 rows of its own column and 16 of the partner lane's (lane +-32): 16 swaps give every lane
@@ -75,29 +77,28 @@ static_assert(small_g(0) == 25 && small_g(1) < small_g(2) && small_g(2) < (1ull 
 // that constant into the row's accumulator start (Rows::addc). Elements that are not known yet and the two pad elements keep the
 // literal digits 0 (not 0 ^ BIAS): their weights are zero.
 GL_HD u64 to_digits(u64 v) { return v ^ DIGIT_BIAS; }
-GL_HD u32 byte_perm(u32 s0, u32 s1, u32 sel) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_perm(s0, s1, sel);
-#else
-    const u64 pool = ((u64)s0 << 32) | s1;
-    u32 r = 0;
-    for (int i = 0; i < 4; i++) r |= (u32)((pool >> (8 * ((sel >> (8 * i)) & 7))) & 0xFF) << (8 * i);
-    return r;
-#endif
-}
-// sum_l z[l] 2^(8 l) as a 96-bit integer (lo + top 2^64) for 8 limbs in [0, 2^24): limbs l, l+3, l+6 do not overlap (three byte
-// concatenations), then one 96-bit add chain. The sum is below 2^24 (2^56 + 2^48 + ...) < 2^81 (so below 2^82): the
-// top word stays below 2^18.
+// The largest limb a join may see: 16 711 935 x 257 = 2^32 - 1, so z + 256 z' fits 32 bits for any two limbs up to it. What a
+// chain can reach is far below: an accumulator starts at 2^23 + one byte and collects at most 288 products of two digits of
+// magnitude <= 128, 2^23 + 255 + 288 x 2^14 = 13 107 455. host::fill_tiles proves the bound for every row from the table bytes
+// themselves (a table that cannot hold it is never uploaded); host::emu_gemm checks every limb it computes against it.
+constexpr u32 LIMB_MAX = 16711935u;
+static_assert((u64)LIMB_MAX * 257 == 0xFFFFFFFFull, "two limbs at 8-bit spacing fit one word");
+// sum_l z[l] 2^(8 l) as a 96-bit integer (lo + top 2^64) for 8 limbs in [0, LIMB_MAX]: neighbours pair up in one 32-bit
+// shift-add each (t1..t4, no overflow, above), and t1 + t2 2^16 + t3 2^32 + t4 2^48 is three words with two carries: word 0 =
+// t1 + (t2 << 16), word 1 = t3 + (lo16(t4) : hi16(t2)) + carry (one v_alignbit_b32 makes the middle term), top = (t4 >> 16) +
+// carry. One text for host and device; the gfx950 compiler makes 14 to 15 vector instructions of it (about 22 for the three byte
+// concatenations and the 96-bit add chain it replaces). Two other forms were counted and are not used, profiles/mds_gemm_isa.txt:
+// two multiply-adds by 2^16 (X = t1 + t2 2^16, Y = t3 + t4 2^16, joined as X + Y 2^32; 8 instructions on paper, 14 compiled: the
+// multiplications become 64-bit shifts and every 64-bit addend pays a v_mov for its zero upper half), and the same three words
+// as an explicit add-with-carry chain (10 instructions, all full rate, but 16 more bytes of scratch per lane in the proof-of-work
+// kernel and 4 in Poseidon2's node kernel, which no change to these kernels may cost).
+// The sum is below 2^24 (2^56 + 2^48 + ...) < 2^81 (so below 2^82): the top word stays below 2^18.
 GL_HD void recombine_wide(const u32 (&z)[LIMBS], u64 &lo, u32 &top) {
-    const u32 a0 = (z[3] << 24) | z[0], a1 = byte_perm(z[6], z[3], 0x05040201u), a2 = z[6] >> 16;
-    const u32 b0 = z[1] << 8, b1 = (z[7] << 24) | z[4], b2 = z[7] >> 8;
-    const u32 c0 = z[2] << 16, c1 = byte_perm(z[5], z[2], 0x06050402u);
-    typedef unsigned __int128 u128;
-    const u128 A = ((u128)a2 << 64) | ((u128)a1 << 32) | a0;
-    const u128 B = ((u128)b2 << 64) | ((u128)b1 << 32) | b0;
-    const u128 Cc = ((u128)c1 << 32) | c0;
-    const u128 S = A + B + Cc;
-    lo = (u64)S; top = (u32)(S >> 64);
+    const u32 t1 = z[0] + (z[1] << 8), t2 = z[2] + (z[3] << 8), t3 = z[4] + (z[5] << 8), t4 = z[6] + (z[7] << 8);
+    const u32 m = (t4 << 16) | (t2 >> 16);     // v_alignbit_b32: the two halves do not overlap
+    const u64 s0 = (u64)t1 + (t2 << 16), s1 = (u64)t3 + m + (s0 >> 32);
+    const u32 w0 = (u32)s0, w1 = (u32)s1, c1 = (u32)(s1 >> 32);
+    lo = ((u64)w1 << 32) | w0; top = (t4 >> 16) + c1;
 }
 // the same mod p: one reduce96
 GL_HD u64 recombine(const u32 (&z)[LIMBS]) {
@@ -150,6 +151,23 @@ inline bool const_digits(u64 w, signed char (&d)[LIMBS]) {
     return rep == 0;
 }
 struct Rows { u64 w[4][N_ELEM]; u64 addc[4]; };   // the four outputs of a tile
+// The largest limb one tile chain can produce, from the table bytes alone: over its 32 rows, start + 128 sum |a| (a B digit has
+// magnitude at most 128, whatever the inputs). A row that could go below zero (start - 128 sum |a| < 0) counts as unbounded.
+inline u64 chain_limb_max(const unsigned char *tiles, const unsigned char *cinit, int steps) {
+    u64 worst = 0;
+    for (int row = 0; row < 32; row++) {
+        u64 mag = 0;
+        for (int q = 0; q < steps; q++)
+            for (int k = 0; k < 32; k++) {
+                const int a = (signed char)tiles[(size_t)q * 1024 + (row + 32 * (k >> 4)) * 16 + (k & 15)];
+                mag += (u64)(a < 0 ? -a : a);
+            }
+        u32 start; memcpy(&start, cinit + (row >> 2 & 1) * 64 + ((row & 3) + 4 * (row >> 3)) * 4, 4);   // row = (i&3) + 8 (i>>2) + 4 h
+        if (start < 128 * mag) return ~0ull;
+        if (start + 128 * mag > worst) worst = start + 128 * mag;
+    }
+    return worst;
+}
 inline bool fill_tiles(const Rows &rw, int steps, unsigned char *tiles, unsigned char *cinit) {
     static signed char dig[4][N_ELEM][8][LIMBS];
     for (int o = 0; o < 4; o++)
@@ -174,7 +192,7 @@ inline bool fill_tiles(const Rows &rw, int steps, unsigned char *tiles, unsigned
             const u32 v = (1u << 23) + (u32)((c >> (8 * (i & 7))) & 0xFF);
             memcpy(cinit + h * 64 + i * 4, &v, 4);
         }
-    return true;
+    return chain_limb_max(tiles, cinit, steps) <= LIMB_MAX;
 }
 // to_digits hands the gemm v - BIAS for every element whose digits are in: row o gets BIAS sum_e w[o][e] back through its additive
 // constant. A tile's rows carry weights only on elements that are known when the tile runs (the twelve state elements and the y
@@ -284,6 +302,19 @@ inline bool build_tables_p2(const poseidon2::Params &p, unsigned char *tab) {
     for (int i = 0; i < 12; i++) L.after[i] = p.rc_ext[4 * 12 + i];
     return build_tables(L, tab);
 }
+// the largest limb any chain of a finished table can produce (chain_limb_max over every chain the device runs)
+inline u64 table_limb_max(const unsigned char *tab) {
+    u64 worst = 0;
+    for (int g = 0; g < N_GROUP; g++) {
+        const u64 m = chain_limb_max(tab + (size_t)group_base(g) * 1024, tab + CINIT_OFF + g * 128, group_steps(g));
+        if (m > worst) worst = m;
+    }
+    for (int f = 0; f < N_FIN; f++) {
+        const u64 m = chain_limb_max(tab + (size_t)(N_GROUP_TILES + f * FIN_STEPS) * 1024, tab + CINIT_OFF + (N_GROUP + f) * 128, FIN_STEPS);
+        if (m > worst) worst = m;
+    }
+    return worst;
+}
 // what one MFMA chain computes for one column, from the table bytes (layout assumptions as the device code's)
 inline bool emu_gemm(const unsigned char *tab, int tile0, int cidx, int steps, const u64 *D, u32 (&Z)[4][LIMBS]) {
     for (int o = 0; o < 4; o++)
@@ -298,7 +329,7 @@ inline bool emu_gemm(const unsigned char *tab, int tile0, int cidx, int steps, c
                     const int bdig = (signed char)(D[4 * q + (k >> 3)] >> (8 * (k & 7)));
                     acc += (long long)a * bdig;
                 }
-            if (acc < 0 || acc >= (1 << 24)) return false;
+            if (acc < 0 || acc > (long long)LIMB_MAX) return false;
             Z[o][limb] = (u32)acc;
         }
     return true;

@@ -2,7 +2,7 @@
 // against 128-bit integer arithmetic mod p:
 //   * pmf::recombine_wide + pmf::reduce96_terms (poseidon_mfma.hpp): the S-box input of a round of the running group, i.e. the
 //     gemm's eight limbs recombined to a 96-bit integer, the group's earlier y added UNREDUCED with their small integer
-//     coefficients, one reduce96. Limbs at 0 and at 2^24 - 1, y at the edges of the 64-bit range (loose values included), one,
+//     coefficients, one reduce96. Limbs at 0 and at pmf::LIMB_MAX (the largest limb the join is specified for), y at the edges of the 64-bit range (loose values included), one,
 //     two and three terms with every choice of the three coefficients, and 10^5 random cases in the device's own coefficient
 //     order. The bounds the code states (top word of the recombined sum below 2^18, of the total below 2^24) are checked too.
 //   * poseidon::mds_layer_rows<FIRST, COUNT> (poseidon.hpp) against mds_layer_naive, row by row mod p, for the row sets the
@@ -42,7 +42,7 @@ static int check_terms() {
     long cases = 0;
     for (int zc = 0; zc < 3; zc++) {
         u32 z[pmf::LIMBS];
-        for (int l = 0; l < pmf::LIMBS; l++) z[l] = zc == 0 ? 0 : zc == 1 ? (1u << 24) - 1 : ((l & 1) ? (1u << 24) - 1 : 0);
+        for (int l = 0; l < pmf::LIMBS; l++) z[l] = zc == 0 ? 0 : zc == 1 ? pmf::LIMB_MAX : ((l & 1) ? pmf::LIMB_MAX : 0);
         bad += terms_case(z, nullptr, nullptr, 0); cases++;
         for (int n = 1; n <= pmf::MAX_GROUP_TERMS; n++) {
             int ny = 1, ng = 1;
@@ -58,7 +58,7 @@ static int check_terms() {
     for (int t = 0; t < 100000; t++) {
         u32 z[pmf::LIMBS], g[pmf::MAX_GROUP_TERMS];
         u64 y[pmf::MAX_GROUP_TERMS];
-        for (int l = 0; l < pmf::LIMBS; l++) z[l] = (u32)rnd() & ((1u << 24) - 1);
+        for (int l = 0; l < pmf::LIMBS; l++) z[l] = (u32)(rnd() % (pmf::LIMB_MAX + 1ull));
         const int n = (int)(rnd() % 4);                            // the round's place in its group: n earlier y
         for (int i = 0; i < n; i++) {
             y[i] = rnd();
