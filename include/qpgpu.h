@@ -69,6 +69,32 @@ int qpgpu_memcpy_h2d(qpgpu_ctx *ctx, void *dst_dev, const void *src_host, size_t
 int qpgpu_memcpy_d2h(qpgpu_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes);
 int qpgpu_memcpy_d2d(qpgpu_ctx *ctx, void *dst_dev, const void *src_dev, size_t bytes);   /* asynchronous on the ctx stream */
 
+/* ---- secret residue audit (a test facility) --------------------------------------------------------------------
+ * The library lists every device and pinned buffer it allocates on behalf of a context, by region; the scan looks for
+ * witness-derived 64-bit words in them (the counterpart of the reference's allocator test,
+ * wormhole/circuit/tests/heap_zeroization.rs). Region r's stable name is qpgpu_residue_region_name(r) (NULL past the end):
+ * circuit-setup, circuit-workspace, witness-plan, partial-witness, ctx-scratch, ctx-pinned, oracle, stage-plan, fri-session,
+ * pool-witness, verify-staging, zk-tree, tables. Process-wide constant tables belong to no context and are not listed
+ * (DESIGN.md section 4.5); neither is anything the caller allocated (qpgpu_malloc, d_wires arguments). */
+typedef struct { uint64_t word; uint32_t region; uint32_t pinned; uint64_t offset_words; uint64_t alloc_bytes; } qpgpu_residue_hit;
+#define QPGPU_RESIDUE_MAX_NEEDLES 16
+/* Scans every tracked buffer of ctx (device: one grid-stride kernel per buffer, 8-byte aligned 64-bit compares against up to 16
+ * needles held in kernel arguments, hit count by atomicAdd, the first `cap` hits recorded; pinned: a host loop) for any needle word.
+ * region_mask: bit r = scan region r; 0 = every region except circuit-setup, tables, zk-tree and verify-staging (public data).
+ * A needle below 2^32 is QPGPU_EINVAL naming it: 32-bit-sized values occur in tables by chance; sensitive 64-bit words do not.
+ * Synchronous on the ctx stream; same threading rule as every ctx call. Reads only memory the library itself allocated.
+ * Of one device buffer at most 64 hits are recorded (all are counted): with many hits in one buffer fewer than min(hits, cap)
+ * entries of first_hits are written; the unwritten ones are left as the caller passed them. hits, first_hits (with cap 0) and
+ * bytes_scanned may be NULL. */
+int qpgpu_ctx_residue_scan(qpgpu_ctx *ctx, const uint64_t *needles, size_t n_needles, uint64_t region_mask,
+                           uint64_t *hits, qpgpu_residue_hit *first_hits, size_t cap, uint64_t *bytes_scanned);
+const char *qpgpu_residue_region_name(uint32_t region);
+/* From now on every tracked buffer of ctx is scanned for the needles immediately BEFORE the library frees it (i.e. after whatever
+ * scrub the release path performs); hits accumulate. _end returns the totals and switches the audit off. Off by default; no cost
+ * when off. _end without _begin, and _begin while an audit is open, are QPGPU_EINVAL. */
+int qpgpu_ctx_residue_audit_begin(qpgpu_ctx *ctx, const uint64_t *needles, size_t n_needles);
+int qpgpu_ctx_residue_audit_end(qpgpu_ctx *ctx, uint64_t *hits, qpgpu_residue_hit *first_hits, size_t cap, uint64_t *buffers_released);
+
 /* ---- proof-system hasher -------------------------------------------------------------------------------------
  * Which permutation backs the fork's `PoseidonGoldilocksConfig` hasher (Merkle trees, Fiat-Shamir challenger, public-input
  * hash, proof of work) cannot be told from the reference, so it is a plug, and a property of the
@@ -158,8 +184,10 @@ size_t qpgpu_circuit_num_public_inputs(const qpgpu_circuit *c);
 /* Releases the handle; every device region that held witness-derived data is overwritten first. */
 void qpgpu_circuit_free(qpgpu_circuit *c);
 /* Overwrites the witness-derived workspace now (witness copy, Z / quotient values, coefficients, LDEs, salts, FRI
- * workspace, openings). qpgpu_prove does this after every proof; the _dev and pool entries leave the workspace as it is
- * until the next proof or the free (the caller owns the witness buffer it passed and clears that itself). */
+ * workspace, openings), the stage s1 value buffers of the circuit (public-input values and hash, prepared partial-witness
+ * values and keys) and, of its context, the transform scratch and the pinned bounce buffer. qpgpu_prove does this after
+ * every proof; the _dev and pool entries leave the workspace as it is until the next proof, a scrub (qpgpu_pool_scrub for
+ * a pool) or the free (the caller owns the witness buffer it passed and clears that itself). */
 int qpgpu_circuit_scrub(qpgpu_circuit *c);
 int qpgpu_circuit_constants_sigmas_cap(const qpgpu_circuit *c, uint64_t *out, size_t out_words);
 /* Zero-knowledge packs (standard_recursion_zk_config, reference common/src/circuit.rs:396-402): the wires,
@@ -525,7 +553,14 @@ int qpgpu_pool_create_multi(const int *devices, unsigned n_devices, const uint64
 /* A job's arguments are checked at submit (null pointers: QPGPU_EINVAL; out_cap below qpgpu_pool_proof_size:
  * QPGPU_EBUFSIZE). Jobs of different callers share a lockstep batch: when a batch fails, its jobs are proven again one at
  * a time, so only the failing job's wait() returns the error (with that job's own message). */
-void qpgpu_pool_destroy(qpgpu_pool *p);          /* drains the queue first; witness workspaces are overwritten before release */
+void qpgpu_pool_destroy(qpgpu_pool *p);          /* drains the queue first; scrubs as qpgpu_pool_scrub does before anything is released */
+/* Every worker, after the job it is in: scrubs its circuit workspace (qpgpu_circuit_scrub's regions), its resident
+ * witness buffers and its partial-witness buffers. Returns when all have. Jobs submitted meanwhile run afterwards. */
+int qpgpu_pool_scrub(qpgpu_pool *p);
+/* qpgpu_ctx_residue_scan run by each worker on its own context (the threading rule), totals summed; first_hits from the lowest
+ * worker that has any. */
+int qpgpu_pool_residue_scan(qpgpu_pool *p, const uint64_t *needles, size_t n_needles, uint64_t region_mask,
+                            uint64_t *hits, qpgpu_residue_hit *first_hits, size_t cap, uint64_t *bytes_scanned);
 /* qpgpu_circuit_set_witness_check on every worker's circuit; only while no ticket is outstanding (QPGPU_EINVAL otherwise) */
 int qpgpu_pool_set_witness_check(qpgpu_pool *p, int on);
 size_t qpgpu_pool_proof_size(const qpgpu_pool *p);

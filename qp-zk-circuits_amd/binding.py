@@ -202,6 +202,12 @@ def load_library():
                                              c.POINTER(c.c_size_t), u64p, u64p]),
         "qpgpu_synth_circuit": (c.c_int, [c.c_uint, c.c_uint, c.c_uint, c.c_uint, c.c_uint64, u64p, c.c_size_t,
                                           c.POINTER(c.c_size_t), u64p, u64p]),
+        "qpgpu_ctx_residue_scan": (c.c_int, [vp, u64p, c.c_size_t, c.c_uint64, c.POINTER(c.c_uint64), vp, c.c_size_t, c.POINTER(c.c_uint64)]),
+        "qpgpu_residue_region_name": (c.c_char_p, [c.c_uint32]),
+        "qpgpu_ctx_residue_audit_begin": (c.c_int, [vp, u64p, c.c_size_t]),
+        "qpgpu_ctx_residue_audit_end": (c.c_int, [vp, c.POINTER(c.c_uint64), vp, c.c_size_t, c.POINTER(c.c_uint64)]),
+        "qpgpu_pool_scrub": (c.c_int, [vp]),
+        "qpgpu_pool_residue_scan": (c.c_int, [vp, u64p, c.c_size_t, c.c_uint64, c.POINTER(c.c_uint64), vp, c.c_size_t, c.POINTER(c.c_uint64)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -1303,6 +1309,69 @@ class FriVerifier:
         return [r == 0 for r in self.results]
 
 
+class ResidueHit(ctypes.Structure):
+    """qpgpu_residue_hit: one needle word found in a buffer the library owns."""
+    _fields_ = [("word", ctypes.c_uint64), ("region", ctypes.c_uint32), ("pinned", ctypes.c_uint32),
+                ("offset_words", ctypes.c_uint64), ("alloc_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        name = load_library().qpgpu_residue_region_name(self.region)
+        return {"word": self.word, "region": name.decode() if name else None, "pinned": bool(self.pinned),
+                "offset_words": self.offset_words, "alloc_bytes": self.alloc_bytes}
+
+
+RESIDUE_MAX_NEEDLES = 16
+
+
+def residue_regions():
+    """The stable region names of the residue audit, by region number."""
+    lib, out = load_library(), []
+    while True:
+        name = lib.qpgpu_residue_region_name(len(out))
+        if name is None:
+            return out
+        out.append(name.decode())
+
+
+def _residue_mask(regions):
+    """None -> 0 (the library's default: every region that can hold witness-derived words); an int is passed through; names are looked up."""
+    if regions is None:
+        return 0
+    if isinstance(regions, int):
+        return regions
+    names = residue_regions()
+    return sum(1 << names.index(r) for r in set(regions))
+
+
+_NO_REGION = 0xFFFFFFFF
+
+
+def _blank_hits(cap):
+    """The library writes the hits it recorded (at most 64 per device buffer) and leaves the rest of the array as it was: entries
+    marked with a region no buffer has are the ones it did not write."""
+    first = (ResidueHit * max(cap, 1))()
+    for h in first:
+        h.region = _NO_REGION
+    return first
+
+
+def _written_hits(first, cap):
+    out = []
+    for i in range(cap):
+        if first[i].region == _NO_REGION:
+            break
+        out.append(first[i].as_dict())
+    return out
+
+
+def _residue_call(fn, handle, needles, regions, cap):
+    nd = np.ascontiguousarray(needles, dtype=np.uint64)
+    hits, nbytes = ctypes.c_uint64(), ctypes.c_uint64()
+    first = _blank_hits(cap)
+    rc = fn(handle, nd.ctypes.data, nd.size, _residue_mask(regions), ctypes.byref(hits), first, cap, ctypes.byref(nbytes))
+    return rc, hits.value, _written_hits(first, cap), nbytes.value
+
+
 class ProvingPool:
     """Several proofs of one circuit in flight on one GPU (qpgpu_pool_*): worker threads, streams and circuit copies live
     inside the library."""
@@ -1397,6 +1466,19 @@ class ProvingPool:
         rc = self.lib.qpgpu_pool_submit_partial(self.h, v.ctypes.data, None if p is None else p.ctypes.data, out.ctypes.data, out.size, ctypes.byref(t))
         return self._submitted(rc, t, (p, out, None))
 
+    def scrub(self):
+        """Every worker, after the job it is in, overwrites its circuit workspace, resident witnesses and partial-witness buffers."""
+        rc = self.lib.qpgpu_pool_scrub(self.h)
+        if rc != 0:
+            raise QpGpuError(rc, self.lib.qpgpu_pool_last_error(self.h).decode())
+
+    def residue_scan(self, needles, regions=None, cap=16):
+        """QpGpu.residue_scan on every worker's context, totals summed: (hits, first_hits, bytes_scanned)."""
+        rc, hits, first, nbytes = _residue_call(self.lib.qpgpu_pool_residue_scan, self.h, needles, regions, cap)
+        if rc != 0:
+            raise QpGpuError(rc, self.lib.qpgpu_pool_last_error(self.h).decode())
+        return hits, first, nbytes
+
     def wait(self, ticket, copy=True):
         """The proof of a ticket (bytes); copy=False: only its length — the bytes are in the `out` buffer given to submit()."""
         ln = ctypes.c_size_t()
@@ -1405,6 +1487,25 @@ class ProvingPool:
         if rc != 0:
             raise QpGpuError(rc, self.lib.qpgpu_pool_last_error(self.h).decode())
         return out[:ln.value].tobytes() if copy else ln.value
+
+
+class _ResidueAudit:
+    def __init__(self, gpu, needles, cap):
+        self.gpu, self.cap = gpu, cap
+        self.needles = np.ascontiguousarray(needles, dtype=np.uint64)
+        self.hits = self.buffers_released = None
+        self.first_hits = []
+
+    def __enter__(self):
+        self.gpu._check(self.gpu.lib.qpgpu_ctx_residue_audit_begin(self.gpu.ctx, self.needles.ctypes.data, self.needles.size))
+        return self
+
+    def __exit__(self, *a):
+        hits, released = ctypes.c_uint64(), ctypes.c_uint64()
+        first = _blank_hits(self.cap)
+        self.gpu._check(self.gpu.lib.qpgpu_ctx_residue_audit_end(self.gpu.ctx, ctypes.byref(hits), first, self.cap, ctypes.byref(released)))
+        self.hits, self.buffers_released = hits.value, released.value
+        self.first_hits = _written_hits(first, self.cap)
 
 
 class _Stage3:
@@ -1507,6 +1608,19 @@ class QpGpu(_Stage3):
         ms, n = ctypes.c_double(), ctypes.c_uint64()
         self._check(self.lib.qpgpu_profile_read(self.ctx, kernel.encode(), ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+    def residue_scan(self, needles, regions=None, cap=16):
+        """Looks for the 64-bit needle words in every device / pinned buffer the library allocated for this context (a test
+        facility). regions: None (every region that can hold witness-derived words), region names, or a bit mask. Returns
+        (hits, first_hits, bytes_scanned); first_hits: up to `cap` dicts (word, region, pinned, offset_words, alloc_bytes)."""
+        rc, hits, first, nbytes = _residue_call(self.lib.qpgpu_ctx_residue_scan, self.ctx, needles, regions, cap)
+        self._check(rc)
+        return hits, first, nbytes
+
+    def residue_audit(self, needles, cap=16):
+        """Context manager: every tracked buffer the library frees inside the block is scanned for the needles right before the
+        free. The object it yields has hits, first_hits and buffers_released once the block has ended."""
+        return _ResidueAudit(self, needles, cap)
 
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)

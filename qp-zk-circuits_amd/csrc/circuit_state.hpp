@@ -10,7 +10,10 @@
 #include "prover_stages.hpp"
 
 struct WitnessPlan;
-void witness_plan_free(WitnessPlan *p);
+void witness_plan_free(WitnessPlan *p, qpgpu_ctx *ctx);
+// stream-ordered zero fill of the plan's value buffers (public-input values and hash, prepared assignment values, ChaCha keys);
+// null plan: nothing
+void witness_plan_scrub(WitnessPlan *p, hipStream_t st);
 
 struct qpgpu_circuit {
     qpgpu_ctx *ctx = nullptr;
@@ -46,7 +49,7 @@ struct qpgpu_circuit {
     template <class T> int alloc(T **p, size_t count, bool secret = false) {
         void *v = nullptr;
         const size_t bytes = std::max<size_t>(count * sizeof(T), 8);
-        hipError_t e = hipMalloc(&v, bytes);
+        hipError_t e = ctx->track_malloc(&v, bytes, secret ? residue::CIRCUIT_WORKSPACE : residue::CIRCUIT_SETUP);
         if (e == hipErrorOutOfMemory) return ctx->fail(QPGPU_ENOMEM, "hipMalloc(circuit): out of device memory");
         if (e != hipSuccess) return ctx->hip_fail(e, "hipMalloc(circuit)");
         allocs.push_back(v);

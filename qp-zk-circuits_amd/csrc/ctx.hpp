@@ -9,6 +9,7 @@
 #include "../../include/qpgpu.h"
 #include "merkle.hpp"
 #include "poseidon.hpp"
+#include "residue.hpp"
 
 struct NttTables;  // ntt_plan.cpp
 
@@ -77,6 +78,19 @@ struct qpgpu_ctx {
     // with the verdict codes behind it; grow-only, freed at destroy
     void *vd_pin = nullptr, *vd_dev = nullptr;
     size_t vd_pin_bytes = 0, vd_dev_bytes = 0;
+    // every device / pinned allocation made on behalf of this context, by region (residue.hpp): what qpgpu_ctx_residue_scan walks
+    // and what the release audit scans before a free. track_* are the only way library code allocates and frees such memory
+    // (residue_api.cpp); the caller has selected the device.
+    residue::Registry mem;
+    void bind_residue_backend();                    // the HIP scan and free operations of the registry (qpgpu_ctx_create)
+    struct ResidueResult *d_residue = nullptr;      // result block of the scan kernel (untracked: it holds what a scan found, zeroed after each)
+    hipError_t track_malloc(void **p, size_t bytes, uint32_t region);
+    hipError_t track_host_malloc(void **p, size_t bytes, uint32_t region);
+    void track_free(void *p);                       // release audit when one is open, then hipFree / hipHostFree; null is ignored
+    // witness-derived words outside any circuit handle: the transform scratch (stream-ordered fill) and the pinned bounce buffer
+    // (host fill: call after a stream synchronisation)
+    void scrub_scratch();
+    void scrub_pinned();
 };
 
 // HIP's current device is per host thread: every entry point selects the ctx's GPU first

@@ -5,6 +5,7 @@
 // one proof and for a lockstep batch (the _batch entries; a session remembers its batch): the single-proof ones are the batch of one.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include "fri_prover.hpp"
 #include "oracle_handle.hpp"
@@ -76,10 +77,10 @@ struct FriSpace {
     FriWork work;
     int alloc(qpgpu_ctx *ctx, const FriCall &c) {
         work_words = FriWork::words(c.fp, c.widths, c.max_count, c.nb);
-        QP_HIP(ctx, hipMalloc(&dv, work_words * 8));
+        QP_HIP(ctx, ctx->track_malloc(&dv, work_words * 8, residue::FRI_SESSION));
         stage.words = FriWork::stage_words(c.fp, c.max_count, c.nb);
-        hipError_t e = hipHostMalloc(&hv, stage.words * 8, hipHostMallocDefault);
-        if (e != hipSuccess) { (void)hipFree(dv); dv = nullptr; return ctx->hip_fail(e, "hipHostMalloc(fri stage)"); }
+        hipError_t e = ctx->track_host_malloc(&hv, stage.words * 8, residue::FRI_SESSION);
+        if (e != hipSuccess) { ctx->track_free(dv); dv = nullptr; return ctx->hip_fail(e, "hipHostMalloc(fri stage)"); }
         stage.h = (u64 *)hv;
         work.bind((u64 *)dv, c.fp, c.widths, c.max_count, c.nb);
         return QPGPU_OK;
@@ -89,7 +90,8 @@ struct FriSpace {
         if (!dv) return;
         (void)hipMemsetAsync(dv, 0, work_words * 8, ctx->stream);
         (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(dv); (void)hipHostFree(hv);
+        if (hv) std::memset(hv, 0, stage.words * 8);      // the pinned ring held challenges and query indices
+        ctx->track_free(dv); ctx->track_free(hv);
         dv = hv = nullptr;
     }
 };

@@ -125,15 +125,15 @@ extern "C" int qpgpu_fri_verify_many_device(const qpgpu_fri_verifier *v, qpgpu_c
     if (int rc = merkle_ensure_constants(ctx)) return device_fail(rc);
     if (pin_bytes > ctx->vd_pin_bytes) {
         hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess && ctx->vd_pin) { e = hipHostFree(ctx->vd_pin); ctx->vd_pin = nullptr; ctx->vd_pin_bytes = 0; }
-        if (e == hipSuccess) e = hipHostMalloc(&ctx->vd_pin, pin_bytes, hipHostMallocDefault);
+        if (e == hipSuccess && ctx->vd_pin) { ctx->track_free(ctx->vd_pin); ctx->vd_pin = nullptr; ctx->vd_pin_bytes = 0; }
+        if (e == hipSuccess) e = ctx->track_host_malloc(&ctx->vd_pin, pin_bytes, residue::VERIFY_STAGING);
         if (e != hipSuccess) { ctx->vd_pin = nullptr; return device_fail(ctx->hip_fail(e, "hipHostMalloc (verification staging)")); }
         ctx->vd_pin_bytes = pin_bytes;
     }
     if (dev_bytes > ctx->vd_dev_bytes) {
         hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess && ctx->vd_dev) { e = hipFree(ctx->vd_dev); ctx->vd_dev = nullptr; ctx->vd_dev_bytes = 0; }
-        if (e == hipSuccess) e = hipMalloc(&ctx->vd_dev, dev_bytes);
+        if (e == hipSuccess && ctx->vd_dev) { ctx->track_free(ctx->vd_dev); ctx->vd_dev = nullptr; ctx->vd_dev_bytes = 0; }
+        if (e == hipSuccess) e = ctx->track_malloc(&ctx->vd_dev, dev_bytes, residue::VERIFY_STAGING);
         if (e != hipSuccess) { ctx->vd_dev = nullptr; return device_fail(ctx->hip_fail(e, "hipMalloc (verification workspace)")); }
         ctx->vd_dev_bytes = dev_bytes;
     }

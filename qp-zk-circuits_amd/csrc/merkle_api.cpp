@@ -31,7 +31,7 @@ int merkle_ensure_constants(qpgpu_ctx *ctx) {
     }
     if (ctx->hasher.kind == hasher::POSEIDON2 && !ctx->d_p2) {   // the context's Poseidon2 parameter block
         void *v = nullptr;
-        QP_HIP(ctx, hipMalloc(&v, sizeof(poseidon2::Params)));
+        QP_HIP(ctx, ctx->track_malloc(&v, sizeof(poseidon2::Params), residue::TABLES));
         ctx->d_p2 = (poseidon2::Params *)v;
         QP_HIP(ctx, hipMemcpyAsync(ctx->d_p2, &ctx->hasher.p2, sizeof(poseidon2::Params), hipMemcpyHostToDevice, ctx->stream));
         QP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -42,11 +42,11 @@ int merkle_ensure_constants(qpgpu_ctx *ctx) {
 int qpgpu_ctx::ensure_p2_app() {
     if (d_p2_app) return QPGPU_OK;
     void *v = nullptr;
-    QP_HIP(this, hipMalloc(&v, sizeof(poseidon2::Params)));
+    QP_HIP(this, track_malloc(&v, sizeof(poseidon2::Params), residue::TABLES));
     // pageable source with static lifetime (qp_params() is a function-local static); the copy is ordered on the ctx stream
     hipError_t e = hipMemcpyAsync(v, &poseidon2::qp_params(), sizeof(poseidon2::Params), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { (void)hipFree(v); return hip_fail(e, "upload of the Poseidon2 application parameters"); }
+    if (e != hipSuccess) { track_free(v); return hip_fail(e, "upload of the Poseidon2 application parameters"); }
     d_p2_app = (poseidon2::Params *)v;
     return QPGPU_OK;
 }

@@ -21,8 +21,12 @@ struct NttTables {
 
 int qpgpu_ctx::ensure_scratch(size_t bytes) {
     if (bytes <= scratch_bytes) return QPGPU_OK;
-    if (scratch) { QP_HIP(this, hipStreamSynchronize(stream)); QP_HIP(this, hipFree(scratch)); scratch = nullptr; scratch_bytes = 0; }
-    QP_HIP(this, hipMalloc((void **)&scratch, bytes));
+    if (scratch) {      // transforms of witness columns wrote it: overwritten before the allocator gets it back
+        scrub_scratch();
+        QP_HIP(this, hipStreamSynchronize(stream));
+        track_free(scratch); scratch = nullptr; scratch_bytes = 0;
+    }
+    QP_HIP(this, track_malloc((void **)&scratch, bytes, residue::CTX_SCRATCH));
     scratch_bytes = bytes;
     return QPGPU_OK;
 }
@@ -31,8 +35,8 @@ int qpgpu_ctx::reserve_read_back(size_t bytes) {
     if (bytes < (1u << 20)) bytes = 1u << 20;
     if (bytes > h_pin_bytes) {
         QP_HIP(this, hipStreamSynchronize(stream));
-        if (h_pin) { (void)hipHostFree(h_pin); h_pin = nullptr; h_pin_bytes = 0; }
-        QP_HIP(this, hipHostMalloc(&h_pin, bytes, hipHostMallocDefault));
+        if (h_pin) { scrub_pinned(); track_free(h_pin); h_pin = nullptr; h_pin_bytes = 0; }
+        QP_HIP(this, track_host_malloc(&h_pin, bytes, residue::CTX_PINNED));
         h_pin_bytes = bytes;
     }
     return QPGPU_OK;
@@ -62,7 +66,7 @@ int qpgpu_ctx::read_back_2d(void *host_dst, const void *dev_src, size_t src_pitc
 
 int qpgpu_ctx::upload(const std::vector<uint64_t> &host, uint64_t **dptr) {
     void *p = nullptr;
-    QP_HIP(this, hipMalloc(&p, host.size() * sizeof(uint64_t)));
+    QP_HIP(this, track_malloc(&p, host.size() * sizeof(uint64_t), residue::TABLES));
     owned.push_back(p);
     // tables are tiny; the copy is ordered on the context's own stream (never the legacy null stream, which every proving
     // thread of a process shares) and waited for, so the pageable source may go out of scope

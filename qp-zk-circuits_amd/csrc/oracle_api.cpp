@@ -21,7 +21,7 @@ extern "C" void qpgpu_oracle_free(qpgpu_oracle *h) {
         // committed columns can hold the witness (reference wormhole/circuit/src/sensitive.rs:36-44): scrub before release
         (void)hipMemsetAsync(h->block, 0, h->block_words * 8, h->ctx->stream);
         (void)hipStreamSynchronize(h->ctx->stream);
-        (void)hipFree(h->block);
+        h->ctx->track_free(h->block);
     }
     delete h;
 }
@@ -50,7 +50,7 @@ int commit_impl(qpgpu_ctx *ctx, const uint64_t *const *polys, uint32_t batch, ui
                  w_salt = blinding ? (size_t)4 * lde_n : 0, w_eval = 2 + 2 * (size_t)num_polys;
     h->block_words = B * (w_coeffs + w_lde + w_dig + w_salt + w_eval + 4);
     void *v = nullptr;
-    hipError_t e = hipMalloc(&v, h->block_words * 8);
+    hipError_t e = ctx->track_malloc(&v, h->block_words * 8, residue::ORACLE);
     if (e != hipSuccess) { delete h; return ctx->hip_fail(e, "hipMalloc(oracle)"); }
     h->block = (u64 *)v;
     o.coeffs = h->block; o.lde = o.coeffs + B * w_coeffs; o.digests = o.lde + B * w_lde;

@@ -39,7 +39,16 @@ struct Job {
     std::vector<uint64_t> values;        // JOB_PARTIAL: copied at submit, wiped after use (they carry the spend secret)
 };
 struct Done { int rc = 1; size_t len = 0; std::string err; };   // rc 1 = pending
-struct Worker { int slot = 0, device = 0; qpgpu_ctx *ctx = nullptr; qpgpu_circuit *circ = nullptr; uint64_t *d_wit = nullptr; };
+// a request every worker carries out on its own context between two jobs (qpgpu_pool_scrub, qpgpu_pool_residue_scan)
+enum CtlKind : int { CTL_NONE = 0, CTL_SCRUB = 1, CTL_SCAN = 2 };
+struct Ctl {
+    int kind = CTL_NONE, rc = QPGPU_OK;
+    const uint64_t *needles = nullptr; size_t n_needles = 0, cap = 0; uint64_t region_mask = 0;   // CTL_SCAN
+    uint64_t hits = 0, bytes = 0;
+    std::vector<qpgpu_residue_hit> first;
+    std::string err;
+};
+struct Worker { int slot = 0, device = 0; qpgpu_ctx *ctx = nullptr; qpgpu_circuit *circ = nullptr; uint64_t *d_wit = nullptr; Ctl ctl; };
 void wipe(std::vector<uint64_t> &v) { volatile uint64_t *q = v.data(); for (size_t i = 0; i < v.size(); i++) q[i] = 0; }
 }  // namespace
 
@@ -48,7 +57,8 @@ struct qpgpu_pool {
     std::vector<Worker> workers;
     std::vector<std::thread> threads;
     std::mutex mu;
-    std::condition_variable cv_job, cv_done;
+    std::condition_variable cv_job, cv_done, cv_ctl;
+    std::mutex ctl_turn;             // one control request (scrub / scan) at a time
     std::deque<Job> queue;
     std::vector<Done> done;          // ring indexed by ticket % size
     uint64_t next_ticket = 0, oldest_live = 0;
@@ -81,6 +91,47 @@ void finish(qpgpu_pool *p, const std::vector<Job> &js, const std::vector<int> &r
     p->cv_done.notify_all();
 }
 
+// the worker's circuit workspace (with the stage s1 buffers, the context's scratch and bounce buffer) and its resident witnesses
+int scrub_worker(qpgpu_pool *p, Worker &w) {
+    if (hipSetDevice(w.device) != hipSuccess) return QPGPU_EDEVICE;
+    if (w.d_wit && w.ctx && hipMemsetAsync(w.d_wit, 0, p->wit_words * 8 * p->max_batch, w.ctx->stream) != hipSuccess) return QPGPU_EDEVICE;
+    return w.circ ? qpgpu_circuit_scrub(w.circ) : QPGPU_OK;      // waits for the stream
+}
+
+void run_ctl(qpgpu_pool *p, Worker &w) {
+    Ctl &c = w.ctl;
+    // under a queue-intercepting profiler one thread submits at a time: the same turn a job takes (qpgpu_pool::serialize)
+    std::unique_lock<std::mutex> turn(p->device_turn, std::defer_lock);
+    if (p->serialize) turn.lock();
+    if (c.kind == CTL_SCRUB) c.rc = scrub_worker(p, w);
+    else {
+        // the scan writes the hits it recorded and leaves the rest of the array alone: a region no buffer has marks those
+        qpgpu_residue_hit blank{}; blank.region = UINT32_MAX;
+        c.first.assign(c.cap, blank);
+        c.rc = qpgpu_ctx_residue_scan(w.ctx, c.needles, c.n_needles, c.region_mask, &c.hits, c.first.data(), c.cap, &c.bytes);
+        size_t written = 0;
+        while (written < c.first.size() && c.first[written].region != UINT32_MAX) written++;
+        c.first.resize(c.rc == QPGPU_OK ? written : 0);
+    }
+    if (c.rc != QPGPU_OK) c.err = qpgpu_last_error(w.ctx);
+    if (turn.owns_lock()) turn.unlock();
+    { std::lock_guard<std::mutex> lk(p->mu); c.kind = CTL_NONE; }
+    p->cv_ctl.notify_all();
+}
+
+// hands `proto` to every worker and waits until all have carried it out; the caller holds ctl_turn (and reads the results under it)
+int broadcast(qpgpu_pool *p, const Ctl &proto) {
+    std::unique_lock<std::mutex> lk(p->mu);
+    if (p->stopping) { p->err = "pool: shutting down"; return QPGPU_EINVAL; }
+    for (Worker &w : p->workers) w.ctl = proto;
+    lk.unlock();
+    p->cv_job.notify_all();
+    lk.lock();
+    p->cv_ctl.wait(lk, [&] { for (const Worker &w : p->workers) if (w.ctl.kind != CTL_NONE) return false; return true; });
+    for (const Worker &w : p->workers) if (w.ctl.rc != QPGPU_OK) { p->err = w.ctl.err; return w.ctl.rc; }
+    return QPGPU_OK;
+}
+
 void worker(qpgpu_pool *p, size_t wi) {
     Worker &w = p->workers[wi];
     (void)hipSetDevice(w.device);
@@ -92,10 +143,15 @@ void worker(qpgpu_pool *p, size_t wi) {
             auto mine = [&](const Job &j) { return j.slot < 0 || j.slot == w.slot; };
             auto first = [&]() { return std::find_if(p->queue.begin(), p->queue.end(), mine); };
             auto it = first();
-            while (it == p->queue.end()) {
+            while (it == p->queue.end() && w.ctl.kind == CTL_NONE) {
                 if (p->stopping) return;        // drained as far as this worker is concerned (jobs pinned elsewhere are their workers')
                 p->cv_job.wait(lk);
                 it = first();
+            }
+            if (w.ctl.kind != CTL_NONE) {       // between two jobs: a scrub or a scan of this worker's context, on its own thread
+                lk.unlock();
+                run_ctl(p, w);
+                continue;
             }
             // whatever is queued for this worker, up to the lockstep width, split evenly when several workers wait for little
             // work; a batch holds jobs of one kind
@@ -216,7 +272,7 @@ int ensure_workspace(qpgpu_pool *p) {
     if (p->host_witness) return QPGPU_OK;
     for (Worker &w : p->workers) {
         if (hipSetDevice(w.device) != hipSuccess) return QPGPU_EDEVICE;
-        if (hipMalloc((void **)&w.d_wit, p->wit_words * 8 * p->max_batch) != hipSuccess) { p->err = "pool: witness workspace allocation failed"; return QPGPU_EDEVICE; }
+        if (w.ctx->track_malloc((void **)&w.d_wit, p->wit_words * 8 * p->max_batch, residue::POOL_WITNESS) != hipSuccess) { p->err = "pool: witness workspace allocation failed"; return QPGPU_EDEVICE; }
     }
     p->host_witness = true;
     return QPGPU_OK;
@@ -257,11 +313,9 @@ void qpgpu_pool_destroy(qpgpu_pool *p) {
     for (auto &t : p->threads) if (t.joinable()) t.join();
     for (Worker &w : p->workers) {
         (void)hipSetDevice(w.device);
-        if (w.d_wit) {     // the workspace held witnesses: overwritten before release
-            (void)hipMemsetAsync(w.d_wit, 0, p->wit_words * 8 * p->max_batch, w.ctx ? w.ctx->stream : nullptr);
-            (void)hipStreamSynchronize(w.ctx ? w.ctx->stream : nullptr);
-            (void)hipFree(w.d_wit);
-        }
+        // the workspaces held witnesses: overwritten (as qpgpu_pool_scrub does) before anything is released
+        (void)scrub_worker(p, w);
+        if (w.ctx) { (void)hipStreamSynchronize(w.ctx->stream); w.ctx->track_free(w.d_wit); }
         if (w.circ) qpgpu_circuit_free(w.circ);
         if (w.ctx) qpgpu_ctx_destroy(w.ctx);
     }
@@ -319,6 +373,34 @@ int qpgpu_pool_set_witness_check(qpgpu_pool *p, int on) {
     std::lock_guard<std::mutex> lk(p->mu);
     if (!p->queue.empty() || p->next_ticket != p->oldest_live) { p->err = "pool_set_witness_check: jobs in flight"; return QPGPU_EINVAL; }
     for (Worker &w : p->workers) qpgpu_circuit_set_witness_check(w.circ, on);
+    return QPGPU_OK;
+}
+
+int qpgpu_pool_scrub(qpgpu_pool *p) {
+    if (!p) return QPGPU_EINVAL;
+    std::lock_guard<std::mutex> one(p->ctl_turn);
+    Ctl c; c.kind = CTL_SCRUB;
+    return broadcast(p, c);
+}
+
+int qpgpu_pool_residue_scan(qpgpu_pool *p, const uint64_t *needles, size_t n_needles, uint64_t region_mask,
+                            uint64_t *hits, qpgpu_residue_hit *first_hits, size_t cap, uint64_t *bytes_scanned) {
+    if (!p) return QPGPU_EINVAL;
+    if (cap && !first_hits) { std::lock_guard<std::mutex> lk(p->mu); p->err = "pool_residue_scan: cap without a first_hits array"; return QPGPU_EINVAL; }
+    std::lock_guard<std::mutex> one(p->ctl_turn);
+    Ctl c; c.kind = CTL_SCAN; c.needles = needles; c.n_needles = n_needles; c.region_mask = region_mask; c.cap = cap;
+    const int rc = broadcast(p, c);
+    if (rc != QPGPU_OK) return rc;
+    std::lock_guard<std::mutex> lk(p->mu);
+    uint64_t h = 0, b = 0;
+    bool copied = false;
+    for (Worker &w : p->workers) {
+        h += w.ctl.hits; b += w.ctl.bytes;
+        if (!copied && !w.ctl.first.empty()) { std::copy(w.ctl.first.begin(), w.ctl.first.end(), first_hits); copied = true; }
+        w.ctl.first.clear();
+    }
+    if (hits) *hits = h;
+    if (bytes_scanned) *bytes_scanned = b;
     return QPGPU_OK;
 }
 

@@ -44,8 +44,11 @@ int alloc_batch(qpgpu_circuit *c, PolyOracle &b, uint32_t ncols, uint32_t nb, bo
 
 void scrub(qpgpu_circuit *c) {
     for (auto &r : c->secret_allocs) (void)hipMemsetAsync(r.first, 0, r.second, c->ctx->stream);
+    witness_plan_scrub(c->wplan, c->ctx->stream);    // stage s1: public-input values and hash, prepared assignments and keys
+    c->ctx->scrub_scratch();                         // multi-pass transforms of witness columns wrote it
     (void)hipStreamSynchronize(c->ctx->stream);
     if (c->stage.h) std::memset(c->stage.h, 0, c->stage.words * 8);   // the staging ring held challenges and salt keys
+    c->ctx->scrub_pinned();                          // assignments went up and openings came back through the bounce buffer
 }
 
 // Replays, in planning mode, every transform a lockstep batch of max_batch proofs will issue (prove_batch_impl, fri_prove):
@@ -98,9 +101,9 @@ void qpgpu_circuit_free(qpgpu_circuit *c) {
     // the workspace held witness-derived data (reference wormhole/circuit/src/sensitive.rs:36-44): clear it before the
     // allocator can hand the memory to someone else
     scrub(c);                                    // includes the pinned staging ring
-    if (c->stage.h) (void)hipHostFree(c->stage.h);
-    for (void *p : c->allocs) (void)hipFree(p);
-    witness_plan_free(c->wplan);
+    c->ctx->track_free(c->stage.h);
+    for (void *p : c->allocs) c->ctx->track_free(p);
+    witness_plan_free(c->wplan, c->ctx);
     delete c;
 }
 
@@ -174,7 +177,7 @@ int qpgpu_circuit_load_batch(qpgpu_ctx *ctx, const uint64_t *pack_words, size_t 
         // test hook: a staging ring too small for anything sends every table through the synchronous bounce path of Stager::put
         if (const char *e = getenv("QPGPU_STAGE_FALLBACK")) if (*e == '1') c->stage.words = 1;
         void *hp = nullptr;
-        hipError_t e = hipHostMalloc(&hp, c->stage.words * 8, hipHostMallocDefault);
+        hipError_t e = ctx->track_host_malloc(&hp, c->stage.words * 8, residue::CIRCUIT_WORKSPACE);
         if (e != hipSuccess) return fail(ctx->hip_fail(e, "hipHostMalloc(stage)"));
         c->stage.h = (u64 *)hp;
     }

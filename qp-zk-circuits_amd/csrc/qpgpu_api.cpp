@@ -72,6 +72,7 @@ int qpgpu_ctx_create(int device, qpgpu_ctx **out) {
     qpgpu_ctx *c = new (std::nothrow) qpgpu_ctx();
     if (!c) return QPGPU_ENOMEM;
     c->device = device;
+    c->bind_residue_backend();
     c->hasher = hasher::process_default();   // the context's proof-system hasher; qpgpu_ctx_set_hasher changes it
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return QPGPU_EDEVICE; }
     c->own_stream = true;
@@ -83,13 +84,18 @@ void qpgpu_ctx_destroy(qpgpu_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (void *p : ctx->owned) (void)hipFree(p);
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->d_p2) (void)hipFree(ctx->d_p2);
-    if (ctx->d_p2_app) (void)hipFree(ctx->d_p2_app);
-    if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
-    if (ctx->vd_pin) (void)hipHostFree(ctx->vd_pin);
-    if (ctx->vd_dev) (void)hipFree(ctx->vd_dev);
+    // the scratch and the bounce buffer may hold witness-derived words of calls that do not scrub (the _dev entries)
+    ctx->scrub_scratch();
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->scrub_pinned();
+    for (void *p : ctx->owned) ctx->track_free(p);
+    ctx->track_free(ctx->scratch);
+    ctx->track_free(ctx->d_p2);
+    ctx->track_free(ctx->d_p2_app);
+    ctx->track_free(ctx->h_pin);
+    ctx->track_free(ctx->vd_pin);
+    ctx->track_free(ctx->vd_dev);
+    if (ctx->d_residue) (void)hipFree(ctx->d_residue);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }

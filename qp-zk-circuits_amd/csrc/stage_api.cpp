@@ -32,7 +32,7 @@ struct qpgpu_stage_plan {
     int alloc(u64 **p, size_t count, bool secret) {
         void *v = nullptr;
         const size_t bytes = std::max<size_t>(count * 8, 8);
-        hipError_t e = hipMalloc(&v, bytes);
+        hipError_t e = ctx->track_malloc(&v, bytes, secret ? residue::STAGE_PLAN : residue::CIRCUIT_SETUP);
         if (e == hipErrorOutOfMemory) return ctx->fail(QPGPU_ENOMEM, "hipMalloc(stage plan): out of device memory");
         if (e != hipSuccess) return ctx->hip_fail(e, "hipMalloc(stage plan)");
         allocs.push_back(v);
@@ -87,8 +87,8 @@ void qpgpu_stage_plan_free(qpgpu_stage_plan *pl) {
     (void)hipSetDevice(pl->ctx->device);
     (void)hipStreamSynchronize(pl->ctx->stream);
     pl->scrub();
-    if (pl->stage.h) (void)hipHostFree(pl->stage.h);
-    for (void *p : pl->allocs) (void)hipFree(p);
+    pl->ctx->track_free(pl->stage.h);
+    for (void *p : pl->allocs) pl->ctx->track_free(p);
     delete pl;
 }
 
@@ -144,7 +144,7 @@ int qpgpu_stage_plan_create_batch(qpgpu_ctx *ctx, const uint64_t *words, size_t 
     {
         pl->stage.words = 2 * stage_ring_words(pl->tab, max_batch) + 64;    // s6 puts the beta part again, then the alpha part and the check's seed
         void *hp = nullptr;
-        const hipError_t e = hipHostMalloc(&hp, pl->stage.words * 8, hipHostMallocDefault);
+        const hipError_t e = ctx->track_host_malloc(&hp, pl->stage.words * 8, residue::STAGE_PLAN);
         if (e != hipSuccess) return fail(ctx->hip_fail(e, "hipHostMalloc(stage plan)"));
         pl->stage.h = (u64 *)hp;
     }

@@ -18,6 +18,7 @@
 #include "circuit_state.hpp"
 #include "witness.hpp"
 #include "prover_kernels.hpp"
+#include "residue_kernels.hpp"
 
 using gl::u64;
 
@@ -45,6 +46,7 @@ struct WitnessPlan {
     // public-input cells (pack trailer "PUBI1"): stage s1 writes the caller's public inputs there
     uint32_t *d_pi_idx = nullptr;            // flat cell (column * n + row) of public input i
     u64 *d_pi_vals = nullptr;                // [pi_cap][num_public_inputs]
+    size_t pi_vals_bytes = 0;                // its allocation
     // partial-witness entry: host view of the copy classes and growable device staging
     std::vector<uint32_t> h_src_of;          // [n][num_routed] -> flat source cell of the copy class
     std::vector<uint8_t> generated;          // [num_wires][n]: 1 = a generator produces this cell (or its copy class)
@@ -78,31 +80,38 @@ struct PartialPrep {
     uint32_t *d_scatter_idx = nullptr, *d_check_idx = nullptr, *d_keys = nullptr;   // d_keys: [cap][8], ChaCha20 keys of device-drawn values
     u64 *d_scatter_val = nullptr, *d_check_val = nullptr;   // [cap][count]
     uint32_t cap = 0;
+    size_t scatter_val_bytes = 0, check_val_bytes = 0, keys_bytes = 0;     // sizes of the three value buffers
     bool valid = false, with_pis = true;          // with_pis: the public-input cells are assignments too (values supplied by the caller)
-    void release() {
-        for (void *q : {(void *)d_scatter_idx, (void *)d_check_idx, (void *)d_scatter_val, (void *)d_check_val, (void *)d_keys}) if (q) (void)hipFree(q);
+    // the values and keys of the last call: zero fill behind their last readers on `st`
+    void scrub(hipStream_t st) {
+        if (d_scatter_val) (void)hipMemsetAsync(d_scatter_val, 0, scatter_val_bytes, st);
+        if (d_check_val) (void)hipMemsetAsync(d_check_val, 0, check_val_bytes, st);
+        if (d_keys) (void)hipMemsetAsync(d_keys, 0, keys_bytes, st);
+    }
+    // the caller has waited for the stream
+    void release(qpgpu_ctx *ctx) {
+        if (d_scatter_val || d_check_val || d_keys) { scrub(ctx->stream); (void)hipStreamSynchronize(ctx->stream); }
+        for (void *q : {(void *)d_scatter_idx, (void *)d_check_idx, (void *)d_scatter_val, (void *)d_check_val, (void *)d_keys}) ctx->track_free(q);
         d_scatter_idx = d_check_idx = d_keys = nullptr; d_scatter_val = d_check_val = nullptr; cap = 0;
+        scatter_val_bytes = check_val_bytes = keys_bytes = 0;
     }
 };
 
-void witness_plan_free(WitnessPlan *p) {
+void witness_plan_scrub(WitnessPlan *p, hipStream_t st) {
     if (!p) return;
-    if (p->d_src_of) (void)hipFree(p->d_src_of);
-    if (p->d_insts) (void)hipFree(p->d_insts);
-    if (p->d_level_start) (void)hipFree(p->d_level_start);
-    if (p->d_level_poseidon) (void)hipFree(p->d_level_poseidon);
-    if (p->d_pi_hash) (void)hipFree(p->d_pi_hash);
-    if (p->d_hints) (void)hipFree(p->d_hints);
-    if (p->d_pi_idx) (void)hipFree(p->d_pi_idx);
-    if (p->d_pi_vals) (void)hipFree(p->d_pi_vals);
-    if (p->d_pair_idx) (void)hipFree(p->d_pair_idx);
-    if (p->d_pair_val) (void)hipFree(p->d_pair_val);
-    if (p->d_check_own) (void)hipFree(p->d_check_own);
-    if (p->d_check_src) (void)hipFree(p->d_check_src);
-    if (p->d_nz_a) (void)hipFree(p->d_nz_a);
-    if (p->d_nz_b) (void)hipFree(p->d_nz_b);
-    if (p->d_err) (void)hipFree(p->d_err);
-    if (p->prep) { p->prep->release(); delete p->prep; }
+    if (p->d_pi_hash) (void)hipMemsetAsync(p->d_pi_hash, 0, (size_t)p->pi_cap * 32, st);
+    if (p->d_pi_vals) (void)hipMemsetAsync(p->d_pi_vals, 0, p->pi_vals_bytes, st);
+    if (p->prep) p->prep->scrub(st);
+}
+
+void witness_plan_free(WitnessPlan *p, qpgpu_ctx *ctx) {
+    if (!p) return;
+    witness_plan_scrub(p, ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (void *q : {(void *)p->d_src_of, (void *)p->d_insts, (void *)p->d_level_start, (void *)p->d_level_poseidon, (void *)p->d_pi_hash, (void *)p->d_hints,
+                    (void *)p->d_pi_idx, (void *)p->d_pi_vals, (void *)p->d_pair_idx, (void *)p->d_pair_val, (void *)p->d_check_own, (void *)p->d_check_src,
+                    (void *)p->d_nz_a, (void *)p->d_nz_b, (void *)p->d_err}) ctx->track_free(q);
+    if (p->prep) { p->prep->release(ctx); delete p->prep; }
     delete p;
 }
 
@@ -405,7 +414,7 @@ std::string build_plan(qpgpu_circuit *c, WitnessPlan &plan, const std::vector<u6
     // ---- device copies ----
     qpgpu_ctx *ctx = c->ctx;
     auto up = [&](const void *src, size_t bytes, void **dst) -> bool {
-        if (hipMalloc(dst, std::max<size_t>(bytes, 8)) != hipSuccess) return false;
+        if (ctx->track_malloc(dst, std::max<size_t>(bytes, 8), residue::WITNESS_PLAN) != hipSuccess) return false;
         return hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
     };
     if (!up(src_of.data(), src_of.size() * 4, (void **)&plan.d_src_of)) return "witness plan: device allocation failed";
@@ -476,7 +485,7 @@ int ensure_plan(qpgpu_circuit *c, const std::vector<u64> *assigned = nullptr, si
         for (size_t i = pi_prefix; i < assigned->size() && !hints; i++) { const u64 cell = (*assigned)[i]; hints = cell < NW * n && d.generated[(cell % NW) * n + cell / NW]; }
         if (!hints) { c->wplan->decided_for = *assigned; return QPGPU_OK; }
     }
-    if (c->wplan) { QP_HIP(c->ctx, hipStreamSynchronize(c->ctx->stream)); witness_plan_free(c->wplan); c->wplan = nullptr; }
+    if (c->wplan) { QP_HIP(c->ctx, hipStreamSynchronize(c->ctx->stream)); witness_plan_free(c->wplan, c->ctx); c->wplan = nullptr; }
     WitnessPlan *plan = new WitnessPlan();
     std::string err = build_plan(c, *plan);
     if (assigned) {
@@ -488,11 +497,11 @@ int ensure_plan(qpgpu_circuit *c, const std::vector<u64> *assigned = nullptr, si
         if (want_aware) {
             WitnessPlan *aware = new WitnessPlan();
             const std::string err2 = build_plan(c, *aware, assigned);
-            if (err2.empty() && (!err.empty() || aware->level_start.size() < plan->level_start.size())) { witness_plan_free(plan); plan = aware; err.clear(); }
-            else { witness_plan_free(aware); if (!err.empty()) err = err2.empty() ? err : err2; }
+            if (err2.empty() && (!err.empty() || aware->level_start.size() < plan->level_start.size())) { witness_plan_free(plan, c->ctx); plan = aware; err.clear(); }
+            else { witness_plan_free(aware, c->ctx); if (!err.empty()) err = err2.empty() ? err : err2; }
         }
     }
-    if (!err.empty()) { witness_plan_free(plan); return c->ctx->fail(QPGPU_EINVAL, err); }
+    if (!err.empty()) { witness_plan_free(plan, c->ctx); return c->ctx->fail(QPGPU_EINVAL, err); }
     if (assigned) plan->decided_for = *assigned;
     c->wplan = plan;
     return QPGPU_OK;
@@ -561,16 +570,36 @@ std::string prepare_partial(const CircuitPack &p, const WitnessPlan &plan, const
     for (size_t i = 0; i < count; i++) { const std::string e = assign(cells[i], npis + (uint32_t)i); if (!e.empty()) return e; }
     return "";
 }
+// the plan's per-witness buffers (public-input values and hash; with_err: the check results too) for `batch` witnesses. The old
+// ones are overwritten before they go back to the allocator.
+int grow_pi(qpgpu_ctx *ctx, WitnessPlan &plan, uint32_t batch, size_t npis, bool with_err) {
+    witness_plan_scrub(&plan, ctx->stream);
+    QP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->track_free(plan.d_pi_hash); plan.d_pi_hash = nullptr;
+    ctx->track_free(plan.d_pi_vals); plan.d_pi_vals = nullptr;
+    plan.pi_cap = 0; plan.pi_vals_bytes = 0;
+    if (with_err) { ctx->track_free(plan.d_err); plan.d_err = nullptr; plan.err_cap = 0; }
+    const size_t vals_bytes = std::max<size_t>((size_t)batch * npis * 8, 8);
+    QP_HIP(ctx, ctx->track_malloc((void **)&plan.d_pi_hash, (size_t)batch * 32, residue::WITNESS_PLAN));
+    QP_HIP(ctx, ctx->track_malloc((void **)&plan.d_pi_vals, vals_bytes, residue::WITNESS_PLAN));
+    plan.pi_vals_bytes = vals_bytes;
+    if (with_err) QP_HIP(ctx, ctx->track_malloc((void **)&plan.d_err, (size_t)batch * 16, residue::WITNESS_PLAN));
+    plan.pi_cap = batch;
+    if (with_err) plan.err_cap = batch;
+    return QPGPU_OK;
+}
+
 int prep_device(qpgpu_ctx *ctx, PartialPrep &pp, uint32_t batch) {
     if (pp.cap >= batch && pp.d_scatter_idx) return QPGPU_OK;
     QP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    pp.release();
+    pp.release(ctx);
     const size_t ns = std::max<size_t>(pp.scatter_idx.size(), 1), nc = std::max<size_t>(pp.check_idx.size(), 1);
-    QP_HIP(ctx, hipMalloc((void **)&pp.d_scatter_idx, ns * 4));
-    QP_HIP(ctx, hipMalloc((void **)&pp.d_check_idx, nc * 4));
-    QP_HIP(ctx, hipMalloc((void **)&pp.d_scatter_val, ns * 8 * batch));
-    QP_HIP(ctx, hipMalloc((void **)&pp.d_check_val, nc * 8 * batch));
-    QP_HIP(ctx, hipMalloc((void **)&pp.d_keys, (size_t)32 * batch));
+    pp.scatter_val_bytes = ns * 8 * batch; pp.check_val_bytes = nc * 8 * batch; pp.keys_bytes = (size_t)32 * batch;
+    QP_HIP(ctx, ctx->track_malloc((void **)&pp.d_scatter_idx, ns * 4, residue::PARTIAL_WITNESS));
+    QP_HIP(ctx, ctx->track_malloc((void **)&pp.d_check_idx, nc * 4, residue::PARTIAL_WITNESS));
+    QP_HIP(ctx, ctx->track_malloc((void **)&pp.d_scatter_val, pp.scatter_val_bytes, residue::PARTIAL_WITNESS));
+    QP_HIP(ctx, ctx->track_malloc((void **)&pp.d_check_val, pp.check_val_bytes, residue::PARTIAL_WITNESS));
+    QP_HIP(ctx, ctx->track_malloc((void **)&pp.d_keys, pp.keys_bytes, residue::PARTIAL_WITNESS));
     if (!pp.scatter_idx.empty()) QP_HIP(ctx, hipMemcpyAsync(pp.d_scatter_idx, pp.scatter_idx.data(), pp.scatter_idx.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     if (!pp.check_idx.empty()) QP_HIP(ctx, hipMemcpyAsync(pp.d_check_idx, pp.check_idx.data(), pp.check_idx.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     QP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -620,17 +649,7 @@ int generate_batch(qpgpu_circuit *c, uint64_t *d_wires, uint32_t batch, const ui
                 }
         }
     const bool pair_checks = !plan.h_check_own.empty(), val_checks = pp && !pp->check_idx.empty(), nz_checks = !plan.h_nz_a.empty();
-    if (plan.pi_cap < batch || (plan.err_cap < batch)) {
-        QP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (plan.d_pi_hash) { (void)hipFree(plan.d_pi_hash); plan.d_pi_hash = nullptr; }
-        if (plan.d_pi_vals) { (void)hipFree(plan.d_pi_vals); plan.d_pi_vals = nullptr; }
-        if (plan.d_err) { (void)hipFree(plan.d_err); plan.d_err = nullptr; }
-        plan.pi_cap = 0; plan.err_cap = 0;
-        QP_HIP(ctx, hipMalloc((void **)&plan.d_pi_hash, (size_t)batch * 32));
-        QP_HIP(ctx, hipMalloc((void **)&plan.d_pi_vals, std::max<size_t>((size_t)batch * npis * 8, 8)));
-        QP_HIP(ctx, hipMalloc((void **)&plan.d_err, (size_t)batch * 16));
-        plan.pi_cap = batch; plan.err_cap = batch;
-    }
+    if (plan.pi_cap < batch || (plan.err_cap < batch)) QP_TRY(grow_pi(ctx, plan, batch, npis, true));
     if (pp) QP_TRY(prep_device(ctx, *pp, batch));
     // everything the host sends goes up through the context's pinned bounce buffer and a copy kernel (ctx.hpp: read_back)
     const size_t ns = pp ? pp->scatter_idx.size() : 0, nc = pp ? pp->check_idx.size() : 0;
@@ -639,6 +658,20 @@ int generate_batch(qpgpu_circuit *c, uint64_t *d_wires, uint32_t batch, const ui
     QP_TRY(ctx->reserve_read_back(pi_bytes + hash_bytes + sc_bytes + ck_bytes + key_bytes + (size_t)batch * 8));
     QP_HIP(ctx, hipStreamSynchronize(ctx->stream));       // nothing of an earlier call still reads the bounce buffer
     u64 *bounce = (u64 *)ctx->h_pin;
+    // From here on the bounce buffer and the prepared value buffers hold the caller's assignments (the spend secret among them)
+    // and the ChaCha keys. They go again on every way out: on the ordinary one by fills queued behind their last readers (no
+    // synchronisation of its own: the next host write to the bounce buffer waits for the stream as the line above does), on an
+    // early return by this guard, which waits for the stream first.
+    struct Wipe {
+        qpgpu_ctx *ctx; PartialPrep *pp; u64 *bounce; size_t bytes; bool queued;
+        ~Wipe() {
+            if (queued) return;
+            (void)hipStreamSynchronize(ctx->stream);
+            volatile u64 *z = bounce;
+            for (size_t i = 0; i < bytes / 8; i++) z[i] = 0;
+            if (pp) { pp->scrub(ctx->stream); (void)hipStreamSynchronize(ctx->stream); }
+        }
+    } wipe{ctx, pp, bounce, pi_bytes + hash_bytes + sc_bytes + ck_bytes + key_bytes, false};
     if (pp) QP_HIP(ctx, hipMemsetAsync(d_wires, 0, (size_t)batch * stride * 8, ctx->stream));
     if (pi_bytes) std::memcpy(bounce, public_inputs, pi_bytes);
     u64 *pih = bounce + pi_bytes / 8;
@@ -712,6 +745,11 @@ int generate_batch(qpgpu_circuit *c, uint64_t *d_wires, uint32_t batch, const ui
     if (nz_checks) QP_HIP(ctx, wk_check_nonzero(d_wires, plan.d_nz_a, plan.d_nz_b, (uint32_t)plan.h_nz_a.size(), batch, stride, plan.d_err, 2, ctx->stream));
     QP_HIP(ctx, wk_fill_copies(a, batch, ctx->stream));
     ctx->prof_end();
+    // the last readers of the uploaded values are behind us on the stream (wk_scatter, pk_random_felts, wk_check_vals and the copy
+    // kernels that pulled the bounce buffer in): a few KB of fills, ordered after them
+    QP_HIP(ctx, rk_zero(wipe.bounce, wipe.bytes, ctx->stream));
+    if (pp) pp->scrub(ctx->stream);
+    wipe.queued = true;
     if (pair_checks || val_checks || nz_checks) {
         std::vector<uint32_t> err((size_t)batch * 4);
         QP_TRY(ctx->read_back(err.data(), plan.d_err, err.size() * 4));
@@ -729,11 +767,7 @@ int generate_batch(qpgpu_circuit *c, uint64_t *d_wires, uint32_t batch, const ui
             }
         }
     }
-    if (n_blind) {   // the keys are secrets: the device has read the bounce buffer (the launches above are ordered before this sync)
-        QP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        volatile u64 *kz = keyv;
-        for (size_t i = 0; i < key_bytes / 8; i++) kz[i] = 0;
-    }
+    if (n_blind) QP_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the keys are secrets: gone from the bounce buffer and the device when this returns
     return overall;
 }
 
@@ -745,7 +779,7 @@ int ensure_prep(qpgpu_circuit *c, const uint64_t *cells, size_t count, uint32_t 
     PartialPrep &pp = *plan.prep;
     if (!pp.valid || pp.with_pis != with_pis || pp.cells.size() != count || (count && std::memcmp(pp.cells.data(), cells, count * 8) != 0)) {
         QP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        pp.release();
+        pp.release(ctx);
         const std::string err = prepare_partial(c->pack, plan, cells, count, pp, with_pis);
         if (!err.empty()) { pp.valid = false; return ctx->fail(QPGPU_EINVAL, err); }
         pp.valid = true;
@@ -814,17 +848,7 @@ int qpgpu_witness_partial_prepare(qpgpu_circuit *c, const uint64_t *cells, size_
     QP_TRY(ensure_prep(c, cells, count, max_batch));
     WitnessPlan &plan = *c->wplan;
     // size what generation will need, so that the calls themselves neither allocate nor free
-    if (plan.pi_cap < max_batch || plan.err_cap < max_batch) {
-        QP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (plan.d_pi_hash) { (void)hipFree(plan.d_pi_hash); plan.d_pi_hash = nullptr; }
-        if (plan.d_pi_vals) { (void)hipFree(plan.d_pi_vals); plan.d_pi_vals = nullptr; }
-        if (plan.d_err) { (void)hipFree(plan.d_err); plan.d_err = nullptr; }
-        plan.pi_cap = 0; plan.err_cap = 0;
-        QP_HIP(ctx, hipMalloc((void **)&plan.d_pi_hash, (size_t)max_batch * 32));
-        QP_HIP(ctx, hipMalloc((void **)&plan.d_pi_vals, std::max<size_t>((size_t)max_batch * c->pack.num_public_inputs * 8, 8)));
-        QP_HIP(ctx, hipMalloc((void **)&plan.d_err, (size_t)max_batch * 16));
-        plan.pi_cap = max_batch; plan.err_cap = max_batch;
-    }
+    if (plan.pi_cap < max_batch || plan.err_cap < max_batch) QP_TRY(grow_pi(ctx, plan, max_batch, c->pack.num_public_inputs, true));
     const PartialPrep &pp = *plan.prep;
     return ctx->reserve_read_back((size_t)max_batch * (c->pack.num_public_inputs + 4 + pp.scatter_idx.size() + pp.check_idx.size() + 1) * 8);
 }
@@ -877,15 +901,7 @@ int qpgpu_witness_public_inputs_dev(qpgpu_circuit *c, const uint64_t *d_wires, u
     if (p.pi_cells.size() != npis) return ctx->fail(QPGPU_EINVAL, "witness_public_inputs: the circuit pack carries no public-input cell trailer");
     if (!c->wplan) QP_TRY(ensure_plan(c));        // (the public-input cells are the same in a plan of either kind)
     WitnessPlan &plan = *c->wplan;
-    if (plan.pi_cap < batch) {
-        QP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (plan.d_pi_vals) { (void)hipFree(plan.d_pi_vals); plan.d_pi_vals = nullptr; }
-        if (plan.d_pi_hash) { (void)hipFree(plan.d_pi_hash); plan.d_pi_hash = nullptr; }
-        plan.pi_cap = 0;
-        QP_HIP(ctx, hipMalloc((void **)&plan.d_pi_hash, (size_t)batch * 32));
-        QP_HIP(ctx, hipMalloc((void **)&plan.d_pi_vals, (size_t)batch * npis * 8));
-        plan.pi_cap = batch;
-    }
+    if (plan.pi_cap < batch) QP_TRY(grow_pi(ctx, plan, batch, npis, false));
     const u64 stride = p.num_wires * p.n();
     for (uint32_t b = 0; b < batch; b++) QP_HIP(ctx, wk_gather(d_wires + (size_t)b * stride, plan.d_pi_idx, plan.d_pi_vals + (size_t)b * npis, (uint32_t)npis, ctx->stream));
     return ctx->read_back(public_inputs_out, plan.d_pi_vals, (size_t)batch * npis * 8);
@@ -902,6 +918,7 @@ int qpgpu_generate_witness(qpgpu_circuit *c, uint64_t *wires, const uint64_t *pu
     QP_TRY(qpgpu_generate_witness_dev(c, c->d_wires_vals, public_inputs));
     QP_HIP(ctx, hipMemcpyAsync(wires, c->d_wires_vals, bytes, hipMemcpyDeviceToHost, ctx->stream));
     QP_HIP(ctx, hipMemsetAsync(c->d_wires_vals, 0, bytes, ctx->stream));   // the witness carries the spend secret
+    witness_plan_scrub(c->wplan, ctx->stream);                             // and the plan's copies of what went into it
     QP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return QPGPU_OK;
 }

@@ -101,7 +101,8 @@ int build_tree(qpgpu_ctx *ctx, const void *leaves, const zk_tree::Plan &plan, ui
     qpgpu_zk_tree *t = new (std::nothrow) qpgpu_zk_tree;
     if (!t) return refuse(ctx, err, QPGPU_ENOMEM, what, "out of host memory");
     t->ctx = ctx; t->plan = plan; t->capacity = capacity; t->reserved = reserved; t->d_nodes = d_nodes;
-    nodes.p = nullptr;               // owned by the handle from here
+    nodes.p = nullptr;               // owned by the handle from here, and listed with the context (residue.hpp)
+    ctx->mem.add(d_nodes, node_bytes + sizeof(Aux), residue::ZK_TREE, false);
     *out = t;
     return QPGPU_OK;
 }
@@ -153,7 +154,7 @@ int qpgpu_zk_tree_build_reserved(qpgpu_ctx *ctx, const void *leaves, size_t coun
 
 void qpgpu_zk_tree_free(qpgpu_zk_tree *t) {
     if (!t) return;
-    if (t->d_nodes && hipSetDevice(t->ctx->device) == hipSuccess) (void)hipFree(t->d_nodes);
+    if (t->d_nodes && hipSetDevice(t->ctx->device) == hipSuccess) t->ctx->track_free(t->d_nodes);
     delete t;
 }
 

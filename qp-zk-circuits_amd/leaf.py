@@ -9,6 +9,7 @@
 library's native builder (csrc/builder.hpp, csrc/leaf_circuit.cpp); see the header for what cannot match the fork offline.
 """
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -500,6 +501,7 @@ class LeafProver:
         h = pkg.pack_header(circuit.pack)
         self.shape = (h["num_wires"], 1 << h["degree_bits"])
         self.d_wires = gpu.alloc(self.shape[0] * self.shape[1] * 8)
+        self._pools = []
 
     def generate_witness(self, inputs):
         nb = self.circuit.blinding_cells.size
@@ -534,7 +536,17 @@ class LeafProver:
         except Exception:
             pool.close()
             raise
+        self._pools = [r for r in self._pools if r() is not None and r().h] + [weakref.ref(pool)]     # for scrub(); the caller owns the pool
         return pool
+
+    def scrub(self):
+        """Overwrites what the last proofs left on the device: the prover's own circuit workspace and, for every open pool made by
+        pool(), each worker's workspace, resident witnesses and partial-witness buffers (ProvingPool.scrub)."""
+        self.circ.scrub()
+        for r in self._pools:
+            p = r()
+            if p is not None and p.h:
+                p.scrub()
 
     def submit(self, pool, inputs):
         """commit(inputs) queued on a pool made by pool(): the ticket for pool.wait(), which raises QpGpuError(-4) for inputs the
