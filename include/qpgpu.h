@@ -339,6 +339,37 @@ int qpgpu_oracle_device_ptrs(const qpgpu_oracle *o, const uint64_t **d_coeffs, c
 int qpgpu_oracle_open(qpgpu_oracle *o, const uint64_t *indices, size_t n, uint64_t *rows_out, uint64_t *paths_out);
 size_t qpgpu_oracle_leaf_width(const qpgpu_oracle *o);   /* num_polys, + 4 for a blinded oracle */
 
+/* ---- one commitment across several contexts: coset sharding ----------------------------------------------------
+ * qpgpu_oracle_commit over G = n_ctx contexts, on different devices or on the same one. G is a power of two with
+ * 2 <= G <= 2^rate_bits; the contexts are distinct and have the same hasher (n_ctx = 1 is QPGPU_EINVAL naming qpgpu_oracle_commit).
+ * Shard g runs on ctxs[g] and owns the leaves [g N/G, (g + 1) N/G), N = 2^(degree_bits + rate_bits): whole cosets of the LDE
+ * (those k with brev_rate_bits(k) >> (rate_bits - log2 G) == g) and a whole subtree. It gets a copy of the coefficients (1 / 2^rate_bits
+ * of the LDE; a peer copy between devices, no peer-access setting is read or changed), transforms, salts and hashes its leaves and
+ * reduces them to its max(1, 2^cap_height / G) roots alone. ctxs[0] is the home context: `polys` with QPGPU_ORACLE_DEVICE_INPUT
+ * lies on its device, it keeps the coefficients (qpgpu_oracle_eval, QPGPU_ORACLE_READ_COEFFS and the FRI arithmetic read them
+ * there), and when G > 2^cap_height it hashes the log2 G - cap_height levels above the shards' roots. Other arguments, flags and
+ * limits are qpgpu_oracle_commit's, and so is the result: the cap, the salts (drawn at the global leaf index), every leaf and every
+ * path are word for word those of qpgpu_oracle_commit with the same arguments.
+ * The calling thread drives all G streams and has synchronised them when the call returns; the threading rule of a context holds
+ * for all G contexts during this and every later call on the oracle. Errors are reported on ctxs[0]. NULL ctxs, ctxs[i] or out:
+ * QPGPU_EINVAL; *out is NULL after any failure.
+ * On a sharded oracle qpgpu_oracle_cap, _leaf_width, _eval, _read (the LDE: the shards' blocks in leaf order), _open (each index
+ * goes to its shard, one gather per shard on that shard's stream, results in the caller's order) and _free (every shard scrubbed
+ * on its own context) work as on any oracle, and so do qpgpu_fri_prove, qpgpu_fri_begin .. qpgpu_fri_open and
+ * qpgpu_fri_proof_size over any mix of sharded and plain oracles, with the same bytes; their ctx must be the home context of
+ * every sharded oracle. qpgpu_oracle_device_ptrs is QPGPU_EINVAL naming qpgpu_oracle_shard_device_ptrs; qpgpu_stage_plan_create*,
+ * qpgpu_stage_quotient*, qpgpu_oracle_eval_batch, _open_batch, qpgpu_fri_prove_batch and _begin_batch are QPGPU_EINVAL saying
+ * that sharded oracles are not taken there yet: none of them reads shard 0 as if it were the whole. */
+int qpgpu_oracle_commit_sharded(qpgpu_ctx *const *ctxs, uint32_t n_ctx, const uint64_t *polys, uint32_t num_polys,
+                                unsigned degree_bits, unsigned rate_bits, unsigned cap_height, unsigned flags,
+                                uint64_t blinding_seed, uint32_t blinding_stream, qpgpu_oracle **out);
+uint32_t qpgpu_oracle_shards(const qpgpu_oracle *o);            /* 1 for every other oracle */
+/* shard's leaves [*first_leaf, *first_leaf + *num_leaves); any oracle is its own shard 0. Either out may be NULL. */
+int qpgpu_oracle_shard_range(const qpgpu_oracle *o, uint32_t shard, uint64_t *first_leaf, uint64_t *num_leaves);
+/* on the shard's device: its LDE [num_polys][num_leaves] in leaf order, and its subtree's digests from the leaf layer up to its
+ * roots (qpgpu_merkle_digest_count(log2 num_leaves, max(0, cap_height - log2 G)) digests). Either out may be NULL. */
+int qpgpu_oracle_shard_device_ptrs(const qpgpu_oracle *o, uint32_t shard, const uint64_t **d_lde, const uint64_t **d_digests);
+
 /* ---- lockstep batches of the stage flow: one call per stage for `batch` proofs of one circuit ------------------
  * qpgpu_prove_batch_dev launches every stage once for up to max_batch proofs; the entries below give the stage route the same
  * batch dimension, on the same launch sequences (proof = grid.z or a folded leading dimension), so a patched prove() that keeps its

@@ -103,6 +103,13 @@ extern "C" {
     // challenger, the proof-of-work rule and the query indices kept in Rust. qpgpu_fri_prove is the one-call form; use it unless the
     // fork's prove_openings differs from what DESIGN.md section 9 lists. `Oracle::open` and `FriSession` below wrap these.
     pub fn qpgpu_oracle_leaf_width(o: *const QpgpuOracle) -> usize;
+    // one commitment over n_ctx contexts (one per device; ctxs[0] is the home context): the leaves are split by cosets, cap / eval /
+    // open / qpgpu_fri_prove on the home context answer as for any oracle, with the same bytes
+    pub fn qpgpu_oracle_commit_sharded(ctxs: *const *mut QpgpuCtx, n_ctx: u32, polys: *const u64, num_polys: u32, degree_bits: u32, rate_bits: u32,
+                                       cap_height: u32, flags: u32, blinding_seed: u64, blinding_stream: u32, out: *mut *mut QpgpuOracle) -> i32;
+    pub fn qpgpu_oracle_shards(o: *const QpgpuOracle) -> u32;
+    pub fn qpgpu_oracle_shard_range(o: *const QpgpuOracle, shard: u32, first_leaf: *mut u64, num_leaves: *mut u64) -> i32;
+    pub fn qpgpu_oracle_shard_device_ptrs(o: *const QpgpuOracle, shard: u32, d_lde: *mut *const u64, d_digests: *mut *const u64) -> i32;
     pub fn qpgpu_oracle_open(o: *mut QpgpuOracle, indices: *const u64, n: usize, rows_out: *mut u64, paths_out: *mut u64) -> i32;
     pub fn qpgpu_fri_begin(ctx: *mut QpgpuCtx, oracles: *const *mut QpgpuOracle, n: u32, batches: *const QpgpuFriBatch, n_batches: u32,
                            params: *const QpgpuFriParams, alpha: *const u64, out: *mut *mut QpgpuFriSession) -> i32;

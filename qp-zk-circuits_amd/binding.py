@@ -158,6 +158,11 @@ def load_library():
         "qpgpu_oracle_device_ptrs": (c.c_int, [vp, c.POINTER(vp), c.POINTER(vp), c.POINTER(vp)]),
         "qpgpu_oracle_open": (c.c_int, [vp, u64p, c.c_size_t, u64p, u64p]),
         "qpgpu_oracle_leaf_width": (c.c_size_t, [vp]),
+        "qpgpu_oracle_commit_sharded": (c.c_int, [c.POINTER(vp), c.c_uint32, u64p, c.c_uint32, c.c_uint, c.c_uint, c.c_uint, c.c_uint,
+                                                  c.c_uint64, c.c_uint32, c.POINTER(vp)]),
+        "qpgpu_oracle_shards": (c.c_uint32, [vp]),
+        "qpgpu_oracle_shard_range": (c.c_int, [vp, c.c_uint32, c.POINTER(c.c_uint64), c.POINTER(c.c_uint64)]),
+        "qpgpu_oracle_shard_device_ptrs": (c.c_int, [vp, c.c_uint32, c.POINTER(vp), c.POINTER(vp)]),
         "qpgpu_stage_plan_create": (c.c_int, [vp, u64p, c.c_size_t, vp, c.POINTER(vp), c.c_char_p]),
         "qpgpu_stage_plan_free": (None, [vp]),
         "qpgpu_stage_plan_info": (c.c_int, [vp, c.POINTER(c.c_uint), c.POINTER(c.c_uint), c.POINTER(c.c_uint), c.POINTER(c.c_uint),
@@ -845,6 +850,51 @@ class PolyOracle:
         self.h = h
         assert int(gpu.lib.qpgpu_oracle_batch(h)) == self.batch
         return self
+
+    @classmethod
+    def commit_sharded(cls, gpus, polys, rate_bits=3, cap_height=4, coeffs=False, blinding=False, blinding_seed=0, blinding_stream=0):
+        """qpgpu_oracle_commit_sharded: one oracle whose leaves are split over the contexts `gpus` (QpGpu objects on any devices,
+        a power of two of them, at most 2^rate_bits). gpus[0] is the home context: a (device pointer, num_polys, n) input lies on its
+        device, and it is the context of every later call (the oracle's .gpu). cap / eval / read / open answer as an unsharded
+        oracle's; .shards and .shard_range(g) say who holds what."""
+        self = cls.__new__(cls)
+        self.gpu, self.gpus = gpus[0], list(gpus)
+        gpu = self.gpu
+        if isinstance(polys, np.ndarray):
+            a = np.ascontiguousarray(polys, dtype=np.uint64)
+            num_polys, n = a.shape
+            ptr, flags = a.ctypes.data, 0
+        else:
+            dev, num_polys, n = polys
+            ptr, flags = _ptr(dev), ORACLE_DEVICE_INPUT
+        self.num_polys, self.n, self.batch = num_polys, n, None
+        self.degree_bits, self.rate_bits, self.cap_height = n.bit_length() - 1, rate_bits, cap_height
+        assert 1 << self.degree_bits == n
+        flags |= (ORACLE_COEFFS if coeffs else ORACLE_VALUES) | (ORACLE_BLINDING if blinding else 0)
+        h = ctypes.c_void_p()
+        ctxs = (ctypes.c_void_p * max(1, len(gpus)))(*[g.ctx for g in gpus])
+        self.h = None
+        gpu._check(gpu.lib.qpgpu_oracle_commit_sharded(ctxs, len(gpus), ptr, num_polys, self.degree_bits, rate_bits, cap_height, flags,
+                                                       blinding_seed, blinding_stream, ctypes.byref(h)))
+        self.h = h
+        return self
+
+    @property
+    def shards(self):
+        """Contexts the oracle's leaves are split over; 1 for an oracle of one context."""
+        return int(self.gpu.lib.qpgpu_oracle_shards(self.h))
+
+    def shard_range(self, shard):
+        """(first leaf, number of leaves) of a shard."""
+        first, num = ctypes.c_uint64(), ctypes.c_uint64()
+        self.gpu._check(self.gpu.lib.qpgpu_oracle_shard_range(self.h, shard, ctypes.byref(first), ctypes.byref(num)))
+        return int(first.value), int(num.value)
+
+    def shard_device_ptrs(self, shard):
+        """(LDE, digests) of a shard as integer addresses on the shard's device."""
+        lde, dig = ctypes.c_void_p(), ctypes.c_void_p()
+        self.gpu._check(self.gpu.lib.qpgpu_oracle_shard_device_ptrs(self.h, shard, ctypes.byref(lde), ctypes.byref(dig)))
+        return lde.value, dig.value
 
     def strides(self):
         """Words between two proofs' (coefficients, LDEs, digests); (0, 0, 0) for an oracle of one proof."""
@@ -1594,6 +1644,11 @@ class QpGpu(_Stage3):
 
     def sync(self):
         self._check(self.lib.qpgpu_sync(self.ctx))
+
+    def commit_sharded(self, ctxs, polys, **kw):
+        """PolyOracle.commit_sharded with this context as the home context: ctxs is the full list of QpGpu objects, self first."""
+        assert ctxs and ctxs[0] is self, "the home context comes first"
+        return PolyOracle.commit_sharded(ctxs, polys, **kw)
 
     def pci_bus_id(self):
         """"dddd:bb:dd.f" of the context's device (the key of its sysfs directory)."""

@@ -34,7 +34,19 @@ int fri_setup(qpgpu_oracle *const *oracles, uint32_t n, const qpgpu_fri_params *
     for (unsigned a : fp.arity_bits) { if (a == 0 || a > 8) return QPGPU_EINVAL; tot += a; }
     if (tot > fp.degree_bits || fp.degree_bits + fp.rate_bits < tot + fp.cap_h || fp.pow_bits > 40 || fp.num_queries == 0 || fp.num_queries > 4096) return QPGPU_EINVAL;
     widths.clear();
-    for (uint32_t i = 0; i < n; i++) widths.push_back(oracles[i]->o.ncols + (oracles[i]->o.salt ? 4 : 0));
+    for (uint32_t i = 0; i < n; i++) widths.push_back(oracles[i]->o.ncols + (oracles[i]->o.salted() ? 4 : 0));
+    return QPGPU_OK;
+}
+
+// sharded oracles: the call's context is their home context (the FRI arithmetic reads the coefficients there), and the lockstep
+// entries do not take them yet. `ctx` is non-NULL; oracles may be anything (fri_setup checks it afterwards).
+int fri_sharded_check(qpgpu_ctx *ctx, qpgpu_oracle *const *oracles, uint32_t n, bool lockstep) {
+    if (!oracles) return QPGPU_OK;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!oracles[i] || !oracles[i]->sh) continue;
+        if (lockstep) return ctx->fail(QPGPU_EINVAL, "fri_prove_batch: oracle " + std::to_string(i) + " is sharded; sharded oracles are not taken here yet, use qpgpu_fri_prove or qpgpu_fri_begin");
+        if (oracles[i]->ctx != ctx) return ctx->fail(QPGPU_EINVAL, "fri_prove: ctx is not the home context (ctxs[0] of qpgpu_oracle_commit_sharded) of sharded oracle " + std::to_string(i));
+    }
     return QPGPU_OK;
 }
 
@@ -120,6 +132,7 @@ static int prove_impl(qpgpu_ctx *ctx, qpgpu_oracle *const *oracles, uint32_t num
                       const uint64_t *points, uint32_t nb, const qpgpu_fri_params *params, qpgpu_challenger *challengers,
                       uint8_t *const *outs, size_t out_cap, size_t *out_lens) {
     FriCall c;
+    QP_TRY(fri_sharded_check(ctx, oracles, num_oracles, points != nullptr));
     if (fri_setup(oracles, num_oracles, params, c.fp, c.widths) != QPGPU_OK || oracles[0]->ctx != ctx)
         return ctx->fail(QPGPU_EINVAL, "fri_prove: bad oracles or FRI parameters");
     for (uint32_t b = 0; b < nb; b++)
@@ -170,6 +183,7 @@ static int begin_impl(qpgpu_ctx *ctx, qpgpu_oracle *const *oracles, uint32_t num
     qpgpu_fri_params prm = *params;
     prm.proof_of_work_bits = 0; prm.num_query_rounds = kOpenChunk;    // not the session's business: neither is read
     FriCall c;
+    QP_TRY(fri_sharded_check(ctx, oracles, num_oracles, points != nullptr));
     QP_TRY(fri_call(ctx, oracles, num_oracles, batches, num_batches, points, nb, &prm, c));
     qpgpu_fri_session *s = new qpgpu_fri_session();
     s->ctx = ctx;

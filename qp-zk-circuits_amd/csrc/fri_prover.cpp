@@ -335,10 +335,20 @@ int fri_gather(FriState &s, const u64 *qidx, uint32_t nq, ByteWriter *outs) {
     // gather layout (per section, all queries contiguous): for each oracle rows then paths; for each FRI round evals then paths
     struct Sec { size_t off, words; bool is_path; };
     std::vector<Sec> secs;
+    struct Routed { size_t oracle, off; };
+    std::vector<Routed> sharded;
     size_t goff = 0;
     for (size_t i = 0; i < n_oracles; i++) {
         const PolyOracle *o = s.oracles[i];
         const uint32_t plen0 = (uint32_t)w.proof.op[i].path_len;
+        if (o->sh) {    // a sharded oracle's rows and paths are routed to its shards below; its sections keep their place
+            if (nb != 1) return ctx->fail(QPGPU_EINVAL, "fri_gather: sharded oracles are not taken in a lockstep batch yet");
+            sharded.push_back({i, goff});
+            secs.push_back({goff, o->ncols, false}); goff += (size_t)o->ncols * nq;
+            if (o->blinded) { secs.push_back({goff, 4, false}); goff += (size_t)4 * nq; }
+            secs.push_back({goff, (size_t)plen0 * 4, true}); goff += (size_t)plen0 * 4 * nq;
+            continue;
+        }
         QP_HIP(ctx, pk_gather_rows(o->lde, lde_n, o->ncols, w.qidx, nq, w.gather + goff, nb, o->ps_lde, w.ws, st));
         secs.push_back({goff, o->ncols, false}); goff += (size_t)o->ncols * nq;
         if (o->salt) {
@@ -359,6 +369,18 @@ int fri_gather(FriState &s, const u64 *qidx, uint32_t nq, ByteWriter *outs) {
     if (goff * s.p.num_queries != w.gather_words * nq) return ctx->fail(QPGPU_EDEVICE, "prove: internal gather size mismatch");
     std::vector<u64> gathered(goff * nb);
     QP_TRY(ctx->read_back_2d(gathered.data(), w.gather, w.ws * 8, goff * 8, nb));
+    for (const Routed &rt : sharded) {
+        const PolyOracle *o = s.oracles[rt.oracle];
+        const size_t width = (size_t)o->ncols + (o->blinded ? 4 : 0), plen0 = w.proof.op[rt.oracle].path_len;
+        std::vector<u64> rows(width * nq), paths(plen0 * 4 * nq);
+        QP_TRY(oracle_sharded_open(*o, qidx, nq, rows.data(), plen0 ? paths.data() : nullptr));
+        u64 *g_rows = gathered.data() + rt.off, *g_salt = g_rows + (size_t)o->ncols * nq, *g_paths = g_rows + width * nq;
+        for (uint32_t q = 0; q < nq; q++) {
+            std::memcpy(g_rows + (size_t)q * o->ncols, rows.data() + q * width, (size_t)o->ncols * 8);
+            if (o->blinded) std::memcpy(g_salt + (size_t)q * 4, rows.data() + q * width + o->ncols, 32);
+        }
+        if (plen0) std::memcpy(g_paths, paths.data(), paths.size() * 8);
+    }
     ctx->prof_end();
     // FriQueryRound bytes (util::serialization write_fri_query_rounds)
     for (uint32_t b = 0; b < nb; b++) {

@@ -16,6 +16,7 @@ using gl::u64;
 
 extern "C" void qpgpu_oracle_free(qpgpu_oracle *h) {
     if (!h) return;
+    if (h->sh) { oracle_sharded_free(h); return; }
     (void)hipSetDevice(h->ctx->device);
     if (h->block) {
         // committed columns can hold the witness (reference wormhole/circuit/src/sensitive.rs:36-44): scrub before release
@@ -171,6 +172,7 @@ int qpgpu_oracle_read(qpgpu_oracle *h, unsigned what, uint32_t first, uint32_t c
     QP_DEV(ctx);
     if (h->o.nb > 1) return ctx->fail(QPGPU_EINVAL, "oracle_read: the oracle holds a batch of " + std::to_string(h->o.nb) + " proofs, use qpgpu_oracle_device_ptrs and qpgpu_oracle_strides");
     if (!out || count == 0 || (size_t)first + count > h->o.ncols || what > QPGPU_ORACLE_READ_LDE) return ctx->fail(QPGPU_EINVAL, "oracle_read: bad range");
+    if (h->sh && what == QPGPU_ORACLE_READ_LDE) return oracle_sharded_read_lde(h, first, count, out);
     const u64 len = what == QPGPU_ORACLE_READ_LDE ? h->o.lde_n() : 1ull << h->o.log_n;
     const u64 *src = (what == QPGPU_ORACLE_READ_LDE ? h->o.lde : h->o.coeffs) + (size_t)first * len;
     QP_HIP(ctx, hipMemcpyAsync(out, src, (size_t)count * len * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -180,13 +182,14 @@ int qpgpu_oracle_read(qpgpu_oracle *h, unsigned what, uint32_t first, uint32_t c
 
 int qpgpu_oracle_device_ptrs(const qpgpu_oracle *h, const uint64_t **d_coeffs, const uint64_t **d_lde, const uint64_t **d_digests) {
     if (!h) return QPGPU_EINVAL;
+    if (h->sh) return h->ctx->fail(QPGPU_EINVAL, "oracle_device_ptrs: the oracle is sharded over " + std::to_string(h->sh->s.size()) + " contexts, use qpgpu_oracle_shard_device_ptrs");
     if (d_coeffs) *d_coeffs = h->o.coeffs;
     if (d_lde) *d_lde = h->o.lde;
     if (d_digests) *d_digests = h->o.digests;
     return QPGPU_OK;
 }
 
-size_t qpgpu_oracle_leaf_width(const qpgpu_oracle *h) { return h ? (size_t)h->o.ncols + (h->o.salt ? 4 : 0) : 0; }
+size_t qpgpu_oracle_leaf_width(const qpgpu_oracle *h) { return h ? (size_t)h->o.ncols + (h->o.salted() ? 4 : 0) : 0; }
 
 int qpgpu_oracle_open(qpgpu_oracle *h, const uint64_t *indices, size_t n, uint64_t *rows_out, uint64_t *paths_out) {
     if (!h) return QPGPU_EINVAL;
@@ -200,6 +203,7 @@ int qpgpu_oracle_open(qpgpu_oracle *h, const uint64_t *indices, size_t n, uint64
     for (size_t i = 0; i < n; i++)
         if (indices[i] >= lde_n)
             return ctx->fail(QPGPU_EINVAL, "oracle_open: indices[" + std::to_string(i) + "] = " + std::to_string(indices[i]) + " is not below 2^" + std::to_string(o.log_lde()));
+    if (h->sh) return oracle_sharded_open(o, indices, n, rows_out, paths_out);
     const uint32_t plen = o.log_lde() - o.cap_h;
     const size_t width = qpgpu_oracle_leaf_width(h), per = 1 + (rows_out ? width : 0) + (paths_out ? (size_t)plen * 4 : 0);
     if (per == 1) return QPGPU_OK;
@@ -233,6 +237,7 @@ int qpgpu_oracle_eval_batch(qpgpu_oracle *h, const uint64_t *points, uint32_t fi
     if (!h) return QPGPU_EINVAL;
     qpgpu_ctx *ctx = h->ctx;
     QP_DEV(ctx);
+    if (h->sh) return refuse_sharded(h, "oracle_eval_batch");
     if (!points || !out || count == 0 || (size_t)first + count > h->o.ncols) return ctx->fail(QPGPU_EINVAL, "oracle_eval_batch: bad range");
     const PolyOracle &o = h->o;
     const uint32_t nb = o.nb;
@@ -251,6 +256,7 @@ int qpgpu_oracle_open_batch(qpgpu_oracle *h, const uint64_t *indices, size_t n, 
     if (!h) return QPGPU_EINVAL;
     qpgpu_ctx *ctx = h->ctx;
     QP_DEV(ctx);
+    if (h->sh) return refuse_sharded(h, "oracle_open_batch");
     if (n == 0) return QPGPU_OK;
     if (!indices) return ctx->fail(QPGPU_EINVAL, "oracle_open_batch: indices is NULL");
     const PolyOracle &o = h->o;

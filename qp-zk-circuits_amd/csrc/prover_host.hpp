@@ -26,7 +26,9 @@ struct ByteWriter {
 // One committed polynomial batch per proof, resident on the device. Column-major everywhere: coefficient c of polynomial j
 // at coeffs[j*n + c]; LDE value of polynomial j at leaf slot s (= point g*w^bitrev(s)) at lde[j*lde_n + s]. With nb > 1
 // the buffers are [nb][...] arrays (proof b at + b * ps_*); an oracle shared by all proofs of a batch (constants/sigmas)
-// has nb == 1 and strides 0.
+// has nb == 1 and strides 0. A coset-sharded oracle (oracle_handle.hpp: OracleShards) keeps the coefficients here, on its home
+// context, and the LDE, the salts and the tree in its shards: lde, digests and salt are NULL, sh says where the leaves are.
+struct OracleShards;
 struct PolyOracle {
     uint32_t ncols = 0;
     unsigned log_n = 0, rate_bits = 0, cap_h = 0;
@@ -36,6 +38,9 @@ struct PolyOracle {
     gl::u64 ps_coeffs = 0, ps_lde = 0, ps_digests = 0, ps_salt = 0;
     uint32_t oracle_index = 0;          // selects the salt stream of a blinded oracle
     std::vector<gl::u64> cap;           // [nb][4 << cap_h]
+    const OracleShards *sh = nullptr;
+    bool blinded = false;               // a sharded oracle's; everywhere else salt != NULL says it
+    bool salted() const { return salt || blinded; }
     gl::u64 lde_n() const { return 1ull << (log_n + rate_bits); }
     unsigned log_lde() const { return log_n + rate_bits; }
     size_t cap_words() const { return (size_t)4 << cap_h; }
@@ -99,6 +104,11 @@ struct FriWork {
 // o.salt is set. d_values: [nb][ncols][n], dense.
 int oracle_commit_coeffs(qpgpu_ctx *ctx, PolyOracle &o, const uint32_t *d_keys);
 int oracle_commit_values(qpgpu_ctx *ctx, const gl::u64 *d_values, PolyOracle &o, const uint32_t *d_keys);
+// Leaves and Merkle paths of a sharded oracle (o.sh set) at n global leaf indices, in the caller's order, on the host: each index
+// goes to its shard (one gather per shard and pass, on that shard's stream), the siblings above a shard's root come from the home
+// context's merge levels. rows_out: [n][ncols (+ 4 salt words)], paths_out: [n][log_lde - cap_h][4]; either may be NULL. The
+// indices are below lde_n (the caller's check). Leaves the home context's device selected.
+int oracle_sharded_open(const PolyOracle &o, const gl::u64 *indices, size_t n, gl::u64 *rows_out, gl::u64 *paths_out);
 
 // PolynomialBatch::prove_openings + fri_proof for nb proofs: squeezes the FRI alphas, builds the batched opening
 // polynomials, runs the commit phase, the proof of work and the query phase against chs[b], and appends FriProof bytes

@@ -300,6 +300,29 @@ __global__ void __launch_bounds__(256) salt_kernel(const u32 *keys, u32 oracle_i
     }
 }
 
+// The same stream for a contiguous range of the leaves (a shard of a coset-sharded oracle): local leaf j is global leaf
+// first_leaf + j, whose ChaCha20 position the salt is drawn at, so the shards' slices put together are salt_kernel's output.
+// first_leaf is even (a shard holds a power of two of at least two leaves), so a block's two halves stay in one shard. out: [4][count].
+__global__ void __launch_bounds__(256) salt_slice_kernel(const u32 *key, u32 oracle_index, u64 first_leaf, u64 count, u64 *out) {
+    const u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const u64 leaf = first_leaf + j;
+    for (u32 c = 0; c < 4; c++) {
+        u32 blk[16];
+        chacha20_block(key, leaf >> 1, oracle_index, c, blk);
+        const u32 h = (u32)(leaf & 1) * 8;
+        u64 v = 0;
+        bool found = false;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const u64 cand = ((u64)blk[h + 2 * k + 1] << 32) | blk[h + 2 * k];
+            if (!found && cand < gl::P) { v = cand; found = true; }
+        }
+        if (!found) v = (((u64)blk[h + 7] << 32) | blk[h + 6]) - gl::P;
+        out[(u64)c * count + j] = v;
+    }
+}
+
 // RandomValueGenerator on the device (CircuitBuilder::blind's random wires of a zero-knowledge circuit): value j of witness b from
 // the ChaCha20 stream of that witness's key, nonce ("BLND", 0); block (j >> 1) holds the candidates of values 2k and 2k+1, the
 // first of four below p is taken (uniform on [0, p)). out: [batch][pitch], `count` values each.
@@ -447,6 +470,10 @@ hipError_t pk_gather_leaf_rows(const u64 *rows, u32 width, const u64 *idx, u32 s
 }
 hipError_t pk_salt(const u32 *keys, u32 oracle_index, u64 lde_n, u64 *out, u32 batch, hipStream_t st) {
     LAUNCH_1D_B(salt_kernel, lde_n, 256, batch, st, keys, oracle_index, lde_n, out);
+    return hipGetLastError();
+}
+hipError_t pk_salt_slice(const u32 *key, u32 oracle_index, u64 first_leaf, u64 count, u64 *out, hipStream_t st) {
+    LAUNCH_1D(salt_slice_kernel, count, 256, st, key, oracle_index, first_leaf, count, out);
     return hipGetLastError();
 }
 hipError_t pk_random_felts(const u32 *keys, u64 count, u64 *out, u64 pitch, u32 batch, hipStream_t st) {

@@ -61,6 +61,8 @@ int refuse(qpgpu_ctx *ctx, char *err, int code, const std::string &msg) {
 // an oracle argument against the plan's header; empty, or what disagrees
 std::string oracle_mismatch(const qpgpu_stage_plan *pl, const qpgpu_oracle *o, size_t ncols, bool may_blind) {
     const CircuitPack &p = pl->pack;
+    // its LDE lies in its shards, not behind o.lde: refused, never read as if shard 0 were the whole
+    if (o->sh) return "is sharded over " + std::to_string(o->sh->s.size()) + " contexts: sharded oracles are not taken here yet";
     if (o->ctx != pl->ctx) return "belongs to another context";
     if (o->o.ncols != ncols) return "has " + std::to_string(o->o.ncols) + " polynomials, the circuit needs " + std::to_string(ncols);
     if (o->o.log_n != p.degree_bits) return "has degree_bits " + std::to_string(o->o.log_n) + ", the circuit " + std::to_string(p.degree_bits);
