@@ -357,9 +357,12 @@ size_t qpgpu_oracle_leaf_width(const qpgpu_oracle *o);   /* num_polys, + 4 for a
  * goes to its shard, one gather per shard on that shard's stream, results in the caller's order) and _free (every shard scrubbed
  * on its own context) work as on any oracle, and so do qpgpu_fri_prove, qpgpu_fri_begin .. qpgpu_fri_open and
  * qpgpu_fri_proof_size over any mix of sharded and plain oracles, with the same bytes; their ctx must be the home context of
- * every sharded oracle. qpgpu_oracle_device_ptrs is QPGPU_EINVAL naming qpgpu_oracle_shard_device_ptrs; qpgpu_stage_plan_create*,
- * qpgpu_stage_quotient*, qpgpu_oracle_eval_batch, _open_batch, qpgpu_fri_prove_batch and _begin_batch are QPGPU_EINVAL saying
- * that sharded oracles are not taken there yet: none of them reads shard 0 as if it were the whole. */
+ * every sharded oracle. qpgpu_stage_plan_create_sharded makes a stage plan over a sharded constants/sigmas oracle, and
+ * qpgpu_stage_quotient on such a plan takes sharded wire and Z/partial-products oracles (the stage section below).
+ * qpgpu_oracle_device_ptrs is QPGPU_EINVAL naming qpgpu_oracle_shard_device_ptrs; qpgpu_stage_plan_create, _create_batch,
+ * qpgpu_stage_quotient* on a plan made by either of them, qpgpu_oracle_eval_batch, _open_batch, qpgpu_fri_prove_batch and
+ * _begin_batch are QPGPU_EINVAL saying that sharded oracles are not taken there yet: none of them reads shard 0 as if it were
+ * the whole. */
 int qpgpu_oracle_commit_sharded(qpgpu_ctx *const *ctxs, uint32_t n_ctx, const uint64_t *polys, uint32_t num_polys,
                                 unsigned degree_bits, unsigned rate_bits, unsigned cap_height, unsigned flags,
                                 uint64_t blinding_seed, uint32_t blinding_stream, qpgpu_oracle **out);
@@ -536,6 +539,32 @@ int qpgpu_stage_partial_products(qpgpu_stage_plan *plan, const uint64_t *wires, 
 int qpgpu_stage_quotient(qpgpu_stage_plan *plan, const qpgpu_oracle *wires_oracle, const qpgpu_oracle *zs_pp_oracle,
                          const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas, const uint64_t *public_inputs_hash,
                          uint64_t *d_out);
+
+/* ---- the two stages over coset-sharded oracles -----------------------------------------------------------------------
+ * A stage plan over a coset-sharded constants/sigmas oracle. ctx must be cs_oracle's home context; the plan takes the shard
+ * contexts, their order and G from the oracle. Header rules, limits, `err` and the order of checks (header before ctx and oracle)
+ * are qpgpu_stage_plan_create's. A cs_oracle that is not sharded is QPGPU_EINVAL naming qpgpu_stage_plan_create.
+ *
+ * On such a plan qpgpu_stage_partial_products works as on any plan, on the home context alone (s5 lives on the 2^degree_bits trace
+ * domain; the sigma values come from the coefficients, which the home context keeps). qpgpu_stage_quotient takes wires_oracle and
+ * zs_pp_oracle sharded over the same contexts in the same order as the plan's cs_oracle; a plain oracle, another number of shards,
+ * another context at some position or another home context is QPGPU_EINVAL naming the argument and what disagrees. The quotient
+ * domain is the LDE points with natural index 0 mod 2^q_shift (q_shift = rate_bits - log2 quotient_degree_factor), so the first
+ * Gq = max(1, G >> q_shift) shards hold its points, Nq / Gq each, and evaluate them on their own contexts and streams with the launch
+ * sequence of qpgpu_stage_quotient, from their own slices of the three LDEs (the standard configuration, rate_bits 3 and factor 8:
+ * every shard works; rate_bits above log2 of the factor: only the first Gq do). Each transforms its values to coefficients alone;
+ * the home context gathers the Gq blocks (a peer copy between devices; on one device a shard writes its block in place; no
+ * peer-access setting is read or changed) and one kernel there, the last radix-Gq pass of the inverse transform, writes the chunks.
+ * d_out is on the home context's device; its contents, layout and meaning are qpgpu_stage_quotient's, word for word those of the
+ * unsharded call. The witness check is part of the call and runs on the home context from the coefficients, with the same
+ * QPGPU_EUNSAT wording. The calling thread drives all G streams and has synchronised them when the call returns; after any error
+ * the plan's workspace and pinned staging have been overwritten on every shard context, and the plan stays usable.
+ * qpgpu_stage_plan_info and _free (every shard's workspace scrubbed on its own context) work; qpgpu_stage_plan_max_batch is 1;
+ * qpgpu_stage_partial_products_batch and qpgpu_stage_quotient_batch are QPGPU_EINVAL saying that a sharded plan takes one proof.
+ * Limits are unchanged: degree_bits + rate_bits <= 23. */
+int qpgpu_stage_plan_create_sharded(qpgpu_ctx *ctx, const uint64_t *words, size_t n_words, const qpgpu_oracle *cs_oracle,
+                                    qpgpu_stage_plan **out, char *err);
+uint32_t qpgpu_stage_plan_shards(const qpgpu_stage_plan *plan);   /* 1 for every other plan, 0 for NULL */
 
 /* The two stages for a lockstep batch. qpgpu_stage_plan_create_batch: a plan whose workspace holds max_batch proofs (1..1024,
  * checked together with the header, before ctx or cs_oracle is looked at: the refusal needs no device); qpgpu_stage_plan_create is

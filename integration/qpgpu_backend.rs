@@ -133,6 +133,9 @@ extern "C" {
     pub fn qpgpu_stage_plan_create_batch(ctx: *mut QpgpuCtx, words: *const u64, n_words: usize, cs_oracle: *const QpgpuOracle, max_batch: u32,
                                          out: *mut *mut QpgpuStagePlan, err: *mut c_char) -> i32;
     pub fn qpgpu_stage_plan_max_batch(plan: *const QpgpuStagePlan) -> u32;
+    pub fn qpgpu_stage_plan_create_sharded(ctx: *mut QpgpuCtx, words: *const u64, n_words: usize, cs_oracle: *const QpgpuOracle,
+                                           out: *mut *mut QpgpuStagePlan, err: *mut c_char) -> i32;
+    pub fn qpgpu_stage_plan_shards(plan: *const QpgpuStagePlan) -> u32;
     pub fn qpgpu_stage_partial_products_batch(plan: *mut QpgpuStagePlan, wires: *const *const u64, batch: u32, wires_on_device: i32,
                                               betas: *const u64, gammas: *const u64, d_out: *mut u64) -> i32;
     pub fn qpgpu_stage_quotient_batch(plan: *mut QpgpuStagePlan, wires_oracle: *const QpgpuOracle, zs_pp_oracle: *const QpgpuOracle, batch: u32,

@@ -164,6 +164,8 @@ def load_library():
         "qpgpu_oracle_shard_range": (c.c_int, [vp, c.c_uint32, c.POINTER(c.c_uint64), c.POINTER(c.c_uint64)]),
         "qpgpu_oracle_shard_device_ptrs": (c.c_int, [vp, c.c_uint32, c.POINTER(vp), c.POINTER(vp)]),
         "qpgpu_stage_plan_create": (c.c_int, [vp, u64p, c.c_size_t, vp, c.POINTER(vp), c.c_char_p]),
+        "qpgpu_stage_plan_create_sharded": (c.c_int, [vp, u64p, c.c_size_t, vp, c.POINTER(vp), c.c_char_p]),
+        "qpgpu_stage_plan_shards": (c.c_uint32, [vp]),
         "qpgpu_stage_plan_free": (None, [vp]),
         "qpgpu_stage_plan_info": (c.c_int, [vp, c.POINTER(c.c_uint), c.POINTER(c.c_uint), c.POINTER(c.c_uint), c.POINTER(c.c_uint),
                                             c.POINTER(c.c_int)]),
@@ -978,15 +980,24 @@ class StagePlan:
     pack_words: the full pack or stage_header_words(pack); cs_oracle: the PolyOracle of the constants/sigmas values (no
     blinding), which must stay open as long as the plan."""
 
-    def __init__(self, gpu, pack_words, cs_oracle, max_batch=None):
+    @classmethod
+    def create_sharded(cls, gpu, pack_words, cs_oracle):
+        """qpgpu_stage_plan_create_sharded: a plan over a constants/sigmas oracle from PolyOracle.commit_sharded; gpu is its home
+        context. quotient() then takes wire and Z/partial-products oracles sharded over the same contexts."""
+        return cls(gpu, pack_words, cs_oracle, sharded=True)
+
+    def __init__(self, gpu, pack_words, cs_oracle, max_batch=None, sharded=False):
         """max_batch: None = qpgpu_stage_plan_create (one proof); a number = qpgpu_stage_plan_create_batch, a workspace for that
-        many proofs in lockstep (partial_products_batch, quotient_batch)."""
+        many proofs in lockstep (partial_products_batch, quotient_batch). sharded=True: qpgpu_stage_plan_create_sharded (one proof)."""
         self.gpu, self.cs_oracle = gpu, cs_oracle
         pw = np.ascontiguousarray(pack_words, dtype=np.uint64)
         h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(STAGE_ERR_CAP)
         cs = cs_oracle.h if cs_oracle is not None else None
-        if max_batch is None:
+        if sharded:
+            assert max_batch is None, "a sharded plan takes one proof"
+            rc = gpu.lib.qpgpu_stage_plan_create_sharded(gpu.ctx, pw.ctypes.data, pw.size, cs, ctypes.byref(h), err)
+        elif max_batch is None:
             rc = gpu.lib.qpgpu_stage_plan_create(gpu.ctx, pw.ctypes.data, pw.size, cs, ctypes.byref(h), err)
         else:
             rc = gpu.lib.qpgpu_stage_plan_create_batch(gpu.ctx, pw.ctypes.data, pw.size, cs, max_batch, ctypes.byref(h), err)
@@ -994,6 +1005,7 @@ class StagePlan:
             raise QpGpuError(rc, err.value.decode())
         self.h = h
         self.max_batch = int(gpu.lib.qpgpu_stage_plan_max_batch(h))
+        self.shards = int(gpu.lib.qpgpu_stage_plan_shards(h))      # contexts the plan's oracles are split over; 1: a plan on one context
         v = [ctypes.c_uint() for _ in range(4)]
         fused = ctypes.c_int()
         gpu._check(gpu.lib.qpgpu_stage_plan_info(h, *[ctypes.byref(x) for x in v], ctypes.byref(fused)))
@@ -1032,7 +1044,8 @@ class StagePlan:
     def quotient(self, wires_oracle, zs_pp_oracle, betas, gammas, alphas, public_inputs_hash):
         """Returns a DeviceBuffer of num_quotient columns of n coefficients:
         PolyOracle(gpu, (buf, plan.num_quotient, plan.n), coeffs=True, ...) commits it. QpGpuError -4 for a witness that does not
-        satisfy the circuit."""
+        satisfy the circuit. On a plan from create_sharded the two oracles are sharded ones (PolyOracle.commit_sharded over the
+        contexts of the plan's cs_oracle); the buffer is on the home context and holds the same words."""
         b, g, a = self._challenges(betas), self._challenges(gammas), self._challenges(alphas)
         pih = np.ascontiguousarray(public_inputs_hash, dtype=np.uint64).ravel()
         assert pih.size == 4

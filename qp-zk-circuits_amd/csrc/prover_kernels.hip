@@ -343,13 +343,13 @@ __global__ void __launch_bounds__(256) random_felts_kernel(const u32 *keys, u64 
     out[(u64)blockIdx.z * pitch + j] = v;
 }
 
-// x_coset[j] = g * w^bitrev(j), l0_coset[j] = zh(i) / (n (x - 1))
-__global__ void __launch_bounds__(256) coset_tables_kernel(u64 lde_n, u32 log_lde, const u64 *pw_lo, const u64 *pw_hi, u32 lo_bits,
+// x_coset[j] = shift * w^bitrev(j), l0_coset[j] = zh(i) / (n (x - 1))
+__global__ void __launch_bounds__(256) coset_tables_kernel(u64 lde_n, u32 log_lde, u64 shift, const u64 *pw_lo, const u64 *pw_hi, u32 lo_bits,
                                                              const u64 *zh, u32 rate, u64 n_field, u64 *x_coset, u64 *l0_coset) {
     const u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x;
     if (j >= lde_n) return;
     const u64 i = brev32((u32)j, log_lde);
-    const u64 x = gl::canon(gl::mul(gl::MULT_GEN, gl::mul(pw_hi[i >> lo_bits], pw_lo[i & ((1u << lo_bits) - 1)])));
+    const u64 x = gl::canon(gl::mul(shift, gl::mul(pw_hi[i >> lo_bits], pw_lo[i & ((1u << lo_bits) - 1)])));
     x_coset[j] = x;
     l0_coset[j] = gl::canon(gl::mul(zh[i & (rate - 1)], gl::inv(gl::mul(n_field, gl::sub(x, 1)))));
 }
@@ -481,8 +481,8 @@ hipError_t pk_random_felts(const u32 *keys, u64 count, u64 *out, u64 pitch, u32 
     LAUNCH_1D_B(random_felts_kernel, count, 256, batch, st, keys, count, out, pitch);
     return hipGetLastError();
 }
-hipError_t pk_coset_tables(u64 lde_n, u32 log_lde, const u64 *pw_lo, const u64 *pw_hi, u32 lo_bits, const u64 *zh, u32 rate,
+hipError_t pk_coset_tables(u64 lde_n, u32 log_lde, u64 shift, const u64 *pw_lo, const u64 *pw_hi, u32 lo_bits, const u64 *zh, u32 rate,
                            u64 n_field, u64 *x_coset, u64 *l0_coset, hipStream_t st) {
-    LAUNCH_1D(coset_tables_kernel, lde_n, 256, st, lde_n, log_lde, pw_lo, pw_hi, lo_bits, zh, rate, n_field, x_coset, l0_coset);
+    LAUNCH_1D(coset_tables_kernel, lde_n, 256, st, lde_n, log_lde, shift, pw_lo, pw_hi, lo_bits, zh, rate, n_field, x_coset, l0_coset);
     return hipGetLastError();
 }

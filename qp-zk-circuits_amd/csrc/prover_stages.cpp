@@ -65,9 +65,19 @@ int h2d_sync(qpgpu_ctx *ctx, void *dst, const void *src, size_t bytes) {
     return QPGPU_OK;
 }
 
-int stage_tables_build(qpgpu_ctx *ctx, const CircuitPack &p, const StageAlloc &alloc, StageTables &t) {
-    const u64 n = p.n(), lde_n = n << p.rate_bits;
-    const unsigned d = (unsigned)p.degree_bits, L = (unsigned)(p.degree_bits + p.rate_bits);
+StageGeom stage_geom_of(const CircuitPack &p) {
+    // the quotient lives on the coset of size n * quotient_degree_factor: every 2^q_shift-th point of the LDE, i.e. its first q_n slots
+    unsigned qbits = 0; while ((1ull << qbits) < p.quotient_degree_factor) qbits++;
+    StageGeom g;
+    g.shift = gl::MULT_GEN; g.log_lde = (unsigned)(p.degree_bits + p.rate_bits); g.rate_bits = (unsigned)p.rate_bits;
+    g.q_shift = (unsigned)p.rate_bits - qbits; g.log_q = (unsigned)p.degree_bits + qbits;
+    return g;
+}
+
+int stage_tables_build(qpgpu_ctx *ctx, const CircuitPack &p, const StageAlloc &alloc, StageTables &t, const StageGeom *geom) {
+    t.geom = geom ? *geom : stage_geom_of(p);
+    const u64 n = p.n(), lde_n = 1ull << t.geom.log_lde;
+    const unsigned d = (unsigned)p.degree_bits, L = t.geom.log_lde;
     // gates
     std::vector<GateDev> gd(p.gates.size());
     for (size_t i = 0; i < gd.size(); i++) {
@@ -86,9 +96,9 @@ int stage_tables_build(qpgpu_ctx *ctx, const CircuitPack &p, const StageAlloc &a
     // subgroup, coset and vanishing tables
     QP_TRY(alloc(&t.d_omega, n, false));
     { auto w = powers_table(gl::root_of_unity(d), n); QP_TRY(h2d_sync(ctx, t.d_omega, w.data(), n * 8)); }
-    const uint32_t rate = 1u << p.rate_bits;
+    const uint32_t rate = 1u << t.geom.rate_bits;
     std::vector<u64> zh(rate), zh_inv(rate);
-    { u64 gn = gl::pow(gl::MULT_GEN, n), wr = gl::root_of_unity((unsigned)p.rate_bits), a = 1;
+    { u64 gn = gl::pow(t.geom.shift, n), wr = gl::root_of_unity(t.geom.rate_bits), a = 1;
       for (uint32_t i = 0; i < rate; i++) { zh[i] = gl::canon(gl::sub(gl::mul(gn, a), 1)); zh_inv[i] = gl::inv(zh[i]); a = gl::mul(a, wr); } }
     u64 *d_zh = nullptr;
     QP_TRY(alloc(&d_zh, rate, false)); QP_TRY(alloc(&t.d_zh_inv, rate, false));
@@ -101,9 +111,9 @@ int stage_tables_build(qpgpu_ctx *ctx, const CircuitPack &p, const StageAlloc &a
         QP_TRY(alloc(&d_lo, lo.size(), false)); QP_TRY(alloc(&d_hi, hi.size(), false));
         QP_TRY(h2d_sync(ctx, d_lo, lo.data(), lo.size() * 8)); QP_TRY(h2d_sync(ctx, d_hi, hi.data(), hi.size() * 8));
         QP_TRY(alloc(&t.d_x_coset, lde_n, false)); QP_TRY(alloc(&t.d_l0_coset, lde_n, false));
-        hipError_t e = pk_coset_tables(lde_n, L, d_lo, d_hi, lo_bits, d_zh, rate, gl::canon(n % gl::P), t.d_x_coset, t.d_l0_coset, ctx->stream);
+        hipError_t e = pk_coset_tables(lde_n, L, gl::canon(t.geom.shift), d_lo, d_hi, lo_bits, d_zh, rate, gl::canon(n % gl::P), t.d_x_coset, t.d_l0_coset, ctx->stream);
         if (e != hipSuccess) return ctx->hip_fail(e, "coset_tables");
-        const u64 ginv = gl::inv(gl::MULT_GEN);
+        const u64 ginv = gl::inv(t.geom.shift);
         t.ginv_lo_bits = lo_bits;
         auto glo = powers_table(ginv, 1ull << lo_bits), ghi = powers_table(gl::pow(ginv, 1ull << lo_bits), 1ull << (L - lo_bits));
         QP_TRY(alloc(&t.d_ginv_lo, glo.size(), false)); QP_TRY(alloc(&t.d_ginv_hi, ghi.size(), false));
@@ -130,15 +140,17 @@ int stage_tables_build(qpgpu_ctx *ctx, const CircuitPack &p, const StageAlloc &a
     return QPGPU_OK;
 }
 
-int stage_work_alloc(const CircuitPack &p, const StageTables &t, const StageAlloc &alloc, uint32_t B, StageWork &w) {
-    const u64 n = p.n(), lde_n = n << p.rate_bits, nch = p.num_challenges;
+int stage_work_alloc(const CircuitPack &p, const StageTables &t, const StageAlloc &alloc, uint32_t B, StageWork &w, bool quotient_only) {
+    const u64 n = p.n(), lde_n = 1ull << t.geom.log_lde, nch = p.num_challenges;
     QP_TRY(alloc(&w.d_qacc, (size_t)B * nch * lde_n, true));
-    QP_TRY(alloc(&w.d_qcp, (size_t)B * nch * p.num_chunks() * n, true));
-    QP_TRY(alloc(&w.d_rowprod, (size_t)B * nch * n, true));
-    QP_TRY(alloc(&w.d_z, (size_t)B * nch * n, true));
+    if (!quotient_only) {
+        QP_TRY(alloc(&w.d_qcp, (size_t)B * nch * p.num_chunks() * n, true));
+        QP_TRY(alloc(&w.d_rowprod, (size_t)B * nch * n, true));
+        QP_TRY(alloc(&w.d_z, (size_t)B * nch * n, true));
+    }
     QP_TRY(alloc(&w.d_small, (size_t)B * t.small_words, false));
     if (t.fold_words) QP_TRY(alloc(&w.d_fold, (size_t)B * t.fold_words, false));
-    QP_TRY(alloc(&w.d_check, (size_t)B * 2, false));
+    if (!quotient_only) QP_TRY(alloc(&w.d_check, (size_t)B * 2, false));
     return QPGPU_OK;
 }
 
@@ -186,26 +198,38 @@ int stage_partial_products(qpgpu_ctx *ctx, const CircuitPack &p, const StageTabl
     return QPGPU_OK;
 }
 
+namespace {
+// the part of the s6 argument block that the fold sweep reads, shared by the two halves below
+QuotientArgs quotient_args_base(qpgpu_ctx *ctx, const CircuitPack &p, const StageTables &t, const StageWork &w, uint32_t nb) {
+    const SmallLayout sl(p);
+    QuotientArgs qa{};
+    qa.alpha_pows = w.d_small + sl.apow; qa.poseidon_rc = t.d_poseidon_rc; qa.p2_gate = ctx->d_p2_app; qa.p2_layout = p.p2_layout;
+    qa.nch = (uint32_t)p.num_challenges; qa.nchunks = (uint32_t)p.num_chunks(); qa.nterms = (uint32_t)sl.nterms;
+    qa.num_gates = (uint32_t)p.gates.size(); qa.batch = nb; qa.ps_small = t.small_words;
+    qa.fold = w.d_fold; qa.ps_fold = t.fold_words;
+    return qa;
+}
+}  // namespace
+
 int stage_quotient(qpgpu_ctx *ctx, const CircuitPack &p, const StageTables &t, const StageWork &w, uint32_t nb, const u64 *small,
                    const QuotientViews &v) {
+    QP_TRY(stage_quotient_prepare(ctx, p, t, w, nb, small, v));
+    return stage_quotient_values(ctx, p, t, w, nb, v);
+}
+
+int stage_quotient_prepare(qpgpu_ctx *ctx, const CircuitPack &p, const StageTables &t, const StageWork &w, uint32_t nb, const u64 *small,
+                           const QuotientViews &v) {
     hipStream_t st = ctx->stream;
     const SmallLayout sl(p);
-    const u64 n = p.n(), lde_n = n << p.rate_bits, R = p.num_routed_wires;
+    const u64 n = p.n(), R = p.num_routed_wires;
     const uint32_t nch = (uint32_t)p.num_challenges, nchunks = (uint32_t)p.num_chunks();
-    const unsigned d = (unsigned)p.degree_bits, L = (unsigned)(p.degree_bits + p.rate_bits);
+    const unsigned d = (unsigned)p.degree_bits;
     const size_t sig0 = p.num_selectors + p.num_constants, nterms = sl.nterms, SW = t.small_words;
-    // the quotient lives on the coset of size n * quotient_degree_factor: every 2^q_shift-th point of the LDE, i.e. its first q_n slots
-    unsigned qbits = 0; while ((1ull << qbits) < p.quotient_degree_factor) qbits++;
-    const unsigned Lq = d + qbits, q_shift = (unsigned)p.rate_bits - qbits;
-    const u64 q_n = 1ull << Lq;
-    u64 *d_betas = w.d_small + sl.betas, *d_gammas = w.d_small + sl.gammas, *d_bk = w.d_small + sl.bk, *d_apow = w.d_small + sl.apow, *d_pih = w.d_small + sl.pih;
+    u64 *d_apow = w.d_small + sl.apow, *d_pih = w.d_small + sl.pih;
 
     QP_TRY(w.stage->put_rows(ctx, d_apow, SW, small + sl.apow, SW, (size_t)nch * nterms + 4, nb));
     // the folded hash gates' weights for this batch's alphas: one small launch, read by the gate kernels of the witness check and of s6
-    QuotientArgs qa{};
-    qa.alpha_pows = d_apow; qa.poseidon_rc = t.d_poseidon_rc; qa.p2_gate = ctx->d_p2_app; qa.p2_layout = p.p2_layout;
-    qa.nch = nch; qa.nchunks = nchunks; qa.nterms = (uint32_t)nterms; qa.num_gates = (uint32_t)p.gates.size(); qa.batch = nb; qa.ps_small = SW;
-    qa.fold = w.d_fold; qa.ps_fold = t.fold_words;
+    const QuotientArgs qa = quotient_args_base(ctx, p, t, w, nb);
     QP_HIP(ctx, pk_quotient_fold_sweep(qa, t.h_gates.data(), st));
     if (v.check_wires) {
         // the analogue of plonky2's debug assertions: filtered gate constraints must vanish on every trace row and the
@@ -233,17 +257,30 @@ int stage_quotient(qpgpu_ctx *ctx, const CircuitPack &p, const StageTables &t, c
             if (res[2 * b + 1]) return ctx->fail(QPGPU_EUNSAT, "witness does not satisfy the circuit: a copy constraint is violated (permutation product != 1)" + who);
         }
     }
+    return QPGPU_OK;
+}
+
+int stage_quotient_values(qpgpu_ctx *ctx, const CircuitPack &p, const StageTables &t, const StageWork &w, uint32_t nb, const QuotientViews &v) {
+    hipStream_t st = ctx->stream;
+    const SmallLayout sl(p);
+    const u64 lde_n = 1ull << t.geom.log_lde, R = p.num_routed_wires;
+    const uint32_t nch = (uint32_t)p.num_challenges, nchunks = (uint32_t)p.num_chunks();
+    const unsigned L = t.geom.log_lde, Lq = t.geom.log_q, q_shift = t.geom.q_shift;
+    const size_t sig0 = p.num_selectors + p.num_constants, nterms = sl.nterms, SW = t.small_words;
+    const u64 q_n = 1ull << Lq;
+    u64 *d_betas = w.d_small + sl.betas, *d_gammas = w.d_small + sl.gammas, *d_bk = w.d_small + sl.bk, *d_apow = w.d_small + sl.apow, *d_pih = w.d_small + sl.pih;
+    QuotientArgs qa = quotient_args_base(ctx, p, t, w, nb);
     ctx->prof_begin("prove_quotient");
     qa.wires = v.wires_lde; qa.cs = t.cs_lde; qa.zs_pp = v.zs_lde; qa.x_coset = t.d_x_coset; qa.l0_coset = t.d_l0_coset;
     qa.zh_inv = t.d_zh_inv; qa.alpha_pows = d_apow; qa.beta_k_is = d_bk; qa.betas = d_betas; qa.gammas = d_gammas; qa.pi_hash = d_pih;
     qa.gates = t.d_gates; qa.acc = w.d_qacc; qa.poseidon_rc = t.d_poseidon_rc; qa.out = v.out;
-    qa.p2_gate = ctx->d_p2_app; qa.p2_layout = p.p2_layout; qa.lde_n = lde_n; qa.q_n = q_n; qa.q_shift = q_shift; qa.log_lde = L; qa.rate = 1u << p.rate_bits; qa.nch = nch;
+    qa.p2_gate = ctx->d_p2_app; qa.p2_layout = p.p2_layout; qa.lde_n = lde_n; qa.q_n = q_n; qa.q_shift = q_shift; qa.log_lde = L; qa.rate = 1u << t.geom.rate_bits; qa.nch = nch;
     qa.num_routed = (uint32_t)R; qa.chunk = (uint32_t)p.quotient_degree_factor; qa.nchunks = nchunks; qa.sig0 = (uint32_t)sig0;
     qa.num_selectors = (uint32_t)p.num_selectors; qa.num_gates = (uint32_t)p.gates.size(); qa.nterms = (uint32_t)nterms;
     qa.batch = nb; qa.ps_wires = v.ps_wires_lde; qa.ps_zs = v.ps_zs_lde; qa.ps_small = SW; qa.ps_acc = (u64)nch * lde_n; qa.ps_out = (u64)nch * q_n;
     qa.fused = t.quotient_fused ? 1 : 0; qa.fused_plain_map = t.quotient_plain_map ? 1 : 0; qa.pair = t.quotient_pair ? 1 : 0;
     QP_HIP(ctx, pk_quotient(qa, t.h_gates.data(), st));
-    // coset_ifft(g) on the quotient domain: ifft then scale coefficient i by g^-i; the qdf*n coefficients of a challenge
+    // coset_ifft(shift) on the quotient domain: ifft then scale coefficient i by shift^-i; the qdf*n coefficients of a challenge
     // are its qdf chunks of n, contiguous
     QP_TRY(ntt_run(ctx, v.out, v.out, Lq, Lq, (size_t)nch * nb, true, false, 0));
     QP_HIP(ctx, pk_scale_powers(v.out, q_n, (u64)nch * nb, t.d_ginv_lo, t.d_ginv_hi, t.ginv_lo_bits, st));

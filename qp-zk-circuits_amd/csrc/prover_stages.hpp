@@ -15,8 +15,19 @@
 // count words of device memory; secret = the region will hold witness-derived values (its owner overwrites it before release)
 using StageAlloc = std::function<int(gl::u64 **p, size_t count, bool secret)>;
 
+// The LDE that the s6 kernels walk. The circuit's own: shift g_mult, 2^(degree_bits + rate_bits) leaves, the quotient on every
+// 2^(rate_bits - qbits)-th point. One shard's of a coset-sharded oracle (quotient_shard_map.hpp): a whole LDE at a lower rate on a
+// shift of its own, so the same kernels evaluate it from tables built for that shift and rate.
+struct StageGeom {
+    gl::u64 shift = 0;                   // the LDE's points are shift * w_(log_lde)^i
+    unsigned log_lde = 0, rate_bits = 0;
+    unsigned q_shift = 0, log_q = 0;     // the quotient points: natural index >> q_shift, 2^log_q of them
+};
+StageGeom stage_geom_of(const CircuitPack &p);
+
 // What s5 and s6 read that does not depend on a witness. The owner (qpgpu_circuit, qpgpu_stage_plan) frees the allocations.
 struct StageTables {
+    StageGeom geom;                      // set by stage_tables_build
     // set by the owner: the constants/sigmas polynomials as values on the subgroup [num_cs_cols][n] and as LDE (leaf order, stride lde_n)
     const gl::u64 *cs_values = nullptr, *cs_lde = nullptr;
     // built by stage_tables_build
@@ -49,8 +60,10 @@ std::string stage_limits(const CircuitPack &p);
 // synchronous upload from pageable memory
 int h2d_sync(qpgpu_ctx *ctx, void *dst, const void *src, size_t bytes);
 // gate table, Poseidon constants, subgroup / coset / vanishing tables; reads the QPGPU_QUOTIENT_* switches
-int stage_tables_build(qpgpu_ctx *ctx, const CircuitPack &p, const StageAlloc &alloc, StageTables &t);
-int stage_work_alloc(const CircuitPack &p, const StageTables &t, const StageAlloc &alloc, uint32_t max_batch, StageWork &w);
+// (geom: the LDE of s6 where it is not the circuit's own, i.e. a shard's)
+int stage_tables_build(qpgpu_ctx *ctx, const CircuitPack &p, const StageAlloc &alloc, StageTables &t, const StageGeom *geom = nullptr);
+// quotient_only: the workspace of pk_quotient alone (a shard that runs neither s5 nor the witness check)
+int stage_work_alloc(const CircuitPack &p, const StageTables &t, const StageAlloc &alloc, uint32_t max_batch, StageWork &w, bool quotient_only = false);
 // pinned words the two stages put into StageWork::stage per batch
 size_t stage_ring_words(const StageTables &t, uint32_t max_batch);
 
@@ -80,3 +93,9 @@ struct QuotientViews {
 // the coset of size n * quotient_degree_factor and their coefficients: num_quotient_cols chunks of n, back to back, in v.out
 int stage_quotient(qpgpu_ctx *ctx, const CircuitPack &p, const StageTables &t, const StageWork &w, uint32_t nb, const gl::u64 *small,
                    const QuotientViews &v);
+// The two halves of stage_quotient, for a caller that runs them on different contexts (stage_api.cpp, a sharded plan): the alpha
+// upload, the fold sweep and the witness check when v.check_wires is set; then the quotient values on t.geom's points and their
+// coefficients in v.out, 2^t.geom.log_q per challenge (the inverse transform of that size, coefficient i times t.geom.shift^-i).
+int stage_quotient_prepare(qpgpu_ctx *ctx, const CircuitPack &p, const StageTables &t, const StageWork &w, uint32_t nb, const gl::u64 *small,
+                           const QuotientViews &v);
+int stage_quotient_values(qpgpu_ctx *ctx, const CircuitPack &p, const StageTables &t, const StageWork &w, uint32_t nb, const QuotientViews &v);

@@ -908,3 +908,95 @@ hipError_t pk_witness_check(const u64 *acc, u64 n, u32 nch, const u64 *z, const 
     if (n > 0 && batch > 0) hipLaunchKernelGGL(witness_check_kernel, dim3((unsigned)((n + 255) / 256), 1, batch), dim3(256), 0, st, acc, n, nch, z, rowprod, result);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------- s6 on a coset-sharded oracle: the shards' coefficients -> the chunks
+// Working shard g of Gq = 2^lq (quotient_shard_map.hpp) leaves B_e[j] = sum_c (q_(j + cM) g_mult^(cM)) w_Gq^(e c), e = brev_lq(g),
+// j < M, in block g of `gather` ([Gq][nch][M]). This is the last radix-Gq pass of the size Gq M inverse transform, with the coset
+// scaling of the high index folded in: q_(j + cM) = scale[c] sum_e w_Gq^(-e c) B_e[j], scale[c] = g_mult^(-cM) / Gq. tab: [Gq] the
+// powers w_Gq^-k, then [Gq] scale. Threads run along j (VEC adjacent ones each, 16-byte accesses at VEC = 2), the challenge is
+// grid.y: each of the Gq read streams and the Gq write streams is unit-stride, every word is read once and written once.
+namespace {
+
+template <int VEC> struct MergeWord;
+template <> struct MergeWord<1> {
+    u64 v[1];
+    __device__ __forceinline__ void load(const u64 *p) { v[0] = *p; }
+    __device__ __forceinline__ void store(u64 *p) const { *p = v[0]; }
+};
+template <> struct MergeWord<2> {
+    u64 v[2];
+    __device__ __forceinline__ void load(const u64 *p) { const ulonglong2 t = *reinterpret_cast<const ulonglong2 *>(p); v[0] = t.x; v[1] = t.y; }
+    __device__ __forceinline__ void store(u64 *p) const { *reinterpret_cast<ulonglong2 *>(p) = make_ulonglong2(v[0], v[1]); }
+};
+
+// the Gq values of one j in registers; block g holds exponent brev(g), so the decimation-in-time butterflies run on them as they lie
+template <int LQ, int VEC>
+__global__ void __launch_bounds__(256) quotient_merge_kernel(const u64 *gather, u64 *out, u64 m, u32 nch, const u64 *tab) {
+    constexpr int GQ = 1 << LQ;
+    const u64 j = (blockIdx.x * (u64)blockDim.x + threadIdx.x) * VEC;
+    if (j >= m) return;
+    const u64 ch = blockIdx.y;
+    MergeWord<VEC> x[GQ];
+#pragma unroll
+    for (int g = 0; g < GQ; g++) x[g].load(gather + ((u64)g * nch + ch) * m + j);
+#pragma unroll
+    for (int s = 1; s <= LQ; s++) {
+        const int half = 1 << (s - 1), step = GQ >> s;
+#pragma unroll
+        for (int k = 0; k < GQ; k += 2 * half)
+#pragma unroll
+            for (int t = 0; t < half; t++) {
+                const u64 w = tab[t * step];
+#pragma unroll
+                for (int e = 0; e < VEC; e++) {
+                    const u64 u = x[k + t].v[e], v = t ? gl::mul(x[k + t + half].v[e], w) : x[k + t + half].v[e];
+                    x[k + t].v[e] = gl::add(u, v); x[k + t + half].v[e] = gl::sub(u, v);
+                }
+            }
+    }
+#pragma unroll
+    for (int c = 0; c < GQ; c++) {
+        const u64 sc = tab[GQ + c];
+#pragma unroll
+        for (int e = 0; e < VEC; e++) x[c].v[e] = gl::canon(gl::mul(x[c].v[e], sc));
+        x[c].store(out + (ch * GQ + c) * m + j);
+    }
+}
+
+// any Gq: one output chunk c per grid.z, the Gq-term sum written out (the blocks are read Gq times, through the cache)
+__global__ void __launch_bounds__(256) quotient_merge_loop_kernel(const u64 *gather, u64 *out, u64 m, u32 nch, u32 lq, const u64 *tab) {
+    const u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const u32 gq = 1u << lq, c = blockIdx.z;
+    const u64 ch = blockIdx.y;
+    u64 sum = 0;
+    for (u32 e = 0; e < gq; e++) {
+        const u32 g = brev32(e, lq);
+        sum = gl::add(sum, gl::mul(gather[((u64)g * nch + ch) * m + j], tab[(e * c) & (gq - 1)]));
+    }
+    out[(ch * gq + c) * m + j] = gl::canon(gl::mul(sum, tab[gq + c]));
+}
+
+template <int LQ>
+void merge_launch(const u64 *gather, u64 *out, u64 m, u32 nch, const u64 *tab, hipStream_t st) {
+    // two adjacent j per thread where both ends allow 16-byte accesses: m is even, so every row then starts aligned
+    const bool vec = m % 2 == 0 && (((uintptr_t)gather | (uintptr_t)out) & 15) == 0;
+    const u64 threads = vec ? m / 2 : m;
+    dim3 b(256), g((unsigned)((threads + 255) / 256), nch);
+    if (vec) hipLaunchKernelGGL((quotient_merge_kernel<LQ, 2>), g, b, 0, st, gather, out, m, nch, tab);
+    else hipLaunchKernelGGL((quotient_merge_kernel<LQ, 1>), g, b, 0, st, gather, out, m, nch, tab);
+}
+
+}  // namespace
+
+hipError_t pk_quotient_merge(const u64 *gather, u64 *out, u64 m, u32 nch, u32 lq, const u64 *tab, hipStream_t st) {
+    if (m == 0 || nch == 0 || lq == 0 || lq > 8) return hipErrorInvalidValue;   // quotient_degree_factor <= 256 (circuit.cpp)
+    switch (lq) {
+        case 1: merge_launch<1>(gather, out, m, nch, tab, st); break;
+        case 2: merge_launch<2>(gather, out, m, nch, tab, st); break;
+        case 3: merge_launch<3>(gather, out, m, nch, tab, st); break;
+        default:
+            hipLaunchKernelGGL(quotient_merge_loop_kernel, dim3((unsigned)((m + 255) / 256), nch, 1u << lq), dim3(256), 0, st, gather, out, m, nch, lq, tab);
+    }
+    return hipGetLastError();
+}

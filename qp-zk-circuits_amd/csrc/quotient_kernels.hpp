@@ -67,5 +67,10 @@ hipError_t pk_gate_sums(const QuotientArgs &a, const GateDev *host_gates, hipStr
 // result: [batch][2]
 hipError_t pk_witness_check(const uint64_t *acc, uint64_t n, uint32_t nch, const uint64_t *z, const uint64_t *rowprod, uint64_t *result, uint32_t batch, hipStream_t st);
 
+// s6 over a coset-sharded oracle, the home context's step: gather [2^lq][nch][m], block g = working shard g's coefficients (the
+// size-m inverse transform of its values, coefficient j times its shift^-j); tab: [2^lq] powers of w_(2^lq)^-1, then [2^lq]
+// g_mult^(-c m) / 2^lq. out: [nch][2^lq m], the coefficient chunks as pk_scale_powers leaves them on one context. lq: 1..8
+hipError_t pk_quotient_merge(const uint64_t *gather, uint64_t *out, uint64_t m, uint32_t nch, uint32_t lq, const uint64_t *tab, hipStream_t st);
+
 // slot <-> point index of the leaf-ordered LDEs (s6, and the coset tables of prover_kernels.hip)
 __device__ __forceinline__ uint32_t brev32(uint32_t x, uint32_t bits) { return bits ? __brev(x) >> (32 - bits) : 0; }
