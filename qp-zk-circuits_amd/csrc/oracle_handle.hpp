@@ -33,6 +33,14 @@ struct qpgpu_oracle {
     std::unique_ptr<OracleShards> sh;               // qpgpu_oracle_commit_sharded
 };
 
+// a failure on a shard's context is reported where the caller looks: on the home context
+inline int shard_fail(qpgpu_ctx *home, uint32_t g, qpgpu_ctx *ctx, int rc) {
+    if (ctx != home) home->err = "shard " + std::to_string(g) + ": " + ctx->err;
+    return rc;
+}
+#define QP_SHARD(home, g, sctx, expr) do { int _rc = (expr); if (_rc) return shard_fail(home, g, sctx, _rc); } while (0)
+#define QP_SHARD_HIP(home, g, sctx, call) do { hipError_t _e = (call); if (_e != hipSuccess) return shard_fail(home, g, sctx, (sctx)->hip_fail(_e, #call)); } while (0)
+
 // the entries of oracle_api.cpp on a sharded oracle (oracle_sharded.cpp)
 void oracle_sharded_free(qpgpu_oracle *h);
 int oracle_sharded_read_lde(qpgpu_oracle *h, uint32_t first, uint32_t count, uint64_t *out);

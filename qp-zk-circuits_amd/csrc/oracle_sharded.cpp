@@ -16,14 +16,6 @@
 using gl::u64;
 
 namespace {
-// a failure on a shard's context is reported where the caller looks: on the home context
-int shard_fail(qpgpu_ctx *home, uint32_t g, qpgpu_ctx *ctx, int rc) {
-    if (ctx != home) home->err = "shard " + std::to_string(g) + ": " + ctx->err;
-    return rc;
-}
-#define QP_SHARD(home, g, sctx, expr) do { int _rc = (expr); if (_rc) return shard_fail(home, g, sctx, _rc); } while (0)
-#define QP_SHARD_HIP(home, g, sctx, call) do { hipError_t _e = (call); if (_e != hipSuccess) return shard_fail(home, g, sctx, (sctx)->hip_fail(_e, #call)); } while (0)
-
 bool same_hasher(const qpgpu_ctx *a, const qpgpu_ctx *b) {
     if (a->hasher.kind != b->hasher.kind) return false;
     return a->hasher.kind != hasher::POSEIDON2 || std::memcmp(&a->hasher.p2, &b->hasher.p2, sizeof(poseidon2::Params)) == 0;

@@ -65,17 +65,18 @@ int h2d_sync(qpgpu_ctx *ctx, void *dst, const void *src, size_t bytes) {
     return QPGPU_OK;
 }
 
-StageGeom stage_geom_of(const CircuitPack &p) {
-    // the quotient lives on the coset of size n * quotient_degree_factor: every 2^q_shift-th point of the LDE, i.e. its first q_n slots
-    unsigned qbits = 0; while ((1ull << qbits) < p.quotient_degree_factor) qbits++;
-    StageGeom g;
-    g.shift = gl::MULT_GEN; g.log_lde = (unsigned)(p.degree_bits + p.rate_bits); g.rate_bits = (unsigned)p.rate_bits;
-    g.q_shift = (unsigned)p.rate_bits - qbits; g.log_q = (unsigned)p.degree_bits + qbits;
-    return g;
+StageGeom stage_geom_of(const shard_map::QuotientMap &m, uint32_t g) {
+    // the quotient lives on the coset of size n * quotient_degree_factor: every 2^q_shift-th point of the LDE, i.e. its first q_n
+    // slots; a working shard holds 2^log_q of those points, every 2^q_shift-th of its own LDE on the shift g_mult w_(d+r)^brev(g)
+    StageGeom geom;
+    geom.shift = gl::canon(gl::mul(gl::MULT_GEN, gl::pow(gl::root_of_unity(m.d + m.r), m.shift_exponent(g))));
+    geom.log_lde = m.local_log_lde(); geom.rate_bits = m.local_rate_bits();
+    geom.q_shift = m.local_q_shift(); geom.log_q = m.log_points();
+    return geom;
 }
 
 int stage_tables_build(qpgpu_ctx *ctx, const CircuitPack &p, const StageAlloc &alloc, StageTables &t, const StageGeom *geom) {
-    t.geom = geom ? *geom : stage_geom_of(p);
+    t.geom = geom ? *geom : stage_geom_of(shard_map::QuotientMap::of((unsigned)p.degree_bits, (unsigned)p.rate_bits, p.quotient_degree_factor, 0), 0);
     const u64 n = p.n(), lde_n = 1ull << t.geom.log_lde;
     const unsigned d = (unsigned)p.degree_bits, L = t.geom.log_lde;
     // gates

@@ -11,19 +11,21 @@
 #include "ctx.hpp"
 #include "prover_host.hpp"
 #include "prover_kernels.hpp"
+#include "quotient_shard_map.hpp"
 
 // count words of device memory; secret = the region will hold witness-derived values (its owner overwrites it before release)
 using StageAlloc = std::function<int(gl::u64 **p, size_t count, bool secret)>;
 
 // The LDE that the s6 kernels walk. The circuit's own: shift g_mult, 2^(degree_bits + rate_bits) leaves, the quotient on every
 // 2^(rate_bits - qbits)-th point. One shard's of a coset-sharded oracle (quotient_shard_map.hpp): a whole LDE at a lower rate on a
-// shift of its own, so the same kernels evaluate it from tables built for that shift and rate.
+// shift of its own, so the same kernels evaluate it from tables built for that shift and rate. The circuit's own is the map of one
+// shard (lg = 0), shard 0.
 struct StageGeom {
     gl::u64 shift = 0;                   // the LDE's points are shift * w_(log_lde)^i
     unsigned log_lde = 0, rate_bits = 0;
     unsigned q_shift = 0, log_q = 0;     // the quotient points: natural index >> q_shift, 2^log_q of them
 };
-StageGeom stage_geom_of(const CircuitPack &p);
+StageGeom stage_geom_of(const shard_map::QuotientMap &m, uint32_t g);
 
 // What s5 and s6 read that does not depend on a witness. The owner (qpgpu_circuit, qpgpu_stage_plan) frees the allocations.
 struct StageTables {

@@ -19,6 +19,13 @@ namespace shard_map {
 
 struct QuotientMap {
     unsigned d = 0, r = 0, qbits = 0, lg = 0;
+    // a circuit's s6 over 2^lg shards; lg = 0 is the unsharded stage: one working shard, whose launch is the circuit's own LDE
+    static QuotientMap of(unsigned degree_bits, unsigned rate_bits, uint64_t quotient_degree_factor, unsigned lg) {
+        QuotientMap m;
+        m.d = degree_bits; m.r = rate_bits; m.lg = lg;
+        while ((1ull << m.qbits) < quotient_degree_factor) m.qbits++;
+        return m;
+    }
     unsigned q_shift() const { return r - qbits; }
     uint64_t nq() const { return 1ull << (d + qbits); }
     unsigned log_working() const { return lg > q_shift() ? lg - q_shift() : 0; }      // lq

@@ -1,7 +1,7 @@
 // Drives the index arithmetic of stage s6 over a coset-sharded oracle (csrc/quotient_shard_map.hpp), which has no HIP in it, under
-// the address and undefined-behaviour sanitizers: for every (degree_bits, rate_bits, qbits, shards) on the command line's grid it
-// prints which shards evaluate quotient points, each one's launch, the quotient index of every local point and where every
-// (exponent, j, c) of the merge reads and writes, one record per line. Built and run by tests/test_quotient_shard_map_host.py,
+// the address and undefined-behaviour sanitizers: for every (degree_bits, rate_bits, qbits, shards) on the command line's grid, one
+// shard (the stage on one context, lg = 0) included, it prints which shards evaluate quotient points, each one's launch, the quotient
+// index of every local point and where every (exponent, j, c) of the merge reads and writes, one record per line. Built and run by tests/test_quotient_shard_map_host.py,
 // which checks every line against Python integers.
 //   quotient_shard_map <max degree_bits> <max rate_bits> <max qbits>
 #include <cstdio>
@@ -14,11 +14,16 @@ int main(int argc, char **argv) {
     for (unsigned d = 1; d <= max_d; d++)
         for (unsigned r = 1; r <= max_r; r++)
             for (unsigned qbits = 0; qbits <= max_q && qbits <= r; qbits++)
-                for (uint32_t G = 2; G <= (1u << r); G *= 2) {
-                    const int lg = shard_map::log2_shards(G, r);
+                for (uint32_t G = 1; G <= (1u << r); G *= 2) {
+                    // G = 1 is the stage on one context (a plan that is not sharded): log2_shards refuses it for the commitments
+                    const int lg = G == 1 ? 0 : shard_map::log2_shards(G, r);
                     if (lg < 0) { std::printf("FAIL log2_shards %u %u\n", G, r); return 1; }
-                    shard_map::QuotientMap m;
-                    m.d = d; m.r = r; m.qbits = qbits; m.lg = (unsigned)lg;
+                    const shard_map::QuotientMap m = shard_map::QuotientMap::of(d, r, 1ull << qbits, (unsigned)lg);
+                    // qbits = ceil(log2 factor): the smallest factor that needs qbits bits gives it as the largest does
+                    if (m.qbits != qbits || shard_map::QuotientMap::of(d, r, (1ull << qbits) / 2 + 1, (unsigned)lg).qbits != qbits) {
+                        std::printf("FAIL qbits %u %u\n", m.qbits, qbits);
+                        return 1;
+                    }
                     std::printf("case %u %u %u %u\n", d, r, qbits, G);
                     std::printf("domain %u %llu %u %u %llu\n", m.q_shift(), (unsigned long long)m.nq(), m.log_working(), m.working(),
                                 (unsigned long long)m.points());

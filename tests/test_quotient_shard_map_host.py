@@ -1,7 +1,7 @@
 """The index arithmetic of stage s6 over coset-sharded oracles (qpgpu_stage_plan_create_sharded; csrc/quotient_shard_map.hpp), the
 part that needs no device: tests/native/quotient_shard_map_main.cpp compiled with the header alone under AddressSanitizer and
-UndefinedBehaviorSanitizer prints, for every d in 1..4, r in 1..5, qbits in 0..min(r, 3) and every shard count G = 2 .. 2^r, which
-shards hold quotient points, each working shard's launch (local LDE size, rate, q_shift, number of points M, exponent e), the
+UndefinedBehaviorSanitizer prints, for every d in 1..4, r in 1..5, qbits in 0..min(r, 3) and every shard count G = 1 .. 2^r (G = 1: the
+stage on one context, whose plan takes its geometry from the same arithmetic), which shards hold quotient points, each working shard's launch (local LDE size, rate, q_shift, number of points M, exponent e), the
 quotient index of each of its points and the merge's read blocks and write positions; every line is checked here against a few
 lines of Python integers. The merge formula itself (the shards' size-M inverse transforms, the (g_mult w^e)^-j scaling on the shard
 and the Gq-point inverse transform with g_mult^(-cM) / Gq on the home context) is run in Python integers against directly chosen
@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = 0xFFFFFFFF00000001
 MULT_GEN = 14293326489335486720
 ROOT_2_32 = 7277203076849721926
-CASES = [(d, r, q, 1 << lg) for d in range(1, 5) for r in range(1, 6) for q in range(0, min(r, 3) + 1) for lg in range(1, r + 1)]
+CASES = [(d, r, q, 1 << lg) for d in range(1, 5) for r in range(1, 6) for q in range(0, min(r, 3) + 1) for lg in range(0, r + 1)]
 
 
 def brev(x, bits):
@@ -91,6 +91,20 @@ def test_working_shards_and_their_launches(records, d, r, q, G):
         assert points[g] == [x >> q_shift for x in glob] == [e + Gq * k for k in range(M)]
         # the shard's shift is the quotient coset's shift times w_(d+q)^e
         assert pow(root(d + r), brev(g, lg), P) == pow(root(d + q), e, P)
+
+
+@pytest.mark.parametrize("d,r,q", sorted({c[:3] for c in CASES}))
+def test_one_shard_is_the_unsharded_stage(records, d, r, q):
+    """lg = 0 is where a plan on one context takes its s6 geometry from: one working shard whose launch is the circuit's own LDE
+    (2^(d + r) leaves at rate 2^r on the shift g_mult itself, the quotient on every 2^(r - qbits)-th point), its points the
+    quotient domain in order, and a merge that moves nothing."""
+    recs = records[(d, r, q, 1)]
+    Nq = 1 << (d + q)
+    assert of_kind(recs, "domain") == [[r - q, Nq, 0, 1, Nq]], "one working shard, M = Nq"
+    assert of_kind(recs, "shard") == [[0, 1, d + r, r, r - q, d + q, 0, 0]], "the circuit's LDE, exponent and shift exponent 0"
+    assert of_kind(recs, "points") == [[0] + list(range(Nq))], "local point i is quotient index i"
+    assert of_kind(recs, "out") == [[0] + list(range(Nq))], "the single merge line is the identity"
+    assert of_kind(recs, "blocks") == [[0]]
 
 
 @pytest.mark.parametrize("d,r,q,G", CASES)
