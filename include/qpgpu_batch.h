@@ -27,6 +27,7 @@
 #define QPGPU_BATCH_H
 #include <stddef.h>
 #include <stdint.h>
+#include "qpgpu_wire.h"                      /* qpgpu_circuit_config */
 
 #ifdef __cplusplus
 extern "C" {
@@ -245,6 +246,29 @@ int qpgpu_builder_gadget_circuit(unsigned kind, uint64_t *pack_out, size_t pack_
 int qpgpu_wrapper_circuit_build(const uint64_t *inner_pack, size_t inner_words, const uint64_t *inner_cs_cap, size_t cap_words, unsigned num_proofs,
                                 unsigned num_routed_wires, unsigned min_degree_bits, int inner_hasher, unsigned flags, uint64_t *pack_out, size_t pack_cap_words,
                                 size_t *pack_words, uint64_t *target_map_out, size_t map_cap, size_t *map_count, uint64_t *info_out, char *err);
+/* PrivateBatchCircuit::new(config, ..) / PublicBatchCircuit::new(config, ..) (private_batch/circuit/circuit_logic.rs:88,
+ * public_batch/circuit/circuit_logic.rs:63; PrivateBatchProver::new / PublicBatchProver::new hand their CircuitConfig down to them): the
+ * same circuit under a caller's CircuitConfig. cfg = NULL is qpgpu_wrapper_circuit_build, word for word (pack, target map, its 12 info
+ * words, the blinding cells after the query-index block), and qpgpu_wrapper_circuit_build is this entry with cfg = NULL. With a config,
+ * the config carries the routed-wire count and zero knowledge: num_routed_wires must be 0 and QPGPU_WRAPPER_ZERO_KNOWLEDGE clear
+ * (QPGPU_EINVAL naming the argument otherwise). The config first goes through qpgpu_validate_circuit_config (a refusal is QPGPU_EINVAL
+ * with that function's message); then what the native builder does not model is refused by name, by the policy the leaf entry shares
+ * (csrc/builder_config.hpp; only the entry's name in front of the message differs): security_bits other than 100,
+ * use_base_arithmetic_gate = false, max_quotient_degree_factor other than 8 (the quotient kernels take a power-of-two factor),
+ * num_constants other than 2, reduction arity bits outside 1..4, final polynomial bits above 8, proof_of_work_bits above 32. The fork's
+ * second zero-knowledge mode is un-vendored: zero_knowledge = 1 is upstream's CircuitBuilder::blind. An inner cap_height whose
+ * RandomAccessGate copy (2 + 2^cap_height routed wires) does not fit the config's routed wires is QPGPU_EINVAL naming both numbers.
+ * Below 48 routed wires the Poseidon MDS layer at zeta is laid in its arithmetic form (Poseidon::mds_layer_circuit's own fallback;
+ * the bare-argument entry refuses such a width, as it always has). The pack header carries the config: a pack built from
+ * qpgpu_wormhole_circuit_config(level) passes qpgpu_pack_config_is_canonical(.., level), any other fails naming the field. A circuit
+ * whose LDE would pass 2^23 points still builds here and is refused when loaded. info_out: QPGPU_WRAPPER_CIRCUIT_INFO_WORDS_CFG words
+ * when cfg is given — the 12 above, then PoseidonMdsGate rows, ArithmeticExtensionGate rows, CosetInterpolationGate rows, ReducingGate +
+ * ReducingExtensionGate rows. err: QPGPU_CONFIG_ERR_CAP bytes when cfg is given (the reference's messages are long). */
+#define QPGPU_WRAPPER_CIRCUIT_INFO_WORDS_CFG 16
+int qpgpu_wrapper_circuit_build_cfg(const uint64_t *inner_pack, size_t inner_words, const uint64_t *inner_cs_cap, size_t cap_words, unsigned num_proofs,
+                                    unsigned num_routed_wires, unsigned min_degree_bits, int inner_hasher, unsigned flags, const qpgpu_circuit_config *cfg,
+                                    uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, size_t map_cap, size_t *map_count,
+                                    uint64_t *info_out, char *err);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,27 @@ int qpgpu_validate_circuit_config(const qpgpu_circuit_config *cfg, char *err);  
  * of work, query rounds, zero knowledge) against the level's canonical config. */
 int qpgpu_pack_config_is_canonical(const uint64_t *pack_words, size_t n_words, int level, char *err);   /* err: QPGPU_CONFIG_ERR_CAP bytes */
 
+/* ---- the aggregation layer's config knobs (wormhole/memprof/src/config.rs:52-316: AggConfigArgs::validate / ::build) ----
+ * The overrides a sweep puts on top of the production private-batch config, as plain data: a field counts only when its
+ * QPGPU_AGG_HAS_* bit is set in `present` (0 is a value the reference refuses, so it cannot stand for "unset").
+ * validate: 0, or -1 with the reference's message — "{flag} must be greater than 0", the ceilings of rate_bits and cap_height,
+ * the rate / quotient-degree rule on the EFFECTIVE pair (override or baseline), the floors of num_wires,
+ * max_quotient_degree_factor and num_routed_wires, routed <= the effective num_wires, and the four security-affecting knobs
+ * (zk_mode disabled, num_query_rounds, security_bits, num_challenges) behind allow_weakening_security.
+ * build: starts from qpgpu_wormhole_circuit_config(QPGPU_LEVEL_PRIVATE_BATCH); rate_bits = v also sets num_query_rounds =
+ * ceil(3 * 28 / v) (the FRI soundness product kept); an explicit num_query_rounds wins. build does not validate. */
+enum { QPGPU_AGG_HAS_ZK_MODE = 1, QPGPU_AGG_HAS_RATE_BITS = 2, QPGPU_AGG_HAS_CAP_HEIGHT = 4, QPGPU_AGG_HAS_NUM_WIRES = 8, QPGPU_AGG_HAS_NUM_ROUTED_WIRES = 16,
+       QPGPU_AGG_HAS_MAX_QUOTIENT_DEGREE_FACTOR = 32, QPGPU_AGG_HAS_NUM_QUERY_ROUNDS = 64, QPGPU_AGG_HAS_SECURITY_BITS = 128, QPGPU_AGG_HAS_NUM_CHALLENGES = 256 };
+enum { QPGPU_ZK_MODE_ROWBLINDING = 0, QPGPU_ZK_MODE_DISABLED = 1 };
+typedef struct {
+    uint32_t present;                  /* QPGPU_AGG_HAS_* */
+    int zk_mode;                       /* QPGPU_ZK_MODE_* */
+    uint64_t rate_bits, cap_height, num_wires, num_routed_wires, max_quotient_degree_factor, num_query_rounds, security_bits, num_challenges;
+    int allow_weakening_security;
+} qpgpu_agg_config_args;
+int qpgpu_agg_config_validate(const qpgpu_agg_config_args *args, char *err);                 /* err: QPGPU_CONFIG_ERR_CAP bytes */
+int qpgpu_agg_config_build(const qpgpu_agg_config_args *args, qpgpu_circuit_config *out);    /* -1 for a null argument */
+
 #ifdef __cplusplus
 }
 #endif

@@ -267,6 +267,26 @@ extern "C" {
                                        num_routed_wires: u32, min_degree_bits: u32, inner_hasher: i32, flags: u32, pack_out: *mut u64, pack_cap_words: usize,
                                        pack_words: *mut usize, target_map_out: *mut u64, map_cap: usize, map_count: *mut usize, info_out: *mut u64,
                                        err: *mut c_char) -> i32;
+    // PrivateBatchCircuit::new(config, ..) / PublicBatchCircuit::new(config, ..): the same circuit under a caller's CircuitConfig (cfg null:
+    // the entry above word for word). With cfg: num_routed_wires = 0 and no QPGPU_WRAPPER_ZERO_KNOWLEDGE (the config carries both),
+    // info_out has QPGPU_WRAPPER_CIRCUIT_INFO_WORDS_CFG (16) words, err QPGPU_CONFIG_ERR_CAP (400) bytes.
+    pub fn qpgpu_wrapper_circuit_build_cfg(inner_pack: *const u64, inner_words: usize, inner_cs_cap: *const u64, cap_words: usize, num_proofs: u32,
+                                           num_routed_wires: u32, min_degree_bits: u32, inner_hasher: i32, flags: u32, cfg: *const QpgpuCircuitConfig,
+                                           pack_out: *mut u64, pack_cap_words: usize, pack_words: *mut usize, target_map_out: *mut u64, map_cap: usize,
+                                           map_count: *mut usize, info_out: *mut u64, err: *mut c_char) -> i32;
+    // AggConfigArgs::validate / ::build (wormhole/memprof/src/config.rs): the sweep knobs on top of the production private-batch config
+    pub fn qpgpu_agg_config_validate(args: *const QpgpuAggConfigArgs, err: *mut c_char) -> i32;
+    pub fn qpgpu_agg_config_build(args: *const QpgpuAggConfigArgs, out: *mut QpgpuCircuitConfig) -> i32;
+}
+/// qpgpu_agg_config_args (include/qpgpu_wire.h): a knob counts only when its QPGPU_AGG_HAS_* bit is set in `present`
+/// (zk_mode 1, rate_bits 2, cap_height 4, num_wires 8, num_routed_wires 16, max_quotient_degree_factor 32, num_query_rounds 64,
+/// security_bits 128, num_challenges 256); zk_mode: 0 rowblinding, 1 disabled
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct QpgpuAggConfigArgs {
+    pub present: u32, pub zk_mode: i32,
+    pub rate_bits: u64, pub cap_height: u64, pub num_wires: u64, pub num_routed_wires: u64, pub max_quotient_degree_factor: u64,
+    pub num_query_rounds: u64, pub security_bits: u64, pub num_challenges: u64,
+    pub allow_weakening_security: i32,
 }
 #[repr(C)] pub struct QpgpuZkTree { _p: [u8; 0] }
 /// qpgpu_zk_leaf (include/qpgpu_leaf.h): what a leaf of the ZK tree hashes; 48 bytes

@@ -16,6 +16,7 @@ from .binding import PolyOracle, Challenger, fri_prove, set_hasher_poseidon, set
 from .binding import pack_header, pack_public_input_cells, Verifier, poseidon2_qp_params, synth_p2_sites  # noqa: F401
 from .binding import pack_p2_layout, pack_trailers, p2_site_cells, P2_NO_SWAP  # noqa: F401
 from .binding import CircuitConfig, circuit_config, validate_circuit_config  # noqa: F401
+from .binding import AggConfigArgs, agg_config_args, agg_config_validate, agg_config_build, parse_agg_config_flags  # noqa: F401
 from .binding import FP, FP_OPS, field_probe_host, field_probe_shape  # noqa: F401
 from . import sharding  # noqa: F401,E402
 from . import aggregation  # noqa: F401,E402

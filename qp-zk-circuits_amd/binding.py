@@ -407,6 +407,75 @@ def validate_circuit_config(config):
     return None if lib.qpgpu_validate_circuit_config(ctypes.byref(as_circuit_config(config)), err) == 0 else err.value.decode()
 
 
+class AggConfigArgs(ctypes.Structure):
+    """qpgpu_agg_config_args (include/qpgpu_wire.h): the reference's AggConfigArgs (wormhole/memprof/src/config.rs) — overrides on top of
+    the production private-batch config, each with a presence bit."""
+    KNOBS = ("rate_bits", "cap_height", "num_wires", "num_routed_wires", "max_quotient_degree_factor", "num_query_rounds", "security_bits", "num_challenges")
+    HAS = dict(zk_mode=1, **{k: 2 << i for i, k in enumerate(KNOBS)})
+    ZK_MODES = {"rowblinding": 0, "disabled": 1}
+    _fields_ = [("present", ctypes.c_uint32), ("zk_mode", ctypes.c_int)] + [(k, ctypes.c_uint64) for k in KNOBS] + [("allow_weakening_security", ctypes.c_int)]
+
+
+def agg_config_args(allow_weakening_security=False, **knobs):
+    """AggConfigArgs from keyword overrides: zk_mode="rowblinding" / "disabled", the numeric knobs of AggConfigArgs.KNOBS; a knob
+    left out (or None) is unset."""
+    a = AggConfigArgs()
+    a.allow_weakening_security = 1 if allow_weakening_security else 0
+    for k, v in knobs.items():
+        if k not in AggConfigArgs.HAS:
+            raise TypeError("AggConfigArgs has no knob %r" % k)
+        if v is None:
+            continue
+        a.present |= AggConfigArgs.HAS[k]
+        setattr(a, k, AggConfigArgs.ZK_MODES[v] if k == "zk_mode" else int(v))
+    return a
+
+
+def agg_config_validate(args):
+    """AggConfigArgs::validate: None, or the reference's message."""
+    lib = load_library()
+    lib.qpgpu_agg_config_validate.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+    err = ctypes.create_string_buffer(CONFIG_ERR_CAP)
+    return None if lib.qpgpu_agg_config_validate(ctypes.byref(args), err) == 0 else err.value.decode()
+
+
+def agg_config_build(args):
+    """AggConfigArgs::build: the production private-batch config with the overrides applied (rate_bits re-balances num_query_rounds)."""
+    lib = load_library()
+    lib.qpgpu_agg_config_build.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    c = CircuitConfig()
+    if lib.qpgpu_agg_config_build(ctypes.byref(args), ctypes.byref(c)) != 0:
+        raise ValueError("agg_config_build: bad argument")
+    return c
+
+
+def parse_agg_config_flags(argv):
+    """The aggregation-config flags of the reference's memprof command line ("--zk-mode rowblinding --num-routed-wires 54 ..") ->
+    (AggConfigArgs, the other flags as a dict). A --zk-mode this library has no circuit for ("polyfri": the fork's second
+    zero-knowledge mode is un-vendored) raises ValueError naming it."""
+    knobs, other, allow = {}, {}, False
+    it = iter(argv)
+    for flag in it:
+        if not flag.startswith("--"):
+            raise ValueError("unexpected argument %r" % flag)
+        name = flag[2:].replace("-", "_")
+        if name in ("allow_weakening_security", "skip_leaf_gen"):
+            allow, other = (True, other) if name == "allow_weakening_security" else (allow, dict(other, skip_leaf_gen=True))
+            continue
+        value = next(it, None)
+        if value is None:
+            raise ValueError("%s needs a value" % flag)
+        if name == "zk_mode":
+            if value not in AggConfigArgs.ZK_MODES:
+                raise ValueError("--zk-mode %s: not a mode this library builds (rowblinding, disabled); the fork's second zero-knowledge mode is un-vendored" % value)
+            knobs[name] = value
+        elif name in AggConfigArgs.KNOBS:
+            knobs[name] = int(value)
+        else:
+            other[name] = value
+    return agg_config_args(allow_weakening_security=allow, **knobs), other
+
+
 def pack_header(pack_words):
     """The fixed header of a circuit pack (csrc/circuit.hpp) as a dict. Host only."""
     names = ["degree_bits", "num_wires", "num_routed_wires", "num_constants", "num_selectors", "num_challenges",

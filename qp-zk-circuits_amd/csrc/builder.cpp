@@ -194,7 +194,8 @@ ExtTarget Builder::arithmetic_ext(u64 c0, u64 c1, ExtTarget m0, ExtTarget m1, Ex
 }
 
 ExtTarget Builder::reduce_base(ExtTarget alpha, const std::vector<Target> &terms) {
-    const uint32_t n = std::min<uint32_t>((cfg_.num_wires - 6) / 3, cfg_.num_routed_wires - 6);      // ReducingGate::max_coeffs_len
+    // ReducingGate::max_coeffs_len: 3 D routed wires before the coefficients; the last accumulator is the output, so 2 D + (D + 1) n wires
+    const uint32_t n = std::min<uint32_t>((cfg_.num_wires - 4) / 3, cfg_.num_routed_wires - 6);
     std::vector<Target> rev(terms);
     while (rev.size() % n) rev.push_back(zero());
     std::reverse(rev.begin(), rev.end());
@@ -208,7 +209,7 @@ ExtTarget Builder::reduce_base(ExtTarget alpha, const std::vector<Target> &terms
     return acc;
 }
 ExtTarget Builder::reduce_ext(ExtTarget alpha, const std::vector<ExtTarget> &terms) {
-    const uint32_t n = std::min<uint32_t>((cfg_.num_wires - 6) / 4, (cfg_.num_routed_wires - 6) / 2);  // ReducingExtensionGate::max_coeffs_len
+    const uint32_t n = std::min<uint32_t>((cfg_.num_wires - 4) / 4, (cfg_.num_routed_wires - 6) / 2);  // ReducingExtensionGate::max_coeffs_len: 2 D + 2 D n wires
     std::vector<ExtTarget> rev(terms);
     while (rev.size() % n) rev.push_back(zero_ext());
     std::reverse(rev.begin(), rev.end());
@@ -228,14 +229,30 @@ ExtTarget Builder::interpolate_coset(unsigned bits, Target shift, const std::vec
     // CosetInterpolationGate::with_max_degree: as few intermediates as the degree bound allows, then the smallest degree with that many
     const uint64_t n_int = (np - 2) / (max_degree - 1), degree = (np - 2) / (n_int + 1) + 2;
     const uint32_t s_ep = 1 + 2 * (uint32_t)np, row = add_gate(spec_index(GATE_COSET_INTERPOLATION, bits, degree, 0));
-    if (s_ep + 4 > cfg_.num_routed_wires) throw std::logic_error("interpolate_coset: too few routed wires");
+    if (s_ep + 4 > cfg_.num_routed_wires)
+        throw std::invalid_argument("interpolate_coset: too few routed wires: a CosetInterpolationGate over 2^" + std::to_string(bits) + " points routes " + std::to_string(s_ep + 4) +
+                                    " wires, the circuit config has " + std::to_string(cfg_.num_routed_wires));
+    // (its unrouted wires: the shifted point and the intermediates, 2 D each)
+    if (s_ep + 4 + 2 + 4 * n_int > cfg_.num_wires) throw std::invalid_argument("interpolate_coset: too few wires for the gate's intermediates");
     connect(shift, wire(row, 0));
     for (uint32_t i = 0; i < np; i++) for (uint32_t e = 0; e < 2; e++) connect(values[i].t[e], wire(row, 1 + 2 * i + e));
     for (uint32_t e = 0; e < 2; e++) connect(point.t[e], wire(row, s_ep + e));
     return {{wire(row, s_ep + 2), wire(row, s_ep + 3)}};
 }
 std::array<ExtTarget, 12> Builder::poseidon_mds_ext(const std::array<ExtTarget, 12> &in) {
-    if (cfg_.num_routed_wires < 48) throw std::logic_error("poseidon_mds_ext: too few routed wires");
+    if (cfg_.num_routed_wires < 48) {
+        if (!cfg_.mds_arithmetic_fallback) throw std::logic_error("poseidon_mds_ext: too few routed wires");
+        // Poseidon::mds_layer_circuit without the gate (num_routed_wires < PoseidonMdsGate::num_wires() = 24 D): mds_row_shf_circuit, one
+        // mul_const_add_extension per entry of the circulant row, then the diagonal's (all zero but the first: folds away)
+        static const u64 CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20}, DIAG[12] = {8, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        std::array<ExtTarget, 12> out;
+        for (uint32_t r = 0; r < 12; r++) {
+            ExtTarget res = zero_ext();
+            for (uint32_t i = 0; i < 12; i++) res = mul_add_ext(constant_ext(CIRC[i]), in[(i + r) % 12], res);
+            out[r] = mul_add_ext(constant_ext(DIAG[r]), in[r], res);
+        }
+        return out;
+    }
     const uint32_t row = add_gate(spec_index(GATE_POSEIDON_MDS, 0, 0, 0));
     std::array<ExtTarget, 12> out;
     for (uint32_t i = 0; i < 12; i++) for (uint32_t e = 0; e < 2; e++) { connect(in[i].t[e], wire(row, 2 * i + e)); out[i].t[e] = wire(row, 24 + 2 * i + e); }
@@ -366,7 +383,10 @@ Target Builder::random_access(Target access_index, const std::vector<Target> &v)
     // RandomAccessGate::new_from_config: as many copies as the routed wires (2 + 2^bits each) and the wires (+ bits each) hold
     const uint32_t vec = 1u << bits;
     const uint32_t copies = std::min<uint32_t>(cfg_.num_routed_wires / (2 + vec), cfg_.num_wires / (2 + vec + bits));
-    if (copies == 0) throw std::logic_error("random_access: the gate does not fit the routed wires");
+    if (copies == 0)
+        throw std::invalid_argument("random_access: a RandomAccessGate over 2^" + std::to_string(bits) + " entries needs " + std::to_string(2 + vec) + " routed wires and " +
+                                    std::to_string(2 + vec + bits) + " wires per copy; the circuit config has " + std::to_string(cfg_.num_routed_wires) + " and " +
+                                    std::to_string(cfg_.num_wires) + " (zero copies)");
     const uint32_t extra = std::min<uint32_t>(cfg_.num_routed_wires - (2 + vec) * copies, cfg_.num_constants);
     auto slot = ra_slots_.find(bits);
     uint32_t row, copy;

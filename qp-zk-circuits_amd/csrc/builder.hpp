@@ -41,6 +41,9 @@ struct Config {
     int inner_hasher = 0;            // hasher::POSEIDON / hasher::POSEIDON2: the permutation gate the public-input hash is built from
     P2GateLayout p2_layout;          // wire layout of the fork's Poseidon2 gate (LAYOUT UNPINNED, circuit.hpp)
     unsigned min_degree_bits = 0;    // pad with NoopGate rows to at least 2^min_degree_bits rows
+    // Poseidon::mds_layer_circuit below PoseidonMdsGate's 24 D routed wires: the arithmetic form over extension targets (set for a
+    // circuit built from a caller's CircuitConfig); false: poseidon_mds_ext refuses such a width, as the bare-argument entries always have
+    bool mds_arithmetic_fallback = false;
     std::string validate() const;
 };
 

@@ -31,6 +31,7 @@
 #include "../../include/qpgpu_leaf.h"
 #include "../../include/qpgpu_wire.h"
 #include "builder.hpp"
+#include "builder_config.hpp"
 #include "gadgets.hpp"
 #include "poseidon.hpp"
 
@@ -289,39 +290,10 @@ void logical_targets(const CircuitTargets &t, Target *lt) {
 
 extern "C" {
 
-// WormholeProver::new(config) / WormholeCircuit::new(config) (wormhole/prover/src/lib.rs:137-149, circuit/src/circuit.rs:115-152): the
-// caller's CircuitConfig, or wormhole_leaf_circuit_config() for NULL, checked the way every Wormhole circuit constructor checks it
-// (validate_circuit_config, with its messages) and carried over into the builder's Config. The two fields the builder does not model
-// must hold standard_recursion_config's values: a config that asks for anything else is refused, not built as something it is not.
+// WormholeProver::new(config) / WormholeCircuit::new(config): the caller's CircuitConfig, or wormhole_leaf_circuit_config() for NULL, through
+// the policy every circuit entry shares (builder_config.hpp: validate_circuit_config with its messages, then what the builder does not model)
 static int leaf_builder_config(const qpgpu_circuit_config *user, cb::Config &cfg, char *err, size_t err_cap) {
-    auto fail = [&](const std::string &m) { if (err) std::snprintf(err, err_cap, "%s", m.c_str()); return QPGPU_EINVAL; };
-    qpgpu_circuit_config std_cfg;
-    qpgpu_wormhole_circuit_config(QPGPU_LEVEL_LEAF, &std_cfg);
-    const qpgpu_circuit_config c = user ? *user : std_cfg;
-    char why[QPGPU_CONFIG_ERR_CAP];
-    why[0] = 0;
-    if (qpgpu_validate_circuit_config(&c, why) != 0) return fail(why);
-    if (c.security_bits != std_cfg.security_bits)
-        return fail("leaf_circuit_build: circuit config security_bits (" + std::to_string(c.security_bits) + ") is not modelled by this builder; only " +
-                    std::to_string(std_cfg.security_bits) + " (standard_recursion_config) is accepted");
-    if ((c.use_base_arithmetic_gate != 0) != (std_cfg.use_base_arithmetic_gate != 0))
-        return fail("leaf_circuit_build: circuit config use_base_arithmetic_gate = false is not modelled by this builder; only true (standard_recursion_config) is accepted");
-    const struct { const char *name; uint64_t v; unsigned *to; } f[11] = {
-        {"num_wires", c.num_wires, &cfg.num_wires}, {"num_routed_wires", c.num_routed_wires, &cfg.num_routed_wires}, {"num_constants", c.num_constants, &cfg.num_constants},
-        {"num_challenges", c.num_challenges, &cfg.num_challenges}, {"max_quotient_degree_factor", c.max_quotient_degree_factor, &cfg.max_quotient_degree_factor},
-        {"fri_config.rate_bits", c.rate_bits, &cfg.rate_bits}, {"fri_config.cap_height", c.cap_height, &cfg.cap_height},
-        {"fri_config.proof_of_work_bits", c.proof_of_work_bits, &cfg.proof_of_work_bits}, {"fri_config.num_query_rounds", c.num_query_rounds, &cfg.num_query_rounds},
-        {"fri_config.reduction_strategy arity_bits", c.reduction_arity_bits, &cfg.arity_bits}, {"fri_config.reduction_strategy final_poly_bits", c.reduction_final_poly_bits, &cfg.final_poly_bits}};
-    for (const auto &x : f) {
-        if (x.v > 0xFFFFu) return fail(std::string("leaf_circuit_build: circuit config ") + x.name + " (" + std::to_string(x.v) + ") out of range");
-        *x.to = (unsigned)x.v;
-    }
-    // what the prover's transcript and FRI code take for granted about these three (Builder::validate covers the rest)
-    if (cfg.proof_of_work_bits > 32) return fail("leaf_circuit_build: circuit config fri_config.proof_of_work_bits (" + std::to_string(c.proof_of_work_bits) + ") must be <= 32");
-    if (cfg.arity_bits == 0 || cfg.arity_bits > 4) return fail("leaf_circuit_build: circuit config fri_config.reduction_strategy arity_bits (" + std::to_string(c.reduction_arity_bits) + ") must be 1..4");
-    if (cfg.final_poly_bits > 8) return fail("leaf_circuit_build: circuit config fri_config.reduction_strategy final_poly_bits (" + std::to_string(c.reduction_final_poly_bits) + ") must be <= 8");
-    cfg.zero_knowledge = c.zero_knowledge != 0;
-    return QPGPU_OK;
+    return cb::config_from_circuit_config("leaf_circuit_build", QPGPU_LEVEL_LEAF, user, cfg, err, err_cap);
 }
 
 // copies > 1 (qpgpu_leaf_circuit_build_dense): the full circuit's five fragments and connect_shared_targets laid `copies` times over

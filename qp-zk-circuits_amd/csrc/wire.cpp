@@ -291,6 +291,75 @@ int qpgpu_validate_circuit_config(const qpgpu_circuit_config *c, char *err) {
     return 0;
 }
 
+// ---- AggConfigArgs (wormhole/memprof/src/config.rs:131-316), message for message ----
+int qpgpu_agg_config_validate(const qpgpu_agg_config_args *a, char *err) {
+    if (err) err[0] = 0;
+    if (!a) return cfg_fail(err, "null argument");
+    typedef unsigned long long ull;
+    auto has = [&](uint32_t bit) { return (a->present & bit) != 0; };
+    const struct { const char *name; uint32_t bit; uint64_t v; } knobs[8] = {
+        {"--rate-bits", QPGPU_AGG_HAS_RATE_BITS, a->rate_bits}, {"--cap-height", QPGPU_AGG_HAS_CAP_HEIGHT, a->cap_height}, {"--num-wires", QPGPU_AGG_HAS_NUM_WIRES, a->num_wires},
+        {"--num-routed-wires", QPGPU_AGG_HAS_NUM_ROUTED_WIRES, a->num_routed_wires}, {"--max-quotient-degree-factor", QPGPU_AGG_HAS_MAX_QUOTIENT_DEGREE_FACTOR, a->max_quotient_degree_factor},
+        {"--num-query-rounds", QPGPU_AGG_HAS_NUM_QUERY_ROUNDS, a->num_query_rounds}, {"--security-bits", QPGPU_AGG_HAS_SECURITY_BITS, a->security_bits},
+        {"--num-challenges", QPGPU_AGG_HAS_NUM_CHALLENGES, a->num_challenges}};
+    for (const auto &k : knobs) if (has(k.bit) && k.v == 0) return cfg_fail(err, "%s must be greater than 0", k.name);
+    if (has(QPGPU_AGG_HAS_RATE_BITS) && a->rate_bits > 8)
+        return cfg_fail(err, "--rate-bits must be <= 8 (LDE memory doubles per bit: lde_size = 2^(degree_bits + rate_bits) per committed polynomial), got %llu", (ull)a->rate_bits);
+    if (has(QPGPU_AGG_HAS_CAP_HEIGHT) && a->cap_height > 8)
+        return cfg_fail(err, "--cap-height must be <= 8 (Merkle caps and recursive verifier-data allocations scale as 2^cap_height), got %llu", (ull)a->cap_height);
+    qpgpu_circuit_config base;
+    qpgpu_wormhole_circuit_config(QPGPU_LEVEL_PRIVATE_BATCH, &base);
+    const uint64_t rate = has(QPGPU_AGG_HAS_RATE_BITS) ? a->rate_bits : base.rate_bits;
+    const uint64_t quotient = has(QPGPU_AGG_HAS_MAX_QUOTIENT_DEGREE_FACTOR) ? a->max_quotient_degree_factor : base.max_quotient_degree_factor;
+    const uint64_t bits = quotient > 1 ? 64 - (uint64_t)__builtin_clzll(quotient - 1) : 0;      // log2_ceil(max(quotient, 1))
+    if (rate < bits)
+        return cfg_fail(err, "--rate-bits (%llu) must be >= ceil(log2(max_quotient_degree_factor = %llu)) = %llu; plonky2's prover cannot compute quotient chunks of degree "
+                             "higher than the FRI rate and asserts this only at proving time, after the full circuit build", (ull)rate, (ull)quotient, (ull)bits);
+    if (has(QPGPU_AGG_HAS_NUM_WIRES) && a->num_wires < 135) return cfg_fail(err, "--num-wires must be >= 135 (Poseidon gate floor), got %llu", (ull)a->num_wires);
+    if (has(QPGPU_AGG_HAS_MAX_QUOTIENT_DEGREE_FACTOR) && a->max_quotient_degree_factor < 7)
+        return cfg_fail(err, "--max-quotient-degree-factor must be >= 7 (Poseidon constraint degree), got %llu", (ull)a->max_quotient_degree_factor);
+    if (has(QPGPU_AGG_HAS_NUM_ROUTED_WIRES)) {
+        if (a->num_routed_wires < 37)
+            return cfg_fail(err, "--num-routed-wires must be >= 37 (recursion gate floor: the FRI coset-interpolation gate routes 37 wires, and narrower widths leave "
+                                 "slot-packed gates with zero operation slots), got %llu", (ull)a->num_routed_wires);
+        const uint64_t wires = has(QPGPU_AGG_HAS_NUM_WIRES) ? a->num_wires : base.num_wires;
+        if (a->num_routed_wires > wires)
+            return cfg_fail(err, "--num-routed-wires (%llu) must be <= num_wires (%llu); routed wires are a subset of the wire columns", (ull)a->num_routed_wires, (ull)wires);
+    }
+    std::string violations;
+    auto violation = [&](const char *flag) { if (!violations.empty()) violations += ", "; violations += flag; };
+    if (has(QPGPU_AGG_HAS_ZK_MODE) && a->zk_mode == QPGPU_ZK_MODE_DISABLED) violation("--zk-mode disabled");
+    if (has(QPGPU_AGG_HAS_NUM_QUERY_ROUNDS)) violation("--num-query-rounds");
+    if (has(QPGPU_AGG_HAS_SECURITY_BITS)) violation("--security-bits");
+    if (has(QPGPU_AGG_HAS_NUM_CHALLENGES)) violation("--num-challenges");
+    if (!violations.empty() && !a->allow_weakening_security)
+        return cfg_fail(err, "the following flags can weaken security: %s\npass --allow-weakening-security to acknowledge and proceed", violations.c_str());
+    return 0;
+}
+
+int qpgpu_agg_config_build(const qpgpu_agg_config_args *a, qpgpu_circuit_config *out) {
+    if (!a || !out) return -1;
+    auto has = [&](uint32_t bit) { return (a->present & bit) != 0; };
+    qpgpu_circuit_config c;
+    qpgpu_wormhole_circuit_config(QPGPU_LEVEL_PRIVATE_BATCH, &c);
+    if (has(QPGPU_AGG_HAS_ZK_MODE)) c.zero_knowledge = a->zk_mode == QPGPU_ZK_MODE_ROWBLINDING ? 1 : 0;
+    const uint64_t product = c.rate_bits * c.num_query_rounds;          // the FRI soundness product kept: never below the original
+    if (has(QPGPU_AGG_HAS_RATE_BITS)) {
+        const uint64_t v = a->rate_bits ? a->rate_bits : 1;
+        c.rate_bits = a->rate_bits;
+        c.num_query_rounds = product / v + (product % v != 0);
+    }
+    if (has(QPGPU_AGG_HAS_CAP_HEIGHT)) c.cap_height = a->cap_height;
+    if (has(QPGPU_AGG_HAS_NUM_WIRES)) c.num_wires = a->num_wires;
+    if (has(QPGPU_AGG_HAS_NUM_ROUTED_WIRES)) c.num_routed_wires = a->num_routed_wires;
+    if (has(QPGPU_AGG_HAS_MAX_QUOTIENT_DEGREE_FACTOR)) c.max_quotient_degree_factor = a->max_quotient_degree_factor;
+    if (has(QPGPU_AGG_HAS_NUM_QUERY_ROUNDS)) c.num_query_rounds = a->num_query_rounds;
+    if (has(QPGPU_AGG_HAS_SECURITY_BITS)) c.security_bits = a->security_bits;
+    if (has(QPGPU_AGG_HAS_NUM_CHALLENGES)) c.num_challenges = a->num_challenges;
+    *out = c;
+    return 0;
+}
+
 int qpgpu_pack_config_is_canonical(const uint64_t *w, size_t n, int level, char *err) {
     static const char *labels[3] = {"leaf", "private-batch", "public-batch"};
     qpgpu_circuit_config c;

@@ -30,6 +30,7 @@
 #include "../../include/qpgpu.h"
 #include "../../include/qpgpu_batch.h"
 #include "builder.hpp"
+#include "builder_config.hpp"
 #include "gadgets.hpp"
 #include "poseidon.hpp"
 #include "proof_layout.hpp"
@@ -378,15 +379,19 @@ void fri_query_end(Builder &b, const ProofTargets &p, const FriQuery &q) {
     b.connect_ext(b.reduce_ext(sx.t, coeffs), q.old_eval.t);
 }
 
-}  // namespace
-
-extern "C" {
-
-int qpgpu_wrapper_circuit_build(const uint64_t *inner_pack, size_t inner_words, const uint64_t *inner_cs_cap, size_t cap_words, unsigned num_proofs,
-                                unsigned num_routed_wires, unsigned min_degree_bits, int inner_hasher, unsigned flags, uint64_t *pack_out, size_t pack_cap_words,
-                                size_t *pack_words, uint64_t *target_map_out, size_t map_cap, size_t *map_count, uint64_t *info_out, char *err) {
-    auto fail = [&](int code, const std::string &m) { if (err) std::snprintf(err, QPGPU_BATCH_ERR_CAP, "%s", m.c_str()); return code; };
+// Both entries. user_cfg = NULL: the bare-argument entry's circuit (cb::Config's defaults = standard_recursion_config, the routed-wire
+// count and zero knowledge from the arguments), info_words = QPGPU_WRAPPER_CIRCUIT_INFO_WORDS. user_cfg: the caller's CircuitConfig through
+// the policy the leaf entry shares (builder_config.hpp), info_words = QPGPU_WRAPPER_CIRCUIT_INFO_WORDS_CFG.
+int wrapper_circuit_build_impl(const uint64_t *inner_pack, size_t inner_words, const uint64_t *inner_cs_cap, size_t cap_words, unsigned num_proofs,
+                               unsigned num_routed_wires, unsigned min_degree_bits, int inner_hasher, unsigned flags, const qpgpu_circuit_config *user_cfg, size_t info_words,
+                               uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, size_t map_cap, size_t *map_count, uint64_t *info_out,
+                               char *err, size_t err_cap) {
+    auto fail = [&](int code, const std::string &m) { if (err) std::snprintf(err, err_cap, "%s", m.c_str()); return code; };
     if (err) err[0] = 0;
+    if (user_cfg && num_routed_wires != 0)
+        return fail(QPGPU_EINVAL, "wrapper_circuit_build: num_routed_wires must be 0 when a circuit config is given (the config carries num_routed_wires)");
+    if (user_cfg && (flags & QPGPU_WRAPPER_ZERO_KNOWLEDGE))
+        return fail(QPGPU_EINVAL, "wrapper_circuit_build: QPGPU_WRAPPER_ZERO_KNOWLEDGE must be clear when a circuit config is given (the config carries zero_knowledge)");
     if (!inner_pack || !inner_cs_cap || !pack_words || num_proofs == 0 || num_proofs > 64) return fail(QPGPU_EINVAL, "wrapper_circuit_build: null argument or proof count outside 1..64");
     if (flags & ~(QPGPU_WRAPPER_TRANSCRIPT | QPGPU_WRAPPER_PRIVATE_BATCH | QPGPU_WRAPPER_PUBLIC_BATCH | QPGPU_WRAPPER_VERIFY | QPGPU_WRAPPER_ZERO_KNOWLEDGE)) return fail(QPGPU_EINVAL, "wrapper_circuit_build: unknown flag");
     const bool transcript = (flags & QPGPU_WRAPPER_TRANSCRIPT) != 0, private_batch = (flags & QPGPU_WRAPPER_PRIVATE_BATCH) != 0, public_batch = (flags & QPGPU_WRAPPER_PUBLIC_BATCH) != 0;
@@ -409,11 +414,26 @@ int qpgpu_wrapper_circuit_build(const uint64_t *inner_pack, size_t inner_words, 
     const size_t total = (size_t)num_proofs * (T + 4 + Q);
     try {
         cb::Config cfg;
-        cfg.num_routed_wires = num_routed_wires ? num_routed_wires : 80;
+        if (user_cfg) {
+            const int rc = cb::config_from_circuit_config("wrapper_circuit_build", QPGPU_LEVEL_PUBLIC_BATCH, user_cfg, cfg, err, err_cap);
+            if (rc != QPGPU_OK) return rc;
+            cfg.mds_arithmetic_fallback = true;         // Poseidon::mds_layer_circuit's own choice at fewer than 48 routed wires
+        } else {
+            cfg.num_routed_wires = num_routed_wires ? num_routed_wires : 80;
+            cfg.zero_knowledge = (flags & QPGPU_WRAPPER_ZERO_KNOWLEDGE) != 0;
+        }
         cfg.min_degree_bits = min_degree_bits;
         cfg.inner_hasher = inner_hasher;
-        cfg.zero_knowledge = (flags & QPGPU_WRAPPER_ZERO_KNOWLEDGE) != 0;
         Builder b(cfg);
+        // RandomAccessGate::new_from_config on the inner caps: num_routed_wires / (2 + 2^cap_height) copies, none of which is no gate
+        if (inner.cap_height > 0 && inner.cap_height <= 6 && 2 + (1u << inner.cap_height) > cfg.num_routed_wires)
+            return fail(QPGPU_EINVAL, "wrapper_circuit_build: the inner circuit's cap_height " + std::to_string(inner.cap_height) + " needs " + std::to_string(2 + (1u << inner.cap_height)) +
+                                      " routed wires (a RandomAccessGate copy over the 2^cap_height cap entries: 2 + 2^cap_height); the circuit config has " +
+                                      std::to_string(cfg.num_routed_wires));
+        // a limit of the proof system itself, refused by name: circuit packs, verifiers and the quotient kernels carry RandomAccessGates of up to 2^5 entries
+        if (inner.cap_height > 5)
+            return fail(QPGPU_EINVAL, "wrapper_circuit_build: the inner circuit's cap_height " + std::to_string(inner.cap_height) + " needs a RandomAccessGate over 2^" +
+                                      std::to_string(inner.cap_height) + " cap entries; this prover carries RandomAccessGates of up to 2^5 entries (inner cap_height 0..5)");
         struct Bind { explicit Bind(Builder *p) { cbx::g_b = p; } ~Bind() { cbx::g_b = nullptr; } } bind(&b);     // XT's operations build into `b` while it lives
         const unsigned L = (unsigned)(inner.degree_bits + inner.rate_bits), cap_h = (unsigned)inner.cap_height;
         // verifier data of the inner circuit: constants of this one (builder.constant_merkle_cap)
@@ -513,13 +533,36 @@ int qpgpu_wrapper_circuit_build(const uint64_t *inner_pack, size_t inner_words, 
         if (info_out) {
             const std::map<uint64_t, size_t> gc = b.gate_counts();
             auto cnt = [&](uint64_t t) { auto it = gc.find(t); return it == gc.end() ? (uint64_t)0 : (uint64_t)it->second; };
-            const uint64_t info[QPGPU_WRAPPER_CIRCUIT_INFO_WORDS] = {pack.degree_bits, b.rows_before_padding(), (uint64_t)T, (uint64_t)Q, cnt(GATE_POSEIDON), cnt(GATE_RANDOM_ACCESS),
-                                                                    cnt(GATE_BASE_SUM), cnt(GATE_ARITHMETIC), cnt(GATE_CONSTANT), pack.num_public_inputs, (uint64_t)rows_hash, (uint64_t)b.blinding_rows()};
-            std::memcpy(info_out, info, sizeof info);
+            const uint64_t info[QPGPU_WRAPPER_CIRCUIT_INFO_WORDS_CFG] = {pack.degree_bits, b.rows_before_padding(), (uint64_t)T, (uint64_t)Q, cnt(GATE_POSEIDON), cnt(GATE_RANDOM_ACCESS),
+                                                                        cnt(GATE_BASE_SUM), cnt(GATE_ARITHMETIC), cnt(GATE_CONSTANT), pack.num_public_inputs, (uint64_t)rows_hash, (uint64_t)b.blinding_rows(),
+                                                                        cnt(GATE_POSEIDON_MDS), cnt(GATE_ARITHMETIC_EXT), cnt(GATE_COSET_INTERPOLATION), cnt(GATE_REDUCING) + cnt(GATE_REDUCING_EXT)};
+            std::memcpy(info_out, info, info_words * 8);
         }
     } catch (const std::exception &e) {
         return fail(QPGPU_EINVAL, std::string("wrapper_circuit_build: ") + e.what());
     }
     return QPGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qpgpu_wrapper_circuit_build_cfg(const uint64_t *inner_pack, size_t inner_words, const uint64_t *inner_cs_cap, size_t cap_words, unsigned num_proofs,
+                                    unsigned num_routed_wires, unsigned min_degree_bits, int inner_hasher, unsigned flags, const qpgpu_circuit_config *cfg,
+                                    uint64_t *pack_out, size_t pack_cap_words, size_t *pack_words, uint64_t *target_map_out, size_t map_cap, size_t *map_count,
+                                    uint64_t *info_out, char *err) {
+    if (!cfg)      // the bare-argument entry, word for word (and its 12 info words, the first 12 of this entry's)
+        return wrapper_circuit_build_impl(inner_pack, inner_words, inner_cs_cap, cap_words, num_proofs, num_routed_wires, min_degree_bits, inner_hasher, flags, nullptr,
+                                          QPGPU_WRAPPER_CIRCUIT_INFO_WORDS, pack_out, pack_cap_words, pack_words, target_map_out, map_cap, map_count, info_out, err, QPGPU_BATCH_ERR_CAP);
+    return wrapper_circuit_build_impl(inner_pack, inner_words, inner_cs_cap, cap_words, num_proofs, num_routed_wires, min_degree_bits, inner_hasher, flags, cfg,
+                                      QPGPU_WRAPPER_CIRCUIT_INFO_WORDS_CFG, pack_out, pack_cap_words, pack_words, target_map_out, map_cap, map_count, info_out, err, QPGPU_CONFIG_ERR_CAP);
+}
+
+int qpgpu_wrapper_circuit_build(const uint64_t *inner_pack, size_t inner_words, const uint64_t *inner_cs_cap, size_t cap_words, unsigned num_proofs,
+                                unsigned num_routed_wires, unsigned min_degree_bits, int inner_hasher, unsigned flags, uint64_t *pack_out, size_t pack_cap_words,
+                                size_t *pack_words, uint64_t *target_map_out, size_t map_cap, size_t *map_count, uint64_t *info_out, char *err) {
+    return qpgpu_wrapper_circuit_build_cfg(inner_pack, inner_words, inner_cs_cap, cap_words, num_proofs, num_routed_wires, min_degree_bits, inner_hasher, flags, nullptr,
+                                           pack_out, pack_cap_words, pack_words, target_map_out, map_cap, map_count, info_out, err);
 }
 }  // extern "C"

@@ -8,10 +8,12 @@ import ctypes
 
 import numpy as np
 
-from .binding import QpGpuError, load_library
+from .binding import CONFIG_ERR_CAP, QpGpuError, as_circuit_config, load_library
 
 INFO_FIELDS = ("degree_bits", "rows_before_padding", "targets_per_proof", "query_rounds", "rows_poseidon", "rows_random_access", "rows_base_sum",
                "rows_arithmetic", "rows_constant", "public_inputs", "rows_verification", "rows_blinding")
+# the further words of qpgpu_wrapper_circuit_build_cfg's info (QPGPU_WRAPPER_CIRCUIT_INFO_WORDS_CFG), present when a config is given
+INFO_FIELDS_CFG = INFO_FIELDS + ("rows_poseidon_mds", "rows_arithmetic_ext", "rows_coset_interpolation", "rows_reducing")
 NO_CELL = 0xFFFFFFFFFFFFFFFF
 
 
@@ -22,6 +24,8 @@ def _lib():
         vp, sz, cp = c.c_void_p, c.c_size_t, c.c_char_p
         L.qpgpu_wrapper_circuit_build.restype = c.c_int
         L.qpgpu_wrapper_circuit_build.argtypes = [vp, sz, vp, sz, c.c_uint, c.c_uint, c.c_uint, c.c_int, c.c_uint, vp, sz, c.POINTER(sz), vp, sz, c.POINTER(sz), vp, cp]
+        L.qpgpu_wrapper_circuit_build_cfg.restype = c.c_int
+        L.qpgpu_wrapper_circuit_build_cfg.argtypes = [vp, sz, vp, sz, c.c_uint, c.c_uint, c.c_uint, c.c_int, c.c_uint, vp, vp, sz, c.POINTER(sz), vp, sz, c.POINTER(sz), vp, cp]
         L.qpgpu_batch_fill_proof_targets.argtypes = [vp, sz, vp, vp, sz, sz, vp, sz, sz, cp, vp, vp, sz, c.POINTER(sz), cp]
         L.qpgpu_proof_target_count.argtypes = [vp, sz]; L.qpgpu_proof_target_count.restype = sz
         L.qpgpu_verifier_query_indices.restype = c.c_int
@@ -40,7 +44,8 @@ class WrapperCircuit:
 
     FLAGS = {None: 0, "private_batch": 2, "public_batch": 4}          # QPGPU_WRAPPER_PRIVATE_BATCH / _PUBLIC_BATCH
 
-    def __init__(self, inner_pack, verifier, num_proofs, num_routed_wires=80, min_degree_bits=0, inner_hasher=0, transcript=True, logic=None, verify=False, zero_knowledge=False):
+    def __init__(self, inner_pack, verifier, num_proofs, num_routed_wires=80, min_degree_bits=0, inner_hasher=0, transcript=True, logic=None, verify=False, zero_knowledge=False,
+                 config=None):
         """transcript=True (QPGPU_WRAPPER_TRANSCRIPT): the inner proofs' Fiat-Shamir transcripts are replayed in-circuit, the query
         indices are derived there and the proof-of-work response is range-checked; False: the query indices are witness inputs.
         logic: None (inner public inputs forwarded), "private_batch" (build_private_batch_constraints over leaf proofs) or
@@ -49,8 +54,18 @@ class WrapperCircuit:
         polynomial at zeta, FRI consistency) — the wrapper then enforces everything the host verifier checks on an inner proof.
         zero_knowledge=True (QPGPU_WRAPPER_ZERO_KNOWLEDGE): the circuit is built with CircuitBuilder::blind's rows and proven with
         salted Merkle leaves; commit draws the blinding rows' random wires (blinding_seed: 32 bytes for reproducible tests, None:
-        operating-system entropy)."""
+        operating-system entropy).
+        config (qpgpu_wrapper_circuit_build_cfg; PrivateBatchCircuit::new(config, ..) / PublicBatchCircuit::new(config, ..)): None — the
+        circuit of the arguments above, as ever —, the name of a canonical config ("private_batch", "public_batch"), a
+        binding.CircuitConfig or any object / mapping with its fields. The config then carries the routed-wire count and zero
+        knowledge: num_routed_wires and zero_knowledge must be left at their defaults. A config the reference's
+        validate_circuit_config refuses, or one the native builder does not model, raises QpGpuError with the reason."""
         L = _lib()
+        self.config = as_circuit_config(config)
+        if self.config is not None:
+            if num_routed_wires != 80 or zero_knowledge:
+                raise QpGpuError(-1, "WrapperCircuit: with config= the config carries num_routed_wires and zero_knowledge; leave both arguments at their defaults")
+            num_routed_wires, zero_knowledge = 0, bool(self.config.zero_knowledge)
         self.logic, self.verify, self.zero_knowledge = logic, verify, zero_knowledge
         self.inner_pack = np.ascontiguousarray(inner_pack, dtype=np.uint64)
         self.verifier, self.num_proofs, self.transcript = verifier, num_proofs, transcript
@@ -59,20 +74,25 @@ class WrapperCircuit:
         if L.qpgpu_verifier_constants_sigmas_cap(verifier.h, cap.ctypes.data, cap.size) != 0:
             raise QpGpuError(-1, "verifier has no constants/sigmas cap")
         n, m = ctypes.c_size_t(), ctypes.c_size_t()
-        err = ctypes.create_string_buffer(200)
+        err = ctypes.create_string_buffer(CONFIG_ERR_CAP)
         args = (self.inner_pack.ctypes.data, self.inner_pack.size, cap.ctypes.data, cap.size, num_proofs, num_routed_wires, min_degree_bits, inner_hasher,
-                (1 if transcript else 0) | self.FLAGS[logic] | (8 if verify else 0) | (16 if zero_knowledge else 0))
-        rc = L.qpgpu_wrapper_circuit_build(*args, None, 0, ctypes.byref(n), None, 0, ctypes.byref(m), None, err)
+                (1 if transcript else 0) | self.FLAGS[logic] | (8 if verify else 0) | (16 if zero_knowledge and self.config is None else 0))
+        if self.config is None:
+            build, fields = L.qpgpu_wrapper_circuit_build, INFO_FIELDS
+        else:
+            args, fields = args + (ctypes.byref(self.config),), INFO_FIELDS_CFG
+            build = L.qpgpu_wrapper_circuit_build_cfg
+        rc = build(*args, None, 0, ctypes.byref(n), None, 0, ctypes.byref(m), None, err)
         if rc != 0:
             raise QpGpuError(rc, err.value.decode())
         self.pack = np.empty(n.value, dtype=np.uint64)
         self.target_map = np.empty(m.value, dtype=np.uint64)
-        info = np.zeros(len(INFO_FIELDS), dtype=np.uint64)
-        rc = L.qpgpu_wrapper_circuit_build(*args, self.pack.ctypes.data, self.pack.size, ctypes.byref(n), self.target_map.ctypes.data, self.target_map.size,
-                                           ctypes.byref(m), info.ctypes.data, err)
+        info = np.zeros(len(fields), dtype=np.uint64)
+        rc = build(*args, self.pack.ctypes.data, self.pack.size, ctypes.byref(n), self.target_map.ctypes.data, self.target_map.size, ctypes.byref(m), info.ctypes.data, err)
         if rc != 0:
             raise QpGpuError(rc, err.value.decode())
-        self.info = {k: int(v) for k, v in zip(INFO_FIELDS, info) if k != "_"}
+        self.info = {k: int(v) for k, v in zip(fields, info) if k != "_"}
+        self.num_wires = int(self.pack[2])                      # header word 2 (csrc/circuit.hpp): the trace has this many columns
         self.T, self.Q = self.info["targets_per_proof"], self.info["query_rounds"]
         self.blinding_cells = self.target_map[num_proofs * (self.T + 4 + self.Q):].copy()       # cells, not logical ids
         self.target_map = self.target_map[:num_proofs * (self.T + 4 + self.Q)]
@@ -177,11 +197,12 @@ class PrivateBatchProver:
     the device (Merkle leaves salted)."""
 
     def __init__(self, pkg, gpu, leaf_circuit, num_leaf_proofs, verify=True, leaf_prover=None, zero_knowledge=True, num_routed_wires=60,
-                 verify_on_device=False):
+                 verify_on_device=False, config=None):
         """zero_knowledge / num_routed_wires: wormhole_private_batch_circuit_config (common/src/circuit.rs:396-402) — the one
         zero-knowledge layer of the stack, 60 routed wires. verify_on_device: commit runs the query rounds of the leaf proofs'
         verification on `gpu` (Verifier.verify_many(gpu=...)); "full": the head of verification too (device_head=True); same
-        verdicts and messages as the host verifier."""
+        verdicts and messages as the host verifier. config: PrivateBatchProver::new(agg_circuit_config, ..) — None is the circuit of
+        zero_knowledge / num_routed_wires above; otherwise WrapperCircuit's config, which then carries both."""
         from . import aggregation, leaf as leaf_mod
         self.pkg, self.gpu, self.N, self.A = pkg, gpu, num_leaf_proofs, aggregation
         self.verify_gpu = gpu if verify_on_device else None
@@ -189,11 +210,14 @@ class PrivateBatchProver:
         self.own_leaf_prover = leaf_prover is None
         self.leaf_prover = leaf_prover or leaf_mod.LeafProver(pkg, gpu, leaf_circuit)
         self.leaf_verifier = pkg.Verifier(leaf_circuit.pack, circuit=self.leaf_prover.circ)
-        self.circuit = WrapperCircuit(leaf_circuit.pack, self.leaf_verifier, num_leaf_proofs, num_routed_wires=num_routed_wires, logic="private_batch", verify=verify,
-                                      zero_knowledge=zero_knowledge)
+        if config is None:
+            self.circuit = WrapperCircuit(leaf_circuit.pack, self.leaf_verifier, num_leaf_proofs, num_routed_wires=num_routed_wires, logic="private_batch", verify=verify,
+                                          zero_knowledge=zero_knowledge)
+        else:
+            self.circuit = WrapperCircuit(leaf_circuit.pack, self.leaf_verifier, num_leaf_proofs, logic="private_batch", verify=verify, config=config)
         self.circ = pkg.Circuit(gpu, self.circuit.pack)
         self.verifier = pkg.Verifier(self.circuit.pack, circuit=self.circ)
-        self.d_wires = gpu.alloc(8 * (135 << self.circuit.info["degree_bits"]))
+        self.d_wires = gpu.alloc(8 * (self.circuit.num_wires << self.circuit.info["degree_bits"]))
         # verify_dummy_leaf_template: the sentinel, then the cryptographic check
         self.dummy_leaf_proof = self.leaf_prover.prove(leaf_mod.dummy_circuit_inputs())[0]
         dp = aggregation.proof_public_inputs(self.dummy_leaf_proof, 21)
@@ -261,19 +285,20 @@ class PublicBatchProver:
     admission checks on the supplied private-batch proofs, order-preserving padding with the all-dummy private-batch template
     (no shuffle), the aggregator address as a witness input that becomes the first four public inputs."""
 
-    def __init__(self, pkg, gpu, private_prover, num_private_batch_proofs, verify=True, verify_on_device=False):
+    def __init__(self, pkg, gpu, private_prover, num_private_batch_proofs, verify=True, verify_on_device=False, config=None):
         """verify_on_device: commit runs the query rounds of the private-batch proofs' verification on `gpu`; "full": the head
-        of verification too (Verifier.verify_many(device_head=True))."""
+        of verification too (Verifier.verify_many(device_head=True)). config: PublicBatchProver::new(public_batch_circuit_config, ..)
+        — None is standard_recursion_config as ever; otherwise WrapperCircuit's config."""
         from . import aggregation
         self.pkg, self.gpu, self.M, self.N, self.A = pkg, gpu, num_private_batch_proofs, private_prover.N, aggregation
         self.verify_gpu = gpu if verify_on_device else None
         self.verify_device_head = verify_on_device == "full"
         self.private_verifier = private_prover.verifier
         self.inner_len = aggregation.private_batch_pi_len(self.N)
-        self.circuit = WrapperCircuit(private_prover.circuit.pack, self.private_verifier, self.M, logic="public_batch", verify=verify)
+        self.circuit = WrapperCircuit(private_prover.circuit.pack, self.private_verifier, self.M, logic="public_batch", verify=verify, config=config)
         self.circ = pkg.Circuit(gpu, self.circuit.pack)
         self.verifier = pkg.Verifier(self.circuit.pack, circuit=self.circ)
-        self.d_wires = gpu.alloc(8 * (135 << self.circuit.info["degree_bits"]))
+        self.d_wires = gpu.alloc(8 * (self.circuit.num_wires << self.circuit.info["degree_bits"]))
         # verify_dummy_private_batch_template: the sentinel, then the cryptographic check
         self.dummy_private_batch_proof = private_prover.prove_dummy_template()
         dp = aggregation.proof_public_inputs(self.dummy_private_batch_proof, self.inner_len)
@@ -348,8 +373,11 @@ class AttestingTree:
     of one tree must then be what the reference's layers accept (real spends of ONE block, dummies elsewhere). One lockstep batch
     per level and rank."""
 
-    def __init__(self, pkg, gpu, per_batch=8, batches=8, leaf_min_degree_bits=0, rank=0, world=1, batch_logic=True, aggregator_address=bytes(32), seed=1, verify=True, zero_knowledge=False):
-        """rank / world: with several ranks (one per GPU) a rank proves the leaves and the first-level wrapper of batches
+    def __init__(self, pkg, gpu, per_batch=8, batches=8, leaf_min_degree_bits=0, rank=0, world=1, batch_logic=True, aggregator_address=bytes(32), seed=1, verify=True, zero_knowledge=False,
+                 private_config=None, public_config=None):
+        """private_config / public_config: the first / second level under a caller's CircuitConfig (WrapperCircuit's config; None: the
+        circuits of zero_knowledge above, as ever).
+        rank / world: with several ranks (one per GPU) a rank proves the leaves and the first-level wrapper of batches
         b = rank, rank + world, ..; the first-level proofs travel to rank 0, which proves the second level."""
         self.pkg, self.gpu, self.per_batch, self.batches = pkg, gpu, per_batch, batches
         self.rank, self.world = rank, world
@@ -363,14 +391,17 @@ class AttestingTree:
         self.seed = seed
         # zero_knowledge: the first level as the reference configures its private layer (blinding rows, salted leaves, 60 routed wires)
         self.zero_knowledge = zero_knowledge
-        self.w1 = WrapperCircuit(self.leaf.pack, self.leaf_ver, per_batch, num_routed_wires=60 if zero_knowledge else 80, logic="private_batch" if batch_logic else None,
-                                 verify=verify, zero_knowledge=zero_knowledge)
+        if private_config is None:
+            self.w1 = WrapperCircuit(self.leaf.pack, self.leaf_ver, per_batch, num_routed_wires=60 if zero_knowledge else 80, logic="private_batch" if batch_logic else None,
+                                     verify=verify, zero_knowledge=zero_knowledge)
+        else:
+            self.w1 = WrapperCircuit(self.leaf.pack, self.leaf_ver, per_batch, logic="private_batch" if batch_logic else None, verify=verify, config=private_config)
         self.w1_circ = pkg.Circuit(gpu, self.w1.pack, max_batch=max(1, len(self.my_batches)))
         self.w1_ver = pkg.Verifier(self.w1.pack, circuit=self.w1_circ)
-        self.w2 = WrapperCircuit(self.w1.pack, self.w1_ver, batches, logic="public_batch" if batch_logic else None, verify=verify)
+        self.w2 = WrapperCircuit(self.w1.pack, self.w1_ver, batches, logic="public_batch" if batch_logic else None, verify=verify, config=public_config)
         self.w2_circ = pkg.Circuit(gpu, self.w2.pack)
         self.w2_ver = pkg.Verifier(self.w2.pack, circuit=self.w2_circ)
-        self.words = [135 << c.info["degree_bits"] for c in (self.leaf, self.w1, self.w2)]
+        self.words = [int(c.pack[2]) << c.info["degree_bits"] for c in (self.leaf, self.w1, self.w2)]      # header word 2: num_wires
         self.d_wires = gpu.alloc(8 * max(n_leaves * self.words[0], max(1, len(self.my_batches)) * self.words[1], self.words[2]))
         self.times = {}
 
