@@ -203,6 +203,49 @@ int qpgpu_circuit_set_blinding_seed(qpgpu_circuit *c, uint64_t seed);
  * fails to verify (reference tests catch the panic, wormhole/tests/src/circuit/nullifier_tests.rs:53-58). Costs one
  * extra pass over the trace and one stream sync. */
 int qpgpu_circuit_set_witness_check(qpgpu_circuit *c, int on);
+/* Explain an unsatisfied witness: WHICH gate constraints fail on which rows, and which routed cells break a copy constraint
+ * (upstream plonky2 names the partition and both values for a broken copy, its debug assertions name the gate). wires: one
+ * proof's [num_wires][2^degree_bits] matrix as qpgpu_prove (wires_on_device = 0) or qpgpu_prove_dev (1) takes it; public_inputs
+ * feed the PublicInputGate hash as in qpgpu_prove. A satisfied witness returns QPGPU_OK with *count == 0 and both totals 0; an
+ * unsatisfied one also returns QPGPU_OK, with findings. QPGPU_EBUFSIZE is never returned: *count findings are written
+ * (<= cap) and the two totals say how much there was. Usable whether or not the witness check is switched on; needs no
+ * transcript; changes nothing a later qpgpu_prove* reads. To explain one proof of a failed batch pass that proof's wires.
+ *   GATE findings come first, in ascending (row, constraint) order. *failing_rows counts every row with a non-zero filtered
+ *   constraint; the first max_rows (1..1024; 0 is QPGPU_EINVAL) of them are expanded, one finding per non-zero constraint:
+ *   gate = the gate whose filter is non-zero on the row (index into the pack's gate list), constraint = index within that gate,
+ *   value = filter * constraint, the term that enters the quotient, canonical.
+ *   COPY findings follow, in ascending (row, wire) order: a routed cell whose value differs from the value at the source cell of
+ *   its copy class (wire_b, row_b: the cell stage s1's copy pass fills the class from; a wrong source cell is therefore reported
+ *   once per other member). *copy_mismatches counts all of them; at most cap - (GATE findings written) are written. The
+ *   circuit's witness plan is made here if it has not been.
+ * The values come from the gate kernels that judge the witness in the witness check, run with other weights (csrc/explain_api.cpp);
+ * rows are found under a fixed weight table, which a witness not built against it escapes with probability < 2^-56 per
+ * challenge column. flags: 0. failing_rows and copy_mismatches may be NULL; out may be NULL when cap is 0.
+ * SECRETS: findings are functions of witness values (a COPY finding carries two cells verbatim): treat `out` like the witness.
+ * Every device and pinned buffer the call allocates is listed in the residue registry (region circuit-workspace), overwritten
+ * and released before the call returns, on every exit path; a host witness is uploaded into such a buffer.
+ * NOT covered: stage plans (qpgpu_stage_plan), the proving pool and sharded oracles have no such entry; load the pack with
+ * qpgpu_circuit_load and pass the witness here. */
+enum { QPGPU_FINDING_GATE = 1, QPGPU_FINDING_COPY = 2 };
+typedef struct qpgpu_witness_finding {
+    uint32_t kind, gate;          /* GATE: index into the pack's gate list */
+    uint32_t constraint;          /* GATE: index within the gate, 0 .. num_constraints-1 */
+    uint32_t wire, wire_b;        /* COPY: this cell, and the source cell of its copy class */
+    uint32_t reserved;
+    uint64_t row, row_b;
+    uint64_t value, value_b;      /* GATE: value = filter * constraint, canonical: the term that enters the quotient.
+                                     COPY: the two cells' values, canonical */
+} qpgpu_witness_finding;
+int qpgpu_circuit_explain_witness(qpgpu_circuit *c, const uint64_t *wires, int wires_on_device,
+                                  const uint64_t *public_inputs, uint32_t max_rows, unsigned flags,
+                                  qpgpu_witness_finding *out, size_t cap, size_t *count,
+                                  uint64_t *failing_rows, uint64_t *copy_mismatches);
+/* host only: one line of text for a finding; gates are named as tools/pack_dump.py names them. pack_words: the circuit pack, or
+ * its header form (qpgpu_stage_plan_create). At most cap - 1 characters and a NUL are written: QPGPU_OK if the line fitted,
+ * QPGPU_EBUFSIZE if it was cut (buf holds the cut line). A NULL argument, cap 0, a pack that does not parse, an unknown kind, or a
+ * gate, constraint, wire or row outside the pack is QPGPU_EINVAL with buf[0] = 0 (where there is a buf): nothing is read past the pack. */
+int qpgpu_witness_finding_format(const uint64_t *pack_words, size_t n_words, const qpgpu_witness_finding *f,
+                                 char *buf, size_t cap);
 /* Quotient stage: by default a circuit whose gates, the hash gates aside, are Constant, PublicInput, Arithmetic and BaseSum<2>
  * on routed wires (the leaf circuit) gets its permutation terms and those gates from one kernel; every other circuit, and any
  * circuit after on = 0, from the two kernels that pass over the wires once each. Same proof bytes either way. The default at

@@ -48,6 +48,13 @@ use plonky2::plonk::proof::ProofWithPublicInputs;
 #[repr(C)] pub struct QpgpuFriBatch { pub point: [u64; 2], pub num_ranges: u32, pub ranges: [QpgpuFriRange; 8] }
 #[repr(C)] pub struct QpgpuFriParams { pub rate_bits: u32, pub cap_height: u32, pub proof_of_work_bits: u32, pub num_query_rounds: u32,
                                        pub num_reduction_rounds: u32, pub reduction_arity_bits: [u32; 16] }
+// kind 1 (gate): constraint `constraint` of gate `gate` is `value` on `row`; kind 2 (copy): cell (row, wire) holds `value`, the source
+// cell of its copy class (row_b, wire_b) holds `value_b`
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct QpgpuWitnessFinding { pub kind: u32, pub gate: u32, pub constraint: u32, pub wire: u32, pub wire_b: u32, pub reserved: u32,
+                                 pub row: u64, pub row_b: u64, pub value: u64, pub value_b: u64 }
+pub const QPGPU_FINDING_GATE: u32 = 1;
+pub const QPGPU_FINDING_COPY: u32 = 2;
 pub const QPGPU_STAGE_ERR_CAP: usize = 256;
 
 pub const QPGPU_OK: i32 = 0;
@@ -68,6 +75,14 @@ extern "C" {
     pub fn qpgpu_circuit_free(c: *mut QpgpuCircuit);
     pub fn qpgpu_circuit_scrub(c: *mut QpgpuCircuit) -> i32;
     pub fn qpgpu_circuit_set_witness_check(c: *mut QpgpuCircuit, on: i32) -> i32;
+    // After QPGPU_EUNSAT: which gate, which constraints, which cells. Always QPGPU_OK when it could look;
+    // `count` findings written (<= cap), GATE findings of the first max_rows (1..=1024) failing rows first, then COPY findings.
+    // Findings carry witness values: zeroize `out` like the witness.
+    pub fn qpgpu_circuit_explain_witness(c: *mut QpgpuCircuit, wires: *const u64, wires_on_device: i32, public_inputs: *const u64,
+                                         max_rows: u32, flags: u32, out: *mut QpgpuWitnessFinding, cap: usize, count: *mut usize,
+                                         failing_rows: *mut u64, copy_mismatches: *mut u64) -> i32;
+    // host only; QPGPU_EBUFSIZE (-5) = the line was cut at cap
+    pub fn qpgpu_witness_finding_format(pack: *const u64, n_words: usize, f: *const QpgpuWitnessFinding, buf: *mut c_char, cap: usize) -> i32;
     pub fn qpgpu_circuit_quotient_pair_info(c: *const QpgpuCircuit, enabled: *mut i32, selected: *mut i32) -> i32;   // introspection
     pub fn qpgpu_proof_size(c: *const QpgpuCircuit) -> usize;
     pub fn qpgpu_prove(c: *mut QpgpuCircuit, wires: *const u64, public_inputs: *const u64, out: *mut u8, out_cap: usize, out_len: *mut usize) -> i32;

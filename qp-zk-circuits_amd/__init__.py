@@ -9,6 +9,7 @@ imported through `__graft_entry__.load_package()` under the module name `qp_zk_c
 """
 from .binding import poseidon_constants, synth_circuit, Circuit, QpGpu, QpGpuError, lib_path, load_library, P, MULT_GEN  # noqa: F401
 from .binding import StagePlan, stage_header_words  # noqa: F401
+from .binding import WitnessFinding, format_finding, FINDING_GATE, FINDING_COPY  # noqa: F401
 from .binding import FriSession, fri_grind  # noqa: F401
 from .binding import FriVerifier  # noqa: F401
 from .binding import fri_prove_batch, fri_grind_batch  # noqa: F401

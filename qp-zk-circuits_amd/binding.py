@@ -1,5 +1,6 @@
 """ctypes binding of include/qpgpu.h. Thin: argument marshalling and error mapping only."""
 import ctypes
+import dataclasses
 import os
 
 import numpy as np
@@ -114,6 +115,9 @@ def load_library():
         "qpgpu_proof_size": (c.c_size_t, [vp]),
         "qpgpu_circuit_set_blinding_seed": (c.c_int, [vp, c.c_uint64]),
         "qpgpu_circuit_set_witness_check": (c.c_int, [vp, c.c_int]),
+        "qpgpu_circuit_explain_witness": (c.c_int, [vp, u64p, c.c_int, u64p, c.c_uint32, c.c_uint, vp, c.c_size_t, c.POINTER(c.c_size_t),
+                                                    c.POINTER(c.c_uint64), c.POINTER(c.c_uint64)]),
+        "qpgpu_witness_finding_format": (c.c_int, [u64p, c.c_size_t, vp, c.c_char_p, c.c_size_t]),
         "qpgpu_circuit_set_quotient_fused": (c.c_int, [vp, c.c_int]),
         "qpgpu_circuit_quotient_info": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_int)]),
         "qpgpu_circuit_quotient_pair_info": (c.c_int, [vp, c.POINTER(c.c_int), c.POINTER(c.c_int)]),
@@ -573,6 +577,47 @@ class DeviceBuffer:
             self.ptr = None
 
 
+FINDING_GATE, FINDING_COPY = 1, 2
+
+
+class _WitnessFinding(ctypes.Structure):
+    """qpgpu_witness_finding of include/qpgpu.h (56 bytes)."""
+    _fields_ = [("kind", ctypes.c_uint32), ("gate", ctypes.c_uint32), ("constraint", ctypes.c_uint32), ("wire", ctypes.c_uint32),
+                ("wire_b", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("row", ctypes.c_uint64), ("row_b", ctypes.c_uint64),
+                ("value", ctypes.c_uint64), ("value_b", ctypes.c_uint64)]
+
+
+@dataclasses.dataclass(frozen=True)
+class WitnessFinding:
+    """One finding of Circuit.explain_witness. kind FINDING_GATE: constraint `constraint` of gate `gate` (index into the pack's gate
+    list) is `value` (filter * constraint) on `row`. kind FINDING_COPY: the routed cell (row, wire) holds `value`, the source cell
+    of its copy class (row_b, wire_b) holds `value_b`. Carries functions of witness values: treat it like the witness."""
+    kind: int
+    gate: int = 0
+    constraint: int = 0
+    wire: int = 0
+    wire_b: int = 0
+    row: int = 0
+    row_b: int = 0
+    value: int = 0
+    value_b: int = 0
+
+    def _c(self):
+        return _WitnessFinding(self.kind, self.gate, self.constraint, self.wire, self.wire_b, 0, self.row, self.row_b, self.value, self.value_b)
+
+
+def format_finding(pack, f, cap=256):
+    """qpgpu_witness_finding_format: one line of text for a WitnessFinding, gates named as tools/pack_dump.py names them. Host only.
+    Raises QpGpuError(-1) for a finding that does not fit the pack, (-5) when the line does not fit into cap bytes."""
+    pw = np.ascontiguousarray(pack, dtype=np.uint64)
+    buf = ctypes.create_string_buffer(cap)
+    cf = f._c()
+    rc = load_library().qpgpu_witness_finding_format(pw.ctypes.data, pw.size, ctypes.byref(cf), buf, cap)
+    if rc:
+        raise QpGpuError(rc, "witness_finding_format: " + ("the line does not fit: " + buf.value.decode() if rc == -5 else "the finding does not fit the pack"))
+    return buf.value.decode()
+
+
 class Circuit:
     """A circuit pack loaded on the GPU (constants/sigmas committed, workspace allocated)."""
 
@@ -614,6 +659,21 @@ class Circuit:
     def set_witness_check(self, on=True):
         """Make prove() return QPGPU_EUNSAT (-4) for a witness that violates a gate or copy constraint."""
         self.gpu._check(self.gpu.lib.qpgpu_circuit_set_witness_check(self.h, 1 if on else 0))
+
+    def explain_witness(self, wires, public_inputs, max_rows=8, cap=4096):
+        """qpgpu_circuit_explain_witness: (findings, failing_rows, copy_mismatches). findings: WitnessFinding list, the GATE findings
+        of the first max_rows failing rows in (row, constraint) order, then COPY findings in (row, wire) order, `cap` at most;
+        the two totals count everything there was. wires: a host array [num_wires, n], or a DeviceBuffer / device pointer."""
+        on_device = not isinstance(wires, np.ndarray)
+        if not on_device:
+            wires = np.ascontiguousarray(wires, dtype=np.uint64)
+        p = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        out = (_WitnessFinding * max(cap, 1))()
+        n, rows, copies = ctypes.c_size_t(), ctypes.c_uint64(), ctypes.c_uint64()
+        self.gpu._check(self.gpu.lib.qpgpu_circuit_explain_witness(self.h, _ptr(wires) if on_device else wires.ctypes.data, 1 if on_device else 0,
+                                                                   p.ctypes.data, max_rows, 0, out, cap, ctypes.byref(n), ctypes.byref(rows), ctypes.byref(copies)))
+        found = [WitnessFinding(f.kind, f.gate, f.constraint, f.wire, f.wire_b, f.row, f.row_b, f.value, f.value_b) for f in out[:n.value]]
+        return found, rows.value, copies.value
 
     def set_quotient_fused(self, on=True):
         """Quotient stage: permutation terms and wire-local gates in one kernel where the gate list allows it (the default), or

@@ -45,8 +45,15 @@ hipError_t wk_fill_copies(const WitnessArgs &a, uint32_t batch, hipStream_t st);
 // wires[b * batch_stride + idx[i]] = vals[b * val_stride + i] (flat cell index = column * n + row); out[i] = wires[idx[i]]
 hipError_t wk_scatter(uint64_t *wires, const uint32_t *idx, const uint64_t *vals, uint32_t count, uint32_t batch, uint64_t batch_stride, uint32_t val_stride, hipStream_t st);
 hipError_t wk_gather(const uint64_t *wires, const uint32_t *idx, uint64_t *out, uint32_t count, hipStream_t st);
-// a partition set twice: err[2 * b + slot] = min over failing comparisons of (index), 0xFFFFFFFF = none (the caller presets it).
+// a partition set twice: err[WITNESS_ERR_STRIDE * b + slot] = min over failing comparisons of (index), 0xFFFFFFFF = none (the
+// caller presets it); slot 0 pairs, 1 vals, 2 nonzero, the fourth word of a witness's row is unused.
+constexpr uint32_t WITNESS_ERR_STRIDE = 4;
 // pairs: wires[own[i]] against wires[src[i]]; vals: wires[idx[i]] against vals[b * val_stride + i] (flat cells, canonical compare)
 hipError_t wk_check_nonzero(const uint64_t *wires, const uint32_t *a, const uint32_t *b, uint32_t count, uint32_t batch, uint64_t batch_stride, uint32_t *err, uint32_t slot, hipStream_t st);
 hipError_t wk_check_pairs(const uint64_t *wires, const uint32_t *own, const uint32_t *src, uint32_t count, uint32_t batch, uint64_t batch_stride, uint32_t *err, uint32_t slot, hipStream_t st);
 hipError_t wk_check_vals(const uint64_t *wires, const uint32_t *idx, const uint64_t *vals, uint32_t count, uint32_t batch, uint64_t batch_stride, uint32_t val_stride, uint32_t *err, uint32_t slot, hipStream_t st);
+
+// The copy classes of a circuit as the plan in place holds them on the device (the plan is built if there is none):
+// src_of[row * num_routed + wire] = flat cell (column * n + row) every member of that cell's class is filled from.
+struct qpgpu_circuit;
+int witness_plan_src_of(qpgpu_circuit *c, const uint32_t **d_src_of);

@@ -533,19 +533,19 @@ __global__ void __launch_bounds__(256) witness_check_pairs_kernel(const u64 *wir
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const u64 *w = wires + (u64)blockIdx.y * batch_stride;
-    if (gl::canon(w[own[i]]) != gl::canon(w[src[i]])) atomicMin(&err[4 * blockIdx.y + slot], i);
+    if (gl::canon(w[own[i]]) != gl::canon(w[src[i]])) atomicMin(&err[WITNESS_ERR_STRIDE * blockIdx.y + slot], i);
 }
 // a generator's divisor that is zero (see WitnessPlan::h_nz_a)
 __global__ void __launch_bounds__(256) witness_check_nonzero_kernel(const u64 *wires, const u32 *a, const u32 *b, u32 count, u64 batch_stride, u32 *err, u32 slot) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const u64 *w = wires + (u64)blockIdx.y * batch_stride;
-    if (gl::canon(w[a[i]]) == 0 && gl::canon(w[b[i]]) == 0) atomicMin(&err[4 * blockIdx.y + slot], i);
+    if (gl::canon(w[a[i]]) == 0 && gl::canon(w[b[i]]) == 0) atomicMin(&err[WITNESS_ERR_STRIDE * blockIdx.y + slot], i);
 }
 __global__ void __launch_bounds__(256) witness_check_vals_kernel(const u64 *wires, const u32 *idx, const u64 *vals, u32 count, u64 batch_stride, u32 val_stride, u32 *err, u32 slot) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    if (gl::canon(wires[(u64)blockIdx.y * batch_stride + idx[i]]) != gl::canon(vals[(u64)blockIdx.y * val_stride + i])) atomicMin(&err[4 * blockIdx.y + slot], i);
+    if (gl::canon(wires[(u64)blockIdx.y * batch_stride + idx[i]]) != gl::canon(vals[(u64)blockIdx.y * val_stride + i])) atomicMin(&err[WITNESS_ERR_STRIDE * blockIdx.y + slot], i);
 }
 
 }  // namespace

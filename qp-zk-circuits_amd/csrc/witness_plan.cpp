@@ -63,7 +63,7 @@ struct WitnessPlan {
     std::vector<uint32_t> h_nz_a, h_nz_b;
     std::vector<u64> h_nz_cell;
     uint32_t *d_nz_a = nullptr, *d_nz_b = nullptr;
-    uint32_t *d_err = nullptr; uint32_t err_cap = 0;     // [err_cap][4]: first failing index per check (secondary producers; assignments; zero inverses)
+    uint32_t *d_err = nullptr; uint32_t err_cap = 0;     // [err_cap][WITNESS_ERR_STRIDE]: first failing index per check (secondary producers; assignments; zero inverses)
     // a prepared PartialWitness shape (the cells a caller assigns are the same for every proof of a circuit): see PartialPrep
     struct PartialPrep *prep = nullptr;
 };
@@ -519,6 +519,12 @@ void host_pi_hash(const hasher::Config &h, const u64 *pis, size_t n, u64 out[4])
 
 }  // namespace
 
+int witness_plan_src_of(qpgpu_circuit *c, const uint32_t **d_src_of) {
+    if (!c->wplan) QP_TRY(ensure_plan(c));        // (the copy classes are the same in a plan of either kind; the source cells are the plan's)
+    *d_src_of = c->wplan->d_src_of;
+    return QPGPU_OK;
+}
+
 extern "C" {
 
 int qpgpu_witness_info(qpgpu_circuit *c, uint64_t *num_generators, uint64_t *num_levels, uint64_t *num_free_cells) {
@@ -583,7 +589,7 @@ int grow_pi(qpgpu_ctx *ctx, WitnessPlan &plan, uint32_t batch, size_t npis, bool
     QP_HIP(ctx, ctx->track_malloc((void **)&plan.d_pi_hash, (size_t)batch * 32, residue::WITNESS_PLAN));
     QP_HIP(ctx, ctx->track_malloc((void **)&plan.d_pi_vals, vals_bytes, residue::WITNESS_PLAN));
     plan.pi_vals_bytes = vals_bytes;
-    if (with_err) QP_HIP(ctx, ctx->track_malloc((void **)&plan.d_err, (size_t)batch * 16, residue::WITNESS_PLAN));
+    if (with_err) QP_HIP(ctx, ctx->track_malloc((void **)&plan.d_err, (size_t)batch * WITNESS_ERR_STRIDE * 4, residue::WITNESS_PLAN));
     plan.pi_cap = batch;
     if (with_err) plan.err_cap = batch;
     return QPGPU_OK;
@@ -713,7 +719,7 @@ int generate_batch(qpgpu_circuit *c, uint64_t *d_wires, uint32_t batch, const ui
         QP_HIP(ctx, wk_scatter(d_wires, pp->d_scatter_idx, pp->d_scatter_val, (uint32_t)ns, batch, stride, (uint32_t)ns, ctx->stream));
     }
     if (nc) QP_HIP(ctx, pk_copy(pp->d_check_val, ckv, ck_bytes, ctx->stream));
-    if (pair_checks || val_checks || nz_checks) QP_HIP(ctx, hipMemsetAsync(plan.d_err, 0xFF, (size_t)batch * 16, ctx->stream));
+    if (pair_checks || val_checks || nz_checks) QP_HIP(ctx, hipMemsetAsync(plan.d_err, 0xFF, (size_t)batch * WITNESS_ERR_STRIDE * 4, ctx->stream));
     WitnessArgs a{};
     a.wires = d_wires; a.src_of = plan.d_src_of; a.insts = plan.d_insts; a.gates = c->tab.d_gates; a.cs = c->d_cs_values;
     a.poseidon_rc = c->tab.d_poseidon_rc; a.poseidon_fast = c->d_poseidon_fast; a.pi_hash = plan.d_pi_hash;
@@ -751,17 +757,17 @@ int generate_batch(qpgpu_circuit *c, uint64_t *d_wires, uint32_t batch, const ui
     if (pp) pp->scrub(ctx->stream);
     wipe.queued = true;
     if (pair_checks || val_checks || nz_checks) {
-        std::vector<uint32_t> err((size_t)batch * 4);
+        std::vector<uint32_t> err((size_t)batch * WITNESS_ERR_STRIDE);
         QP_TRY(ctx->read_back(err.data(), plan.d_err, err.size() * 4));
         const u64 n = p.n();
         for (uint32_t b = 0; b < batch; b++) {
-            if (nz_checks && err[4 * b + 2] != 0xFFFFFFFFu) {      // first: the value such a generator wrote is what the other two checks would trip over
-                flag(b, "a generator inverts " + name(plan.h_nz_cell[err[4 * b + 2]]) + ", which is zero (a quotient's denominator or an interpolation's coset shift)");
-            } else if (pair_checks && err[4 * b] != 0xFFFFFFFFu) {
-                const uint32_t own = plan.h_check_own[err[4 * b]];
+            if (nz_checks && err[WITNESS_ERR_STRIDE * b + 2] != 0xFFFFFFFFu) {      // first: the value such a generator wrote is what the other two checks would trip over
+                flag(b, "a generator inverts " + name(plan.h_nz_cell[err[WITNESS_ERR_STRIDE * b + 2]]) + ", which is zero (a quotient's denominator or an interpolation's coset shift)");
+            } else if (pair_checks && err[WITNESS_ERR_STRIDE * b] != 0xFFFFFFFFu) {
+                const uint32_t own = plan.h_check_own[err[WITNESS_ERR_STRIDE * b]];
                 flag(b, name((u64)(own % n) * NW + own / n) + " set twice with different values (two generators of one copy class disagree)");
-            } else if (val_checks && err[4 * b + 1] != 0xFFFFFFFFu) {
-                const uint32_t k = err[4 * b + 1], from = pp->check_from[k];
+            } else if (val_checks && err[WITNESS_ERR_STRIDE * b + 1] != 0xFFFFFFFFu) {
+                const uint32_t k = err[WITNESS_ERR_STRIDE * b + 1], from = pp->check_from[k];
                 const u64 v = gl::canon(from < npis ? public_inputs[(size_t)b * npis + from] : part_values[(size_t)b * count + (from - npis)]);
                 flag(b, name(pp->check_cell[k]) + " set twice with different values (" + std::to_string(v) + " supplied, another value generated)");
             }

@@ -476,6 +476,21 @@ class LeafCircuit:
             cells.append(self.blinding_cells)
         return np.concatenate(cells), np.concatenate(values), self.public_inputs(pis)
 
+    def describe(self, finding):
+        """binding.format_finding's line for a Circuit.explain_witness finding of this circuit; for a COPY finding, followed by the logical
+        targets (indices into target_map: the LT_* numbering of include/qpgpu_leaf.h, plus LT_COUNT per copy) that sit on either of
+        its two cells. A reverse lookup of target_map, nothing more."""
+        from .binding import FINDING_COPY, format_finding
+        line = format_finding(self.pack, finding)
+        if finding.kind != FINDING_COPY:
+            return line
+        nw = int(self.pack[2])                                          # header word 2: num_wires
+        for what, cell in (("cell", finding.row * nw + finding.wire), ("source", finding.row_b * nw + finding.wire_b)):
+            hits = [int(i) for i in np.nonzero(self.target_map == np.uint64(cell))[0]]
+            if hits:
+                line += "; %s = logical target%s %s" % (what, "" if len(hits) == 1 else "s", ", ".join(str(i) for i in hits))
+        return line
+
     def public_inputs(self, pis21):
         """The circuit's own public inputs out of the leaf's 21 (a fragment circuit registers only some of them)."""
         if self.fragment == FRAGMENT_FULL:
